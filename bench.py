@@ -19,6 +19,11 @@ Besides the headline (C2) the line carries, at N = 1 only (`--legs none` drops t
     beam 20, 20 users, V=32600), C5 per-GPU (T5-large, L=512) -- and `task_mix`, the real alternation of sequential
     (L~130) and straightforward (L~16) batches through datasets + sampler + collator + prefetch thread
     (SingleMultiDataTaskSampler.py:55-71).
+
+`--dump-outputs DIR` writes, on rank 0, what the timed path computed: the loss of the last timed training step, the norm of every
+parameter tensor after it and a fixed, seeded sample of the parameter values (`train_*.npy`), and the sequences and scores of the last
+timed headline generation call (`generation_*.npy`, unless --no-gen).  Inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -129,6 +134,9 @@ def train_step(model, opt, batch):
     return training_step(model, opt, batch, alpha=2)
 
 
+STAGED_STEPS = 20      # steps of the staged-backward leg (outside the headline)
+
+
 def time_training(model, opt, batch, steps, warmup, world, device):
     model.train()
     last = None
@@ -141,6 +149,36 @@ def time_training(model, opt, batch, steps, warmup, world, device):
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, device)
     return dt, float(last.detach())
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 1 << 22      # fp32 parameters kept of the ~61M (16 MB)
+DUMP_SEED = 20231
+
+
+def dump_arrays(out_dir, arrays):
+    """--dump-outputs: each array as <out_dir>/<name>.npy, float32 or float64, at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+@torch.no_grad()
+def training_outputs(model, loss):
+    """What a caller of the training step has after the last timed step: the loss it returned and the updated parameters -- the norm of
+    every parameter tensor (named_parameters order, fp64) and the values at a fixed, seeded sample of positions of their concatenation."""
+    import numpy as np
+    params = [p.detach().reshape(-1) for _, p in model.named_parameters()]
+    flat = torch.cat(params)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_PARAM_SAMPLE, flat.numel()),), generator=g).sort().values
+    return {"train_loss": np.asarray(loss, dtype=np.float64),
+            "train_param_norms": torch.stack([p.double().norm() for p in params]).cpu().numpy(),
+            "train_param_sample": flat[idx.to(flat.device)].float().cpu().numpy()}
 
 
 def profile_training(be, model, opt, batch, steps=3):
@@ -178,10 +216,11 @@ def kernel_classes(rows):
     return sorted(cls.values(), key=lambda c: -c["us_per_step"])
 
 
-def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, seed, vocab=V, mode=None):
+def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, seed, vocab=V, mode=None, keep=None):
     """`batches` generate() calls of `gB` users, beam `gK`, bracketed like the training step (barrier + synchronize).  mode (bf16 models):
     "verified" = the bf16 search with extra beams proposes, one fp32 pass decides (lists and scores are the fp32 search's: csrc/p5_verify.h),
-    "draft" = the plain bf16 search.  Returns (seconds, decoded length, engine timing of the search kernels, per-call median ms, stats)."""
+    "draft" = the plain bf16 search.  Returns (seconds, decoded length, engine timing of the search kernels, per-call median ms, stats);
+    a dict `keep` receives the sequences and scores of the last timed call."""
     from openp5_amd.trie import prefix_allowed_tokens_fn
     model.eval()
     if mode is not None:
@@ -207,6 +246,8 @@ def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, 
         pass
     barrier(world)
     gdt = max_over_ranks(time.perf_counter() - g0, world, device)
+    if keep is not None:          # what the last timed call returned (copied before the untimed calls below run)
+        keep.update(sequences=o["sequences"].clone(), sequences_scores=o["sequences_scores"].clone())
     stats = dict(model.verify_stats)
     # per-call wall times (each call ends with the read of the result lengths, i.e. is synchronous) and the device time of the search's
     # decode loop alone (engine-side HIP events around it), both on extra calls OUTSIDE the timed region
@@ -700,7 +741,11 @@ def main():
     ap.add_argument("--legs", default="all", help="all | none | comma list of: configs,task_mix")
     ap.add_argument("--gen-batches", type=int, default=20)
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc subprocess passes (roofline.traffic / mfma_busy then come from profiles/*.json, marked stale)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed training step (and the last timed headline generation call) returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -717,15 +762,18 @@ def main():
     batch = synth_batch(B, L, T, device, 100 + rank)
     dt, final_loss = time_training(model, opt, batch, args.steps, args.warmup, world, device)
     samples_per_s = world * B * args.steps / dt
+    dumps = training_outputs(model, final_loss) if (args.dump_outputs and rank == 0) else None      # before any untimed step changes the model
     prof_rows = profile_training(be, model, opt, batch) if (rank == 0 and world == 1) else None      # outside the timed region
     staged = None
     if world == 1 and args.legs != "none":
         # the data-parallel code path on ONE GPU: stage-by-stage backward (16 engine calls, gradient ranges reported per stage, the same
         # two-layer weight-gradient groups), no collective -- what staging itself costs against the single-call backward timed above
+        # (a fixed number of steps: --steps sizes the timed headline only, so that a run sized from ms_per_step takes K x ms_per_step
+        #  plus a constant, not twice that)
         model.staged_backward = True
-        sdt, _ = time_training(model, opt, batch, args.steps, 2, 1, device)
+        sdt, _ = time_training(model, opt, batch, STAGED_STEPS, 2, 1, device)
         model.staged_backward = False
-        staged = {"ms_per_step": sdt / args.steps * 1e3, "samples_per_s": B * args.steps / sdt, "steps": args.steps,
+        staged = {"ms_per_step": sdt / STAGED_STEPS * 1e3, "samples_per_s": B * STAGED_STEPS / sdt, "steps": STAGED_STEPS,
                   "note": "p5_backward_stage x 16 + p5_backward_final_range per stage, world size 1, no all-reduce"}
     comm_wait_ms = None
     if world > 1:
@@ -750,7 +798,10 @@ def main():
         # which no lower-precision proposer can know the fp32 top-K -- that number is reported too (`generation_after_noise_training`)
         trained = model
         _, model, _ = build_model(args.backbone, args.dtype, device, be, world, rank)
-        gdt, dec_len, timing, med, vst = time_generation(model, gB, gK, L, trie, 30, args.gen_batches, world, device, 500 + rank, mode="verified")
+        kept = {}
+        gdt, dec_len, timing, med, vst = time_generation(model, gB, gK, L, trie, 30, args.gen_batches, world, device, 500 + rank, mode="verified", keep=kept)
+        if dumps is not None:         # token ids < 2^24: exact in float32
+            dumps.update(generation_sequences=kept["sequences"].float().cpu().numpy(), generation_sequences_scores=kept["sequences_scores"].float().cpu().numpy())
         gen = {"mode": "verified (bf16 search with 6 extra beams proposes, one teacher-forced fp32 pass decides; csrc/p5_verify.h)",
                "items_per_s": world * gB * gK * args.gen_batches / gdt, "ms_per_batch": gdt / args.gen_batches * 1e3, "ms_per_batch_median_call": med,
                "lanes": vst.get("lanes"), "timing_note": "ms_per_batch = timed region / batches with `lanes` batches in flight (throughput); ms_per_batch_median_call = one "
@@ -916,6 +967,8 @@ def main():
             if not args.no_cpu:
                 line["cpu_baseline"] = cpu_baseline_train_hf() or cpu_baseline_train()      # stock HF when transformers is importable, else the oracle port
                 line["cpu_baseline_generation"] = cpu_baseline_generation()
+        if dumps is not None:
+            dump_arrays(args.dump_outputs, dumps)
         print(json.dumps(line), flush=True)
     if world > 1:
         barrier(world)      # rank 0 times its stand-alone kernels after the last collective: the others wait here, then all tear down together

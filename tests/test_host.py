@@ -1,10 +1,10 @@
 """not-gpu: host-side logic of the path (collator, trie, metrics, prompts, samplers, datasets) -- known-answer values
-from SURVEY.md App. D and, when /root/reference is present (build container only), equality with the reference's own
-modules run on the same inputs."""
+from SURVEY.md App. D and equality with what the reference's own modules return on the same inputs (stored in
+tests/golden/host_reference.json by tests/golden/make_host_reference.py)."""
 import argparse
+import json
 import os
 import random
-import sys
 
 import numpy as np
 import pytest
@@ -20,8 +20,7 @@ from openp5_amd.trie import CompiledTrie, Trie, find_trie, prefix_allowed_tokens
 from openp5_amd.utils import utils
 from openp5_amd.utils.prompt import get_info_from_prompt, load_prompt_template
 
-REF = "/root/reference/src/src_t5"
-HAVE_REF = os.path.isdir(REF)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "host_reference.json")
 
 
 @pytest.fixture(scope="module")
@@ -29,12 +28,11 @@ def tok():
     return build_offline_tokenizer()
 
 
-def ref_module(name):
-    sys.dont_write_bytecode = True
-    if REF not in sys.path:
-        sys.path.append(REF)
-    import importlib
-    return importlib.import_module(name)
+@pytest.fixture(scope="module")
+def ref():
+    """the reference modules' answers on the inputs below (tests/golden/make_host_reference.py)"""
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def test_whole_word_ids_kat():
@@ -59,17 +57,15 @@ def test_collator_matches_scalar_definition(tok):
     assert TestCollator(tok)(batch)[5].tolist() == [0, 0, 3]
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
-def test_whole_word_ids_equals_reference(tok):
-    ref = ref_module("processor.Collator")
-    rnd = random.Random(0)
-    for _ in range(50):
-        n = rnd.randint(2, 30)
-        ids = [rnd.randint(3, 400) for _ in range(n)] + [1] + [0] * rnd.randint(0, 5)
+def test_whole_word_ids_equals_reference(tok, ref):
+    cases = ref["whole_word_ids"]
+    assert len(cases) == 50
+    for c in cases:
+        ids, want = c["ids"], c["whole_word_ids"]
         pieces = tok.convert_ids_to_tokens(ids)
-        assert calculate_whole_word_ids(pieces, ids) == ref.calculate_whole_word_ids(pieces, ids)
+        assert calculate_whole_word_ids(pieces, ids) == want
         got = Collator(tok).whole_word_ids(np.asarray([ids]))[0].tolist()
-        assert got == ref.calculate_whole_word_ids(pieces, ids)
+        assert got == want
 
 
 def test_trie_kat_and_csr():
@@ -87,17 +83,14 @@ def test_trie_kat_and_csr():
     assert fn(0, torch.tensor([0, 5])) == t.get([0, 5]) and find_trie(fn) is t
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
-def test_trie_equals_reference():
-    gt = ref_module("utils.generation_trie")
-    rnd = random.Random(1)
-    seqs = [[0] + [rnd.randint(2, 9) for _ in range(rnd.randint(1, 5))] + [1] for _ in range(200)]
-    a, b = Trie(seqs), gt.Trie(seqs)
-    assert len(a) == len(b)
-    for _ in range(500):
-        pre = rnd.choice(seqs)[: rnd.randint(0, 6)]
-        assert sorted(a.get(pre)) == sorted(b.get(pre))
-    assert find_trie(gt.prefix_allowed_tokens_fn(b)) is b      # the reference's closure is recognised -> device path
+def test_trie_equals_reference(ref):
+    r = ref["trie"]
+    a = Trie(r["sequences"])
+    assert len(a) == r["len"] and len(r["queries"]) == 500
+    for q in r["queries"]:
+        assert sorted(a.get(q["prefix"])) == q["allowed"]
+    closure = (lambda t: lambda batch_id, sentence: t.get(sentence.tolist()))(a)     # a plain closure over the trie, the reference's style
+    assert not hasattr(closure, "candidate_trie") and find_trie(closure) is a      # is recognised -> device path
 
 
 def test_metrics_kat():
@@ -107,23 +100,17 @@ def test_metrics_kat():
     assert np.allclose(res, [0.0, 1.0, 0.63092975])
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
-def test_metrics_equal_reference():
-    ref = ref_module("utils.evaluate")
-    rnd = random.Random(2)
-    k, B = 10, 30
-    preds = [f"i{rnd.randint(0, 40)}" for _ in range(B * k)]
-    gold = [f"i{rnd.randint(0, 40)}" for _ in range(B)]
-    scores = [rnd.random() for _ in range(B * k)]
-    assert evaluate.rel_results(preds, gold, scores, k) == ref.rel_results(preds, gold, scores, k)
-    ms = ['hit@5', 'hit@10', 'ndcg@5', 'ndcg@10']
+def test_metrics_equal_reference(ref):
+    r = ref["metrics"]
+    k, preds, gold, scores, ms = r["k"], r["predictions"], r["gold"], r["scores"], r["metrics"]
+    B = len(gold)
     rel = evaluate.rel_results(preds, gold, scores, k)
-    assert np.allclose(evaluate.get_metrics_results(rel, ms), ref.get_metrics_results(rel, ms))
-    pos = {f"u{b}": set(rnd.sample(preds, 5)) for b in range(B)}
+    assert rel == r["rel_results"]
+    assert np.allclose(evaluate.get_metrics_results(rel, ms), r["metrics_results"])
+    pos = {u: set(v) for u, v in r["positive"].items()}
     id2user = {b: f"u{b}" for b in range(B)}
-    a = evaluate.rel_results_filtered(pos, id2user, list(range(B)), k, preds, gold, scores, 5)
-    b_ = ref.rel_results_filtered(pos, id2user, list(range(B)), k, preds, gold, scores, 5)
-    assert a == b_
+    a = evaluate.rel_results_filtered(pos, id2user, list(range(B)), k, preds, gold, scores, r["filter_k"])
+    assert a == r["rel_results_filtered"]
 
 
 SMALL_TOY = dict(n_users=12, n_items=24, n_inter=90)     # a third of the Toy set: the emulated-kernel runner tests that only need "some epochs"
@@ -193,30 +180,23 @@ def test_samplers(tmp_path):
     assert len(set(shards[0]) & set(shards[1])) == 0
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not present")
-def test_dataset_and_sampler_equal_reference(tmp_path):
-    """Same toy data + flags through the reference's own MultiTaskDataset / TestDataset / samplers."""
+def test_dataset_and_sampler_equal_reference(tmp_path, ref):
+    """Same toy data + flags as the reference's own MultiTaskDataset / TestDataset / samplers were given."""
     from torch.utils.data import ConcatDataset
-    RD = ref_module("data.MultiTaskDataset")
-    RT = ref_module("data.TestDataset")
-    RS = ref_module("processor.DistMultiDataTaskSampler")
+    r = ref["dataset_and_sampler"]
     a1 = make_args(str(tmp_path / "a"))
-    a2 = make_args(str(tmp_path / "b"))
-    for a in (a1, a2):
-        a.test_filtered = 0
+    a1.test_filtered = 0
     random.seed(5)
     mine = MultiTaskDataset(a1, "Toy", "train")
-    random.seed(5)
-    ref = RD.MultiTaskDataset(a2, "Toy", "train")
-    assert mine.data["input"] == ref.data["input"] and mine.data["output"] == ref.data["output"]
-    assert mine.task_index == ref.task_index and mine.item_map == ref.item_map
-    tm, tr = TestDataset(a1, "Toy", "straightforward"), RT.TestDataset(a2, "Toy", "straightforward")
-    assert tm.data == tr.data and tm.all_items == tr.all_items
-    for epoch in (0, 1):
+    assert mine.data["input"] == r["train_input"] and mine.data["output"] == r["train_output"]
+    assert mine.task_index == r["task_index"] and mine.item_map == r["item_map"]
+    tm = TestDataset(a1, "Toy", "straightforward")
+    assert tm.data == r["test_data"] and tm.all_items == r["test_all_items"]
+    assert [s["epoch"] for s in r["sampler"]] == [0, 1]
+    for s in r["sampler"]:
         sm = DistMultiDataTaskSampler(ConcatDataset([mine]), 4, 2, 1, seed=2023)
-        sr = RS.DistMultiDataTaskSampler(ConcatDataset([ref]), 4, 2, 1, seed=2023)
-        sm.set_epoch(epoch); sr.set_epoch(epoch)
-        assert list(iter(sm)) == list(iter(sr)) and len(sm) == len(sr)
+        sm.set_epoch(s["epoch"])
+        assert list(iter(sm)) == s["indices"] and len(sm) == s["len"]
 
 
 def test_word_cache_encoder_equals_tokenizer(tok, tmp_path):
