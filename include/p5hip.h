@@ -159,6 +159,14 @@ int p5_engine_adamw_step(P5Engine* e, float* m, float* v, const float* sumsq, do
 int64_t p5_decode_fold_count(const P5Engine* e);
 int p5_engine_bind_decode_fold(P5Engine* e, void* buf);
 int p5_refresh_decode_fold(P5Engine* e, void* stream);
+/* Exact workspace of p5_generate / p5_decode_begin (R = B*K rows, C = min(max_children, 2K), every block rounded up to 256 bytes):
+ * the encoder / forced-prefix buffers, cross-attention K/V, the step KV cache (n_dec_layers x max_len x R x 2 x inner x sizeof(T)),
+ * the decode-step activations, per-row head partials and candidate scratch (R x max_children fp32), the beam state, and
+ *   K <= 64:                 the narrow candidate lists, 2 x R x 2K x 4 bytes, and the [R, V] fp32 logits;
+ *   K > 64:                  no narrow lists; the [R, V] logits only where the head is not the streaming one (toy d_model);
+ *   K > 64 or gen_wide = 1:  the wide step's buffers behind everything else: R x C x 8 (row candidate keys) + R x 4 (counts)
+ *                            + 4 x R x 2 x 4 (the items' top-2K scores / beams / tokens / nodes) + 2 x R x 4 (running selection, finished sources).
+ * The size depends on the gen_wide option at the time of the call: query it under the option the search runs with. */
 int64_t p5_generate_workspace_bytes(const P5Engine* e, int B, int L, int K, int max_len, int max_children, int excluded_words);
 /* trie in CSR: child_off[n_nodes+1], child_tok/child_node[n_edges]; node 0 = empty prefix.
  * out_seq int32 [B,K,max_len] (pad-filled, starts with pad=decoder start), out_score fp32 [B,K], out_len int32 [B,K].
@@ -168,8 +176,12 @@ int64_t p5_generate_workspace_bytes(const P5Engine* e, int B, int L, int K, int 
  * Replaces P5_T5.generate(...) = HF beam search + PrefixConstrainedLogitsProcessor (DistributedRunner.py:361-371).
  * Enqueues the whole search and returns WITHOUT synchronising: HF's stop test is taken on the device, so no step reads
  * anything back.  max_len bounds the number of decode steps enqueued (max_len - 1): pass min(max_length, depth of the trie).
- * Limits: 1 <= K <= 64 beams, 2 <= max_len <= 128; the trie may be any DAG in this CSR form (an appended trie, generation_trie.py:19-21,
- * is grafted by the caller -- openp5_amd/trie.py::CompiledTrie.from_trie). */
+ * Limits: 1 <= K <= 4096 beams, 2 <= max_len <= 128; the trie may be any DAG in this CSR form (an appended trie, generation_trie.py:19-21,
+ * is grafted by the caller -- openp5_amd/trie.py::CompiledTrie.from_trie).  K <= 64 runs the narrow beam step (openp5_amd/csrc/p5_decode.h:
+ * an item's state and candidate pool in one workgroup's LDS); 65 <= K <= 4096 the wide one (p5_decode_wide.h: exact top-2K by radix select
+ * + sort, beam state in global memory), which returns what the narrow step returns, bit for bit, where both run -- p5_set_option("gen_wide", 1)
+ * selects it at any K (a test / benchmark hook; part of the decode-step hipGraph key).  p5_generate_draft and the p5_verify_* calls keep
+ * K <= 64 (draft searches always take the narrow step). */
 int p5_generate(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask,
                 int B, int L, int K, int max_len, const int* child_off, const int* child_tok, const int* child_node,
                 const int* roots /* [B] empty-prefix node per batch item, or NULL = node 0 */,

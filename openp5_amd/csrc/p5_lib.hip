@@ -20,6 +20,7 @@
 #include "p5_embed.h"
 #include "p5_decode.h"
 #include "p5_decode2.h"
+#include "p5_decode_wide.h"
 #include "p5_verify.h"
 #include "../../include/p5hip.h"
 
@@ -42,6 +43,7 @@ static int g_opt_dec_atomic = getenv("P5_DEC_ATOMIC") ? atoi(getenv("P5_DEC_ATOM
 static int g_opt_adam_tiles = getenv("P5_ADAM_TILES") ? atoi(getenv("P5_ADAM_TILES")) : 1;       // p5_engine_adamw_step: tile-wise update that also writes W^T and W diag(ln)
 static int g_opt_gen_ff = getenv("P5_GEN_FF") ? atoi(getenv("P5_GEN_FF")) : 1;             // forced-prefix fast-forward (p5_decode.h): 0 = every step is a decode step
 static int g_opt_dec_head_nv = getenv("P5_DEC_HEAD_NV") ? atoi(getenv("P5_DEC_HEAD_NV")) : 0;   // streaming head: forced E rows per workgroup (0 = auto)
+static int g_opt_gen_wide = getenv("P5_GEN_WIDE") ? atoi(getenv("P5_GEN_WIDE")) : 0;       // 1 = the wide search (p5_decode_wide.h) at every width, not only K > 64
 
 __global__ __launch_bounds__(256) void p5_shift_right_kernel(int64_t* out, const int64_t* labels, int B, int T, int64_t start) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -92,7 +94,7 @@ struct Bump {
   }
 };
 
-struct GraphKey { int B, L, K, max_len, max_c, excl_words; const void *ws, *trie, *trie_tok, *trie_node, *roots, *P, *S, *fold, *hist; int sz, fused; };
+struct GraphKey { int B, L, K, max_len, max_c, excl_words; const void *ws, *trie, *trie_tok, *trie_node, *roots, *P, *S, *fold, *hist; int sz, fused, wide; };
 
 struct GenWs {
   void* kv_cross[64];   // per decoder layer: T [B*L, ldkv] -- column slices of ONE [B*L, n_dec*2*inner] block in the latency-shaped path
@@ -107,6 +109,8 @@ struct GenWs {
   uint32_t* excluded;     // [B, excl_words] copy of the caller's per-item excluded-node bitmap (stable address for the graph)
   int64_t* ff_labels; float* ff_nll;     // forced-prefix pass: its labels [B, F] and per-token NLL
   P5BeamState st;
+  P5WideWs wide;          // wide search (p5_decode_wide.h): null pointers unless the layout holds it
+  int wide_c;             // its per-row candidate capacity min(max_c, 2K)
 };
 
 // state of the search between p5_decode_begin and p5_decode_finish (the workspace layout, the trie, the step counter)
@@ -114,6 +118,7 @@ struct GenCtx {
   bool active = false;
   GenWs w;
   int B = 0, L = 0, K = 0, max_len = 0, max_c = 0, excl_words = 0, steps = 0, steps0 = 0;     // steps0: steps covered by the forced-prefix pass
+  bool wide = false;      // this search runs the wide step (p5_decode_wide.h)
   const int *child_off = nullptr, *child_tok = nullptr, *child_node = nullptr, *roots = nullptr;
   char* ws = nullptr;
 };
@@ -1302,6 +1307,12 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
 
 // ---- generation ------------------------------------------------------------------------------------------
 
+static int head_nv(const P5Engine* e);
+// which step a search of K beams runs: the narrow one (p5_decode.h, K <= 64) or the wide one (p5_decode_wide.h: K > 64, or any K under
+// the gen_wide option -- except for p5_generate_draft, whose history recording only the narrow step does)
+static bool gen_wide_layout(int K) { return K > P5_MAX_K || g_opt_gen_wide != 0; }
+static bool gen_wide_run(int K, const int* hist) { return K > P5_MAX_K || (g_opt_gen_wide != 0 && hist == nullptr); }
+
 static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_len, int max_c, int excl_words, GenWs* g) {
   const P5Config& c = e->c;
   const size_t sz = c.dtype == 1 ? 2 : 4;
@@ -1328,15 +1339,17 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
   w.qkv = b.take(R * 3 * in * sz); w.q = b.take(R * in * sz); w.o = b.take(R * in * sz);
   w.h = b.take(R * (c.gated_gelu ? 3 : 1) * F * sz); w.hn = b.take(R * d * sz);
   w.x32 = (float*)b.take(R * d * 4);
-  w.logits = (float*)b.take(R * Vp * 4);
+  // (beyond 64 beams only the wide step runs: no narrow candidate lists, and no [R, V] logits when the head streams)
+  const bool narrow = K <= P5_MAX_K;
+  w.logits = (float*)b.take(narrow || head_nv(e) == 0 ? R * Vp * 4 : 0);
   w.ssq = (float*)b.take((size_t)(3 * c.n_dec_layers + 1) * R * 4);
   w.cand = (float*)b.take(R * (size_t)max_c * 4);
   w.cand_key = (int*)b.take(R * (size_t)max_c * 4);
   w.part_m = (float*)b.take(R * (size_t)((c.vocab_size + 15) / 16) * 4);
   w.part_s = (float*)b.take(R * (size_t)((c.vocab_size + 15) / 16) * 4);
   w.n_cand = (int*)b.take(R * 4);
-  w.row_top_score = (float*)b.take(R * (size_t)(2 * K) * 4);
-  w.row_top_c = (int*)b.take(R * (size_t)(2 * K) * 4);
+  w.row_top_score = (float*)b.take(narrow ? R * (size_t)(2 * K) * 4 : 0);
+  w.row_top_c = (int*)b.take(narrow ? R * (size_t)(2 * K) * 4 : 0);
   w.mask_copy = (int64_t*)b.take((size_t)B * L * 8);
   w.excluded = (uint32_t*)b.take((size_t)B * (excl_words > 0 ? excl_words : 0) * 4 + 16);
   P5BeamState& st = w.st;
@@ -1353,6 +1366,21 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
   st.E32 = e->P ? e->P + e->off_E : nullptr;
   st.d = d;
   st.hist = nullptr;
+  // wide step (p5_decode_wide.h), behind everything above so that the narrow buffers keep their offsets under the gen_wide option
+  memset(&w.wide, 0, sizeof(w.wide));
+  w.wide_c = 0;
+  if (gen_wide_layout(K)) {
+    const int C = max_c < 2 * K ? max_c : 2 * K;
+    w.wide_c = C;
+    w.wide.row_key = (unsigned long long*)b.take(R * (size_t)C * 8);
+    w.wide.row_n = (int*)b.take(R * 4);
+    w.wide.top_lp = (float*)b.take(R * 2 * 4);
+    w.wide.top_beam = (int*)b.take(R * 2 * 4);
+    w.wide.top_tok = (int*)b.take(R * 2 * 4);
+    w.wide.top_node = (int*)b.take(R * 2 * 4);
+    w.wide.sel_run = (int*)b.take(R * 4);
+    w.wide.fin_src = (int*)b.take(R * 4);
+  }
   return (int64_t)((b.off + 255) & ~(size_t)255);
 }
 
@@ -1653,6 +1681,7 @@ static int decode_begin_impl(P5Engine* e, int B, int L, int K, int max_len, cons
   g.B = B; g.L = L; g.K = K; g.max_len = max_len; g.max_c = max_c; g.excl_words = excl_words; g.ws = ws;
   g.child_off = child_off; g.child_tok = child_tok; g.child_node = child_node; g.roots = roots;
   g.steps = F; g.steps0 = F;
+  g.wide = gen_wide_run(K, w.st.hist);
   g.active = true;
   return 0;
 }
@@ -1684,6 +1713,36 @@ static int decode_step_body(P5Engine* e, hipStream_t s) {
   return P5_KCHECK();
 }
 
+// the wide step (p5_decode_wide.h): same decoder and head; scoring, selection and the scorer with their state in global memory
+template <class T>
+static int decode_step_wide(P5Engine* e, hipStream_t s) {
+  const P5Config& c = e->c;
+  GenCtx& g = e->gen;
+  GenWs& w = g.w;
+  const int d = c.d_model, B = g.B, L = g.L, K = g.K, R = B * K, max_len = g.max_len, max_c = g.max_c, excl_words = g.excl_words, C = w.wide_c;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  const uint32_t* excl = excl_words > 0 ? w.excluded : nullptr;
+  const int* done = w.st.flags + 4;
+  if (g_opt_decode_v2) P5_TRY(decode_step2<T>(e, w, B, L, K, max_len, s));
+  else P5_TRY(decode_step<T>(e, w, B, L, K, max_len, s));
+  if (head_nv(e) > 0) {
+    const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
+    P5_LAUNCH((p5_wide_score2_kernel<T>), dim3(R), dim3(256), 0, s, w.wide.row_key, w.wide.row_n, w.cand, (const float*)w.part_m,
+              (const float*)w.part_s, nt, (const T*)w.hn, Wc<T>(e, e->off_E), d, 1.0f / sqrtf((float)d), (const int*)w.st.run_node,
+              (const float*)w.st.run_score, g.child_off, g.child_tok, g.child_node, excl, excl_words, K, max_c, C, done);
+  } else {
+    P5_LAUNCH(p5_wide_score_kernel, dim3(R), dim3(256), 0, s, w.wide.row_key, w.wide.row_n, w.cand, (const float*)w.logits, Vp, c.vocab_size,
+              (const int*)w.st.run_node, (const float*)w.st.run_score, g.child_off, g.child_tok, g.child_node, excl, excl_words, K, max_c, C, done);
+  }
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_wide_select_kernel, dim3(B), dim3(256), 0, s, w.st, w.wide, g.child_off, g.child_tok, g.child_node, max_c, K, C, max_len, c.eos_id);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_wide_scorer_kernel, dim3(B), dim3(256), 0, s, w.st, w.wide, K, max_len, c.eos_id);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_wide_commit_kernel, dim3((K + P5_WIDE_COMMIT_BEAMS - 1) / P5_WIDE_COMMIT_BEAMS, B), dim3(256), 0, s, w.st, w.wide, K, max_len, R);
+  return P5_KCHECK();
+}
+
 // One beam-search step: the whole decoder over R = B*K rows, the tied head, HF's candidate selection and bookkeeping.  Nothing
 // is read back: HF's global stop test (utils.py:3055-3075) is taken on the device by the beam step, which raises flags[4]; a
 // step enqueued after that returns at once in every kernel.  From the second step of a call on, the step is replayed from a
@@ -1699,7 +1758,7 @@ static int decode_step_impl(P5Engine* e, hipStream_t s) {
   memset(&key, 0, sizeof(key));
   key.B = g.B; key.L = g.L; key.K = g.K; key.max_len = g.max_len; key.max_c = g.max_c; key.excl_words = g.excl_words; key.ws = g.ws;
   key.trie = g.child_off; key.trie_tok = g.child_tok; key.trie_node = g.child_node; key.roots = g.roots;
-  key.P = e->P; key.S = e->S; key.sz = (int)sizeof(T); key.fold = e->fold; key.hist = g.w.st.hist;
+  key.P = e->P; key.S = e->S; key.sz = (int)sizeof(T); key.fold = e->fold; key.hist = g.w.st.hist; key.wide = g.wide ? 1 : 0;
   key.fused = g_opt_decode_fused + 2 * g_opt_decode_v2 + 4 * g_opt_dec_fuseq + 8 * g_opt_dec_nb + 4096 * g_opt_dec_kw + (g_opt_dec_cross << 20) +
               (g_opt_dec_head << 23) + (g_opt_dec_head_nv << 24) + ((g.steps0 > 0 ? 1 : 0) << 30) + (g_opt_dec_atomic << 29);     // (forced-prefix pass: the cross K/V live elsewhere)
   bool have_graph = use_graph && e->gen_graph_exec && memcmp(&key, &e->gen_graph_key, sizeof(key)) == 0;
@@ -1709,7 +1768,7 @@ static int decode_step_impl(P5Engine* e, hipStream_t s) {
     if (e->gen_graph_exec) { hipGraphExecDestroy(e->gen_graph_exec); e->gen_graph_exec = nullptr; }
     hipGraph_t graph = nullptr;
     if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
-      const int rc = decode_step_body<T>(e, s);
+      const int rc = g.wide ? decode_step_wide<T>(e, s) : decode_step_body<T>(e, s);
       const hipError_t ec = hipStreamEndCapture(s, &graph);
       if (rc == 0 && ec == hipSuccess && graph && hipGraphInstantiate(&e->gen_graph_exec, graph, nullptr, nullptr, 0) == hipSuccess) {
         e->gen_graph_key = key;
@@ -1728,7 +1787,7 @@ static int decode_step_impl(P5Engine* e, hipStream_t s) {
     return 0;
   }
 #endif
-  P5_TRY(decode_step_body<T>(e, s));
+  P5_TRY(g.wide ? decode_step_wide<T>(e, s) : decode_step_body<T>(e, s));
   g.steps++;
   return 0;
 }
@@ -2206,6 +2265,7 @@ int p5_set_option(const char* name, int value) {
   else if (!strcmp(name, "dec_head_nv")) g_opt_dec_head_nv = value;
   else if (!strcmp(name, "verify_split")) g_opt_verify_split = value;
   else if (!strcmp(name, "gen_ff")) g_opt_gen_ff = value;
+  else if (!strcmp(name, "gen_wide")) g_opt_gen_wide = value;
   else if (!strcmp(name, "dec_atomic")) g_opt_dec_atomic = value;
   else if (!strcmp(name, "wgrad_group")) g_opt_wgrad_group = value;
   else if (!strcmp(name, "norm_fuse")) g_opt_norm_fuse = value;
@@ -2733,7 +2793,7 @@ int p5_decode_begin(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
                     int max_len, const int* child_off, const int* child_tok, const int* child_node, const int* roots,
                     const uint32_t* excluded_nodes, int excluded_words, int max_children, void* ws, int64_t ws_bytes, void* stream) {
   P5_REQUIRE(e->P, "engine not bound");
-  P5_REQUIRE(K >= 1 && K <= 64, "1 <= num_beams <= 64");
+  P5_REQUIRE(K >= 1 && K <= P5_WIDE_MAX_K, "1 <= num_beams <= 4096");
   P5_REQUIRE(max_len >= 2 && max_len <= P5_MAX_LEN, "2 <= max_length <= 128 (P5_MAX_LEN)");
   P5_REQUIRE(max_len <= 64 || g_opt_decode_v2, "max_length > 64 needs the decode_v2 step (the first-generation self-attention kernel keeps one score per lane)");
   P5_REQUIRE(L >= 1 && L <= 512, "1 <= L <= 512");
@@ -2788,6 +2848,7 @@ int p5_generate_draft(P5Engine* e, const int64_t* input_ids, const int64_t* whol
                       const uint32_t* excluded_nodes, int excluded_words, int max_children, int* out_seq, float* out_score, int* out_len, int* hist,
                       void* ws, int64_t ws_bytes, void* stream) {
   P5_REQUIRE(hist, "p5_generate_draft: history buffer");
+  P5_REQUIRE(K >= 1 && K <= P5_MAX_K, "p5_generate_draft: 1 <= num_beams <= 64");
   e->gen_hist_next = hist;
   const int rc = p5_generate(e, input_ids, whole_word_ids, attention_mask, B, L, K, max_len, child_off, child_tok, child_node, roots, excluded_nodes,
                              excluded_words, max_children, out_seq, out_score, out_len, ws, ws_bytes, stream);

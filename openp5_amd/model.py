@@ -151,6 +151,11 @@ class P5T5Native(nn.Module):
     verify_share_encoder = True   # verified mode: the draft starts from the verification pass's fp32 encoder output (one encoder pass per batch)
     gen_lanes = 3                 # batches in flight in `map_lanes` (the runner's evaluation loops, bench.py): lanes overlap each other's latency-bound chains
     prefix_fast_forward = True    # the steps every item shares ("<dataset> item _") as one teacher-forced pass (p5_generate_set_forced_prefix)
+    NARROW_MAX_K = 64             # widest search of the narrow beam step (csrc/p5_decode.h); up to WIDE_MAX_K beams run the wide one (p5_decode_wide.h)
+    WIDE_MAX_K = 4096
+    wide_max_rows = 4096          # a wide search (K > 64) runs over at most this many decode rows (users x beams) per call: larger batches go in user
+                                  # chunks (the step KV cache alone is n_dec_layers x max_len x rows x 2 x inner x sizeof(T): ~3 GiB for fp32
+                                  # T5-small at max_len 30)
 
     def __init__(self, config, dtype: str = "bf16", device=None, backend=None, seed: int = 2023):
         super().__init__()
@@ -805,6 +810,8 @@ class P5T5Native(nn.Module):
         mode = unused.get("generation_mode", self.generation_mode)
         if mode not in ("verified", "draft"):
             raise ValueError(f"generation_mode={mode!r} (verified | draft)")
+        if not 1 <= K <= self.WIDE_MAX_K:
+            raise ValueError(f"generate(num_beams={K}): 1 <= num_beams <= {self.WIDE_MAX_K}")
         args = (input_ids, whole_word_ids, attention_mask, B, L, K, max_length, off, tok, nxt, roots_t, excl_t, excl_words, maxc)
         if self.compute_dtype == 1 and mode == "verified" and K <= self.VERIFY_MAX_K:
             seq, score, ln = self._generate_verified(*args)
@@ -816,12 +823,12 @@ class P5T5Native(nn.Module):
                 warnings.warn(f"generate(num_beams={K}): verified generation covers num_beams <= {self.VERIFY_MAX_K}; running the plain fp32 beam search "
                               f"instead (same ranked lists, slower).  generation_mode='draft' selects the plain bf16 search.", RuntimeWarning, stacklevel=2)
                 self._warned_wide_verified = True
-            seq, score, ln = self._search_fp32(*args)
+            seq, score, ln = self._in_user_chunks(self._search_fp32, args)
             with self._stats_lock:
                 self.verify_stats["wide_fp32_users"] += B
             path = "fp32_search"
         else:
-            seq, score, ln = self._search(lane.engine, "gen", *args)
+            seq, score, ln = self._in_user_chunks(lambda *a: self._search(lane.engine, "gen", *a), args)
             path = "draft_bf16" if self.compute_dtype == 1 else "fp32_search"
         self.last_generate_path = path
         out_len = 1 + int(ln[:, :nret].max().item())
@@ -830,6 +837,24 @@ class P5T5Native(nn.Module):
         if return_dict_in_generate:
             return {"sequences": sequences, "sequences_scores": scores if output_scores else None}
         return sequences
+
+    def _in_user_chunks(self, fn, args):
+        """fn(*args) for a search wider than the narrow step, over consecutive chunks of users of at most `wide_max_rows` decode rows each,
+        results concatenated.  The beam search of a user depends on that user alone and the decode step has one writer per output element,
+        so the results are those of one call, bit for bit."""
+        B, K = args[3], args[5]
+        per = max(1, int(self.wide_max_rows) // K)
+        if K <= self.NARROW_MAX_K or per >= B:
+            return fn(*args)
+        cut = lambda t, a, b: None if t is None else t[a:b].contiguous()     # noqa: E731
+        outs = []
+        for a in range(0, B, per):
+            b = min(B, a + per)
+            sub = list(args)
+            sub[0], sub[1], sub[2], sub[3] = cut(args[0], a, b), cut(args[1], a, b), cut(args[2], a, b), b - a
+            sub[10], sub[11] = cut(args[10], a, b), cut(args[11], a, b)        # per-user roots / excluded-node bitmap
+            outs.append(fn(*sub))
+        return tuple(torch.cat([o[i] for o in outs], 0) for i in range(3))
 
     def _search(self, engine, ws_attr, input_ids, whole_word_ids, attention_mask, B, L, K, max_length, off, tok, nxt, roots_t, excl_t, excl_words,
                 maxc, hist=None):

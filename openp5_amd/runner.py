@@ -154,7 +154,7 @@ class Prefetcher:
             yield item
 
 
-MAX_DEVICE_BEAMS = 64      # include/p5hip.h: p5_generate keeps <= 64 beams per batch item
+MAX_DEVICE_BEAMS = 4096    # include/p5hip.h: p5_generate keeps <= 4096 beams per batch item (the wide search beyond 64)
 
 
 def _world():
