@@ -9,6 +9,11 @@
 //     per-head bias over relative positions into LDS;
 //   * masked keys get -inf (the reference adds finfo.min; identical whenever a row has one unmasked key).
 //
+// Dead rows (every key of the row masked, e.g. a sample whose attention_mask is all zero): P = 0, so the forward stores O = 0 and
+// lse = -inf, and the backward gives the row zero dQ and no share of dK, dV or the bias gradient (attn_bwd_row_lse).  HF's finfo.min
+// makes such a row attend uniformly (O = mean of V) instead; the two agree on every loss and gradient whenever that sample carries no
+// loss.  The runner never builds such a sample, but any caller of the model can.
+//
 // Layout: Q/K/V are column slices of the fused projection output ([rows, 3*inner] etc.), addressed with a row
 // stride; head h occupies columns h*64..h*64+63.  No head transpose is ever written to HBM.
 //
@@ -1006,6 +1011,11 @@ __global__ __launch_bounds__(256) void p5_attn_bwd_dkv_kernel(P5AttnArgs a) {
 //   at 1.27 ms where the blocked kernel takes 0.74: profiles/r05_call14_attention_head_resident.txt).  The per-wave sums meet in LDS
 //   after the last block (K and V are dead by then) and are added in wave order: ONE relative-bias slot per (batch, head).
 // ------------------------------------------------------------------------------------------------------------
+// The log-sum-exp row a backward kernel folds into its exponent.  A DEAD row (every key masked: the forward stored O = 0 and lse = -inf)
+// would turn the -inf of its masked keys into (-inf) - (-inf) = NaN; as 0 it leaves them -inf, so every P of the row is 0 and so is
+// the row's share of dQ, dK, dV and the bias gradient.  Once per row where the row is loaded or staged, never per score.
+__device__ static __forceinline__ float attn_bwd_row_lse(float lse) { return lse == P5_NEG_INF ? 0.f : lse; }
+
 template <int NKT>
 __global__ __launch_bounds__(512) void p5_attn_bwd_dq_head_kernel(P5AttnArgs a) {
   using T = bf16;
@@ -1104,7 +1114,7 @@ __global__ __launch_bounds__(512) void p5_attn_bwd_dq_head_kernel(P5AttnArgs a) 
   int nblk = 0;
   for (int q0 = wave * 16; q0 < a.Lq; q0 += 128, ++nblk) {
     const u32x4 qf0 = qn[0], qf1 = qn[1], dof0 = don[0], dof1 = don[1];
-    const float lse_q = lse_n * P5_LOG2E;
+    const float lse_q = attn_bwd_row_lse(lse_n) * P5_LOG2E;
     const int qi = q0 + li;
     const bool qok = qi < a.Lq;
     const int qic = qok ? qi : a.Lq - 1;
@@ -1304,8 +1314,10 @@ __global__ __launch_bounds__(512) void p5_attn_bwd_dkv_head_kernel(P5AttnArgs a)
       const int j = i - PADB;
       sbias[i] = (a.rel_table && j >= 0 && j < nrel) ? P5_LOG2E * a.rel_table[a.bucket_lut[j - (a.Lq - 1) + a.lut_half] * a.H + h] : 0.f;
     }
+    // (dead rows: this pass was finite without attn_bwd_row_lse too -- every key of a dead row fails `ok` below, whose select replaces
+    //  the exponent -- but the row is staged as the other passes load it)
     for (int i = tid; i < LQ; i += NT) {
-      slse[i] = i < a.Lq ? P5_LOG2E * a.lse[((size_t)b * a.H + h) * a.Lq + i] : 0.f;
+      slse[i] = i < a.Lq ? P5_LOG2E * attn_bwd_row_lse(a.lse[((size_t)b * a.H + h) * a.Lq + i]) : 0.f;
       sD[i] = i < a.Lq ? a.Dvec[((size_t)b * a.H + h) * a.Lq + i] : 0.f;
     }
 #pragma unroll
@@ -1678,7 +1690,7 @@ __global__ __launch_bounds__(512) void p5_attn_bwd_fused_kernel(P5AttnArgs a) {
   const int qic = qok ? qi : a.Lq - 1;
 #pragma unroll
   for (int c = 0; c < 2; ++c) of[c] = qok ? ld16(O + (size_t)qi * a.ldo + c * 32 + g * 8) : zero16();
-  const float lse_q = qok ? P5_LOG2E * a.lse[((size_t)b * a.H + h) * a.Lq + qi] : 0.f;
+  const float lse_q = qok ? P5_LOG2E * attn_bwd_row_lse(a.lse[((size_t)b * a.H + h) * a.Lq + qi]) : 0.f;
   // (round 6, as the long-sequence passes: log2(e) folded into the bias table and the row's log-sum-exp, the key mask added to the
   //  exponent, a masked score a select on the exponent -- hipcc had turned `ok ? p ... : 0` into a compare + exec-mask branch per score)
   stage_bias_mask(a, b, h, sbias, skneg, 128, tid, P5_LOG2E, 256);

@@ -310,9 +310,10 @@ def gemm_norm_bwd_case(be, M, N, K, dot_nt, drop_p=0.0, seed=0, wgs=256, with_n=
     return e_r, e_w
 
 
-def attn_rowdot_case(be, B, H, L, mode="enc", drop_p=0.1, seed=3):
+def attn_rowdot_case(be, B, H, L, mode="enc", drop_p=0.1, seed=3, mask="suffix"):
     """P5AttnArgs::dot_out of the fused attention backward (bf16, self-attention, 16 < L <= 128): <dQ, Q> + <dK, K> + <dV, V> per token and
-    head from the gradients as stored; the gradients themselves are bit-identical to the call without it."""
+    head from the gradients as stored; the gradients themselves are bit-identical to the call without it.  mask (enc): attn_key_mask's
+    patterns; 'dead' (sample 0 without a valid key): its gradient rows and row sums are exactly 0."""
     g = torch.Generator().manual_seed(seed)
     tt = torch.bfloat16
     inner = H * 64
@@ -322,10 +323,7 @@ def attn_rowdot_case(be, B, H, L, mode="enc", drop_p=0.1, seed=3):
     table_d = dev(be, torch.randn(32, H, generator=g) * 0.5)
     lut_half = 512
     lut_d = dev(be, relative_position_bucket_lut(lut_half, mode == "enc", 32, 128))
-    kmask = torch.ones(B, L, dtype=torch.long)
-    if mode == "enc":
-        for b in range(B):
-            kmask[b, int(torch.randint(max(1, L // 2), L + 1, (1,), generator=g)):] = 0
+    kmask = attn_key_mask(B, L, mask, g) if mode == "enc" else None
     km_d = dev(be, kmask) if mode == "enc" else None
     causal = 1 if mode == "dec" else 0
     dOd = dev(be, torch.randn(B * L, inner, generator=g).to(tt))
@@ -351,6 +349,8 @@ def attn_rowdot_case(be, B, H, L, mode="enc", drop_p=0.1, seed=3):
     prod = (ga.float() * qkv.float()).view(B * L, 3, H, 64).sum(3).sum(1)
     err = ((dot - prod).abs() / prod.abs().clamp(min=1.0)).max().item()
     assert err <= 1e-4 and bool(torch.isfinite(dot).all()), f"row sums of <d qkv, qkv> off by {err}"
+    if mask == "dead":
+        assert bool((ga[:L] == 0).all()) and bool((dot[:L] == 0).all()), "dead sample: gradient rows / row sums are not exactly 0"
     return err
 
 
@@ -476,22 +476,78 @@ def _rmsnorm_bwd_check(be, dtype, rows, d, tt, xr, wr, dres, xd, wd, rd, dyd, dr
     assert e_nx <= (1e-6 if dtype == 0 else 5e-2), msg
 
 
-def attn_ref(q, k, v, bias, mask_add, causal):
+# attn_ref_case: error bound relative to the reference's largest entry, independent of L ...
+ATTN_TAU = {0: 1e-5, 1: 2.0 ** -6}
+# ... or to this fraction of the same sums over |terms| where that is larger (O, dQ, dK, dV; relative-bias gradient dT): a result that
+# cancels to (near) zero -- dQ, dK and dT of rows with one valid key, or at Lk = 1, are sums of P (dP - D) with P = 1 and dP = D -- keeps
+# the rounding of its terms (fp32: ~2^-23 of them).  In bf16 dT needs the floor at long L too: at L = 512 a bucket sums ~10^5 dS values
+# (bf16-rounded, as the MFMA sees them) that cancel to 4e-4 .. 1e-3 of their absolute sum.
+ATTN_FLOOR = {0: (2e-2, 1e-2), 1: (1e-3, 1e-3)}
+
+
+def attn_key_mask(B, Lk, pattern, g):
+    """[B, Lk] key-padding mask (nonzero = attend).  full: no padding; suffix: a valid prefix of at least Lk // 2 keys; one: a single
+    valid key inside the last 16-key chunk (the long-sequence kernels decide mask handling once per 16 / 64 keys); holes: Bernoulli(0.5)
+    per key, at least one valid; dead: sample 0 has no valid key at all, the others are `suffix`."""
+    km = torch.ones(B, Lk, dtype=torch.long)
+    for b in range(B):
+        if pattern == "full":
+            continue
+        if pattern == "suffix" or (pattern == "dead" and b > 0):
+            km[b, int(torch.randint(max(1, Lk // 2), Lk + 1, (1,), generator=g)):] = 0
+        elif pattern == "dead":
+            km[b] = 0
+        elif pattern == "one":
+            c0 = (Lk - 1) // 16 * 16
+            km[b] = 0
+            km[b, c0 + int(torch.randint(0, Lk - c0, (1,), generator=g))] = 1
+        elif pattern == "holes":
+            km[b] = (torch.rand(Lk, generator=g) < 0.5).long()
+            km[b, int(torch.randint(0, Lk, (1,), generator=g))] = 1
+        else:
+            raise ValueError(pattern)
+    return km
+
+
+def attn_ref64(q, k, v, dO, bias, valid, keep, drop_p, o_fwd=None):
+    """float64 attention and its backward, written out.  q, dO [B,H,Lq,64], k, v [B,H,Lk,64], bias [H,Lq,Lk] or None, valid [B,1|H,Lq,Lk]
+    bool (key mask and causal), keep [B,H,Lq,Lk] bool or None.  A DEAD row (no valid key) has P = 0: O = 0, lse = -inf, and it adds
+    nothing to any gradient -- the engine's contract (HF's finfo.min mask would attend uniformly instead).  o_fwd: the forward output
+    the backward is given (D = rowsum(dO o_fwd), as the kernels read it; default: the exact O).  Returns O, lse, dQ, dK, dV, dS (for
+    the bias gradient) and `mag`: the same products over absolute values, the scale of the terms a result cancels."""
     s = q @ k.transpose(2, 3)
     if bias is not None:
-        s = s + bias
-    if mask_add is not None:
-        s = s + mask_add
-    if causal:
-        Lq, Lk = s.shape[-2:]
-        cm = torch.ones(Lq, Lk, dtype=torch.bool).tril()
-        s = s.masked_fill(~cm, float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    return p @ v
+        s = s + bias[None]
+    s = s.masked_fill(~valid, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    dead = torch.isinf(m)
+    e = torch.where(valid, torch.exp(s - torch.where(dead, torch.zeros_like(m), m)), torch.zeros_like(s))
+    l = e.sum(-1, keepdim=True)
+    p = e / torch.where(dead, torch.ones_like(l), l)
+    lse = torch.where(dead, torch.full_like(m, float("-inf")), m + torch.log(torch.where(dead, torch.ones_like(l), l))).squeeze(-1)
+    ks = keep.double() / (1.0 - drop_p) if keep is not None else torch.ones_like(p)
+    pd = p * ks
+    o = pd @ v
+    dp = (dO @ v.transpose(2, 3)) * ks
+    D = (dO * (o if o_fwd is None else o_fwd)).sum(-1, keepdim=True)
+    ds = p * (dp - D)
+    out = dict(O=o, lse=lse, dQ=ds @ k, dK=ds.transpose(2, 3) @ q, dV=pd.transpose(2, 3) @ dO)
+    dsa = p * ((dO.abs() @ v.abs().transpose(2, 3)) * ks + (dO.abs() * (pd @ v.abs())).sum(-1, keepdim=True))
+    mag = dict(O=pd @ v.abs(), dQ=dsa @ k.abs(), dK=dsa.transpose(2, 3) @ q.abs(), dV=pd.transpose(2, 3) @ dO.abs())
+    return out, ds, dsa, mag, dead.squeeze(-1)
 
 
-def attn_case(be, dtype, B, H, Lq, Lk, mode, seed=0):
-    """mode: 'enc' (bidirectional bias + key mask, self), 'dec' (causal + unidirectional bias, self), 'cross' (mask only)."""
+def attn_ref_case(be, dtype, B, H, Lq, Lk, mode, mask="suffix", drop_p=0.0, op_bits=False, seed=0, tau=None, rowdot=False):
+    """Every attention kernel against a float64 reference on the SAME (device-rounded) inputs.  mode: 'enc' (bidirectional bias + key
+    mask, self), 'dec' (causal + unidirectional bias, self, no key mask), 'cross' (key mask only).  mask: attn_key_mask's patterns.
+    Scores are q k^T + rel_bias (no 1/sqrt(d) scaling, as in T5) with -inf at masked keys.  Dropout (drop_p > 0) is the engine's counter
+    hash replayed by the oracle (O.dropout_keep_mask), P keep / (1 - p) before PV, lse before dropout; op_bits: the long-sequence
+    forward stores its keep decisions for the backward.  Per output (O, lse, dQ, dK, dV, d_rel_table): all finite, max |err| <=
+    tau max |ref| and relative L2 error <= tau / 4 (tau = ATTN_TAU[dtype]; where a result cancels, ATTN_FLOOR).  Dead rows (mask
+    'dead'): lse exactly -inf, O and the dead sample's dQ, dK, dV rows exactly 0, and no share in d_rel_table (the reference gives
+    them none).  rowdot (bf16 self-attention, 16 < L <= 128): the fused backward's dot_out as well.  Returns the worst error per
+    output as a fraction of its bound."""
+    tau = ATTN_TAU[dtype] if tau is None else tau
     g = torch.Generator().manual_seed(seed)
     tt = TT[dtype]
     inner = H * 64
@@ -506,87 +562,135 @@ def attn_case(be, dtype, B, H, Lq, Lk, mode, seed=0):
         kvb = (0.5 * torch.randn(B * Lk, 2 * inner, generator=g)).to(tt)
         Qs, Ks, Vs = qb, kvb[:, :inner], kvb[:, inner:]
         ldq, ldk, ldv = inner, 2 * inner, 2 * inner
-    table = 0.5 * torch.randn(32, H, generator=g)
-    kmask = torch.ones(B, Lk, dtype=torch.long)
-    if mode != "dec":
-        for b in range(B):
-            n = int(torch.randint(max(1, Lk // 2), Lk + 1, (1,), generator=g))
-            kmask[b, n:] = 0
+    table = (0.5 * torch.randn(32, H, generator=g)) if self_attn else None
+    kmask = attn_key_mask(B, Lk, mask, g) if mode != "dec" else None
     dO = torch.randn(B * Lq, inner, generator=g).to(tt)
+    state = (1234 + seed, 7)
+    site = 11
 
     def heads(x, Ln):
-        return x.float().reshape(B, Ln, H, 64).transpose(1, 2)
+        return x.double().reshape(B, Ln, H, 64).transpose(1, 2)
 
-    qr = heads(Qs, Lq).clone().requires_grad_(True)
-    kr = heads(Ks, Lk).clone().requires_grad_(True)
-    vr = heads(Vs, Lk).clone().requires_grad_(True)
-    tr = table.clone().requires_grad_(True)
+    def unheads(x, Ln):
+        return x.transpose(1, 2).reshape(B * Ln, inner)
+
     lut_half = 512
-    bias = None
-    lut = None
-    if mode in ("enc", "dec"):
-        lut = relative_position_bucket_lut(lut_half, mode == "enc", 32, 128)
-        rel = torch.arange(Lk)[None, :] - torch.arange(Lq)[:, None]
-        bias = tr[lut[rel + lut_half].long()].permute(2, 0, 1).unsqueeze(0)
-    mask_add = None
-    if mode != "dec":
-        mask_add = torch.where(kmask[:, None, None, :] != 0, 0.0, float("-inf"))
-    out_r = attn_ref(qr, kr, vr, bias, mask_add, mode == "dec")
-    out_r.backward(heads(dO, Lq))
-    O_r = out_r.detach().transpose(1, 2).reshape(B * Lq, inner)
+    lut = relative_position_bucket_lut(lut_half, mode == "enc", 32, 128) if self_attn else None
+    rel = torch.arange(Lk)[None, :] - torch.arange(Lq)[:, None]
+    bias = table.double()[lut[rel + lut_half].long()].permute(2, 0, 1) if self_attn else None
+    valid = torch.ones(B, 1, Lq, Lk, dtype=torch.bool)
+    if kmask is not None:
+        valid = valid & (kmask[:, None, None, :] != 0)
+    if mode == "dec":
+        valid = valid & torch.ones(Lq, Lk, dtype=torch.bool).tril()
+    keep = None
+    if drop_p > 0:
+        sd = (state[0] + state[1] * 0x632BE5AB) & 0xFFFFFFFF                  # p5_rng.h:p5_seed
+        keep = O.dropout_keep_mask(sd, site, B * H * Lq * Lk, drop_p).view(B, H, Lq, Lk)
 
     Od = dev(be, torch.zeros(B * Lq, inner, dtype=tt))
-    lse = dev(be, torch.zeros(B * H * Lq))
+    lse = dev(be, torch.full((B * H * Lq,), float("nan")))
     if self_attn:
         qkv_d = dev(be, qkv)
         Qd, Kd, Vd = qkv_d, qkv_d[:, inner:], qkv_d[:, 2 * inner:]
     else:
         q_d, kv_d = dev(be, qb), dev(be, kvb)
         Qd, Kd, Vd = q_d, kv_d, kv_d[:, inner:]
-    table_d = dev(be, table) if mode != "cross" else None
-    lut_d = dev(be, lut) if lut is not None else None
-    km_d = dev(be, kmask) if mode != "dec" else None
+    table_d = dev(be, table) if self_attn else None
+    lut_d = dev(be, lut) if self_attn else None
+    km_d = dev(be, kmask) if kmask is not None else None
     causal = 1 if mode == "dec" else 0
-    be.check(be.lib.p5_op_attn_fwd(dtype, P(Qd), P(Kd), P(Vd), P(Od), P(lse), P(table_d), P(lut_d), lut_half, P(km_d), B, H, Lq, Lk, ldq,
-                                   ldk, ldv, inner, causal, None, 0, 0.0, be.stream_ptr()), "attn_fwd")
+    rng = dev(be, torch.tensor(state, dtype=torch.int32)) if drop_p > 0 else None
     if self_attn:
-        dqkv = dev(be, torch.zeros(B * Lq, 3 * inner, dtype=tt))
+        dqkv = dev(be, torch.full((B * Lq, 3 * inner), float("nan"), dtype=tt))
         dQd, dKd, dVd = dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:]
         lddq = lddk = lddv = 3 * inner
     else:
-        dq_d = dev(be, torch.zeros(B * Lq, inner, dtype=tt))
-        dkv_d = dev(be, torch.zeros(B * Lk, 2 * inner, dtype=tt))
+        dq_d = dev(be, torch.full((B * Lq, inner), float("nan"), dtype=tt))
+        dkv_d = dev(be, torch.full((B * Lk, 2 * inner), float("nan"), dtype=tt))
         dQd, dKd, dVd = dq_d, dkv_d, dkv_d[:, inner:]
         lddq, lddk, lddv = inner, 2 * inner, 2 * inner
-    dtab = dev(be, torch.zeros(32, H)) if mode != "cross" else None
-    dscr = dev(be, torch.full((B * ((Lq + 63) // 64), 32 * H), float("nan"))) if mode != "cross" else None     # (the op clears its slots itself)
+    dtab = dev(be, torch.zeros(32, H)) if self_attn else None
+    dscr = dev(be, torch.full((B * ((Lq + 63) // 64), 32 * H), float("nan"))) if self_attn else None
     Dv = dev(be, torch.zeros(B * H * Lq))
     dOd = dev(be, dO)
-    be.check(be.lib.p5_op_attn_bwd(dtype, P(Qd), P(Kd), P(Vd), P(Od), P(dOd), P(lse), P(Dv), P(dQd), P(dKd), P(dVd), P(table_d),
-                                   P(dtab), P(dscr), 32, P(lut_d), lut_half, P(km_d), B, H, Lq, Lk, ldq, ldk, ldv, inner, lddq, lddk, lddv, causal, None,
-                                   0, 0.0, be.stream_ptr()), "attn_bwd")
-    sync(be)
-    tol = 2e-5 if dtype == 0 else 4e-2
-    scale = max(1.0, Lk ** 0.5)
+    dot = dev(be, torch.full((B * Lq, H), float("nan"))) if rowdot else None
+    be.check(be.lib.p5_set_option(b"attn_op_keep_bits", 1 if op_bits else 0), "set_option")
+    try:
+        be.check(be.lib.p5_op_attn_fwd(dtype, P(Qd), P(Kd), P(Vd), P(Od), P(lse), P(table_d), P(lut_d), lut_half, P(km_d), B, H, Lq, Lk, ldq,
+                                       ldk, ldv, inner, causal, P(rng), site, drop_p, be.stream_ptr()), "attn_fwd")
+        args = (dtype, P(Qd), P(Kd), P(Vd), P(Od), P(dOd), P(lse), P(Dv), P(dQd), P(dKd), P(dVd), P(table_d), P(dtab), P(dscr), 32, P(lut_d),
+                lut_half, P(km_d), B, H, Lq, Lk, ldq, ldk, ldv, inner, lddq, lddk, lddv, causal, P(rng), site, drop_p)
+        if rowdot:
+            be.check(be.lib.p5_op_attn_bwd_dot(*args, P(dot), be.stream_ptr()), "attn_bwd_dot")
+        else:
+            be.check(be.lib.p5_op_attn_bwd(*args, be.stream_ptr()), "attn_bwd")
+        sync(be)
+    finally:
+        be.check(be.lib.p5_set_option(b"attn_op_keep_bits", 0), "set_option")
 
-    def unheads(x, Ln):
-        return x.transpose(1, 2).reshape(B * Ln, inner)
-
-    errs = {"O": (Od.cpu().float() - O_r).abs().max().item()}
+    # (the backward reference takes D from the forward output as stored: the kernels do, and O itself is checked against the exact one)
+    ref, ds, dsa, mag, dead = attn_ref64(heads(Qs, Lq), heads(Ks, Lk), heads(Vs, Lk), heads(dO, Lq), bias, valid, keep, drop_p,
+                                         o_fwd=heads(Od.cpu(), Lq))
+    if self_attn:      # d rel_table[bucket, h] = sum of dS over the (q, k) whose relative position falls in the bucket
+        idx = lut[rel + lut_half].long().reshape(-1)
+        ref["dT"] = torch.zeros(32, H, dtype=torch.float64).index_add_(0, idx, ds.sum(0).permute(1, 2, 0).reshape(-1, H))
+        mag["dT"] = torch.zeros(32, H, dtype=torch.float64).index_add_(0, idx, dsa.sum(0).permute(1, 2, 0).reshape(-1, H))
+    got = {"O": Od.cpu().double(), "lse": lse.cpu().double().view(B, H, Lq)}
     if self_attn:
-        g_all = dqkv.cpu().float()
-        gq, gk, gv = g_all[:, :inner], g_all[:, inner:2 * inner], g_all[:, 2 * inner:]
+        g_all = dqkv.cpu().double()
+        got["dQ"], got["dK"], got["dV"] = g_all[:, :inner], g_all[:, inner:2 * inner], g_all[:, 2 * inner:]
+        got["dT"] = dtab.cpu().double()
     else:
-        gq = dq_d.cpu().float()
-        gk, gv = dkv_d.cpu().float()[:, :inner], dkv_d.cpu().float()[:, inner:]
-    errs["dQ"] = (gq - unheads(qr.grad, Lq)).abs().max().item()
-    errs["dK"] = (gk - unheads(kr.grad, Lk)).abs().max().item()
-    errs["dV"] = (gv - unheads(vr.grad, Lk)).abs().max().item()
-    if mode != "cross":
-        errs["dT"] = (dtab.cpu() - tr.grad).abs().max().item() / max(1.0, float(tr.grad.abs().max()))
-    for k_, e_ in errs.items():
-        assert e_ <= tol * scale * (4 if k_ != "O" else 1), f"attention {mode} dtype={dtype} Lq={Lq} Lk={Lk}: {k_} err {e_} (all: {errs})"
-    return errs
+        got["dQ"] = dq_d.cpu().double()
+        got["dK"], got["dV"] = dkv_d.cpu().double()[:, :inner], dkv_d.cpu().double()[:, inner:]
+    want = {"O": unheads(ref["O"], Lq), "lse": ref["lse"], "dQ": unheads(ref["dQ"], Lq), "dK": unheads(ref["dK"], Lk),
+            "dV": unheads(ref["dV"], Lk)}
+    floor = {"O": unheads(mag["O"], Lq), "dQ": unheads(mag["dQ"], Lq), "dK": unheads(mag["dK"], Lk), "dV": unheads(mag["dV"], Lk)}
+    if self_attn:
+        want["dT"], floor["dT"] = ref["dT"], mag["dT"]
+    tag = f"attention {mode} dtype={dtype} B={B} H={H} Lq={Lq} Lk={Lk} mask={mask} drop={drop_p} bits={int(op_bits)}"
+    ratios = {}
+    for name, w in want.items():
+        x = got[name]
+        if name == "lse":          # live rows against the reference, dead rows exactly -inf
+            assert bool(torch.isneginf(x[dead]).all()), f"{tag}: lse of dead rows is not -inf: {x[dead][~torch.isneginf(x[dead])][:4]}"
+            x, w = x[~dead], w[~dead]
+            fl = torch.zeros(())
+        else:
+            fl = floor[name]
+        assert bool(torch.isfinite(x).all()), f"{tag}: {name} has {int((~torch.isfinite(x)).sum())} non-finite entries"
+        if x.numel() == 0:
+            continue
+        err = x - w
+        c = ATTN_FLOOR[dtype][1 if name == "dT" else 0]
+        smax = max(float(w.abs().max()), c * float(fl.abs().max()))
+        sl2 = max(float(w.norm()), c * float(fl.norm()))
+        r_max = float(err.abs().max()) / smax if smax > 0 else float(err.abs().max())
+        r_l2 = float(err.norm()) / sl2 if sl2 > 0 else float(err.norm())
+        ratios[name] = max(r_max, 4 * r_l2) / tau
+        assert r_max <= tau and r_l2 <= tau / 4, f"{tag}: {name} max err {r_max:.3e} of max |ref|, L2 err {r_l2:.3e} (tau {tau:.3e})"
+    if mask == "dead":
+        assert not bool(dead[1:].any()) and bool(dead[0].all())
+        for name, Ln in (("O", Lq), ("dQ", Lq), ("dK", Lk), ("dV", Lk)):
+            rows = got[name][:Ln]
+            assert bool((rows == 0).all()), f"{tag}: {name} rows of the dead sample are not exactly 0 (max {float(rows.abs().max())})"
+    if rowdot:
+        dg = dot.cpu().double()
+        gq = torch.cat([got["dQ"], got["dK"], got["dV"]], 1)
+        prod = (gq * qkv.double()).view(B * Lq, 3, H, 64).sum(3).sum(1)
+        assert bool(torch.isfinite(dg).all()), f"{tag}: dot_out not finite"
+        e = float(((dg - prod).abs() / prod.abs().clamp(min=1.0)).max())
+        assert e <= 1e-4, f"{tag}: row sums of <d qkv, qkv> off by {e}"
+        if mask == "dead":
+            assert bool((dg[:Lq] == 0).all()), f"{tag}: dot_out rows of the dead sample are not 0"
+    return ratios
+
+
+def attn_case(be, dtype, B, H, Lq, Lk, mode, seed=0):
+    """mode: 'enc' (bidirectional bias + key mask, self), 'dec' (causal + unidirectional bias, self), 'cross' (mask only); suffix key
+    padding, no dropout: attn_ref_case's float64 reference and bounds."""
+    return attn_ref_case(be, dtype, B, H, Lq, Lk, mode, mask="suffix", seed=seed)
 
 
 def attn_fwd_wg_case(be, B, H, Lq, Lk, mode="enc", drop_p=0.1, seed=6, option=b"attn_fwd_wg", exact=True, op_bits=False):
@@ -828,6 +932,49 @@ def model_train_case(be, ocfg, B, L, T, dtype="fp32", dropout=0.0, seed=3, nll_t
             worst = (rel, name)
     assert worst[0] <= grad_tol, f"gradient mismatch {worst}"
     return err, worst
+
+
+def model_dead_sample_case(be, ocfg, B, L, T, dtype="fp32", seed=3, loss_tol=2e-5, grad_tol=2e-4, drop_tol=1e-5):
+    """A batch whose sample 0 has an all-zero attention_mask and no label weight: every encoder row and every decoder cross-attention
+    row of that sample is dead (no valid key).  The engine gives those rows O = 0 and zero gradient; the oracle follows HF (finfo.min
+    mask: the row attends uniformly) -- the two agree on everything the loss sees, because that sample carries no loss.  The loss and
+    every parameter gradient are finite and match the oracle (relative to each tensor's largest entry, as model_train_case), and they
+    equal the gradients of the same batch without sample 0 (scaled by (B - 1) / B: runner_loss averages over the samples) to drop_tol."""
+    params = O.init_params(ocfg, 7)
+    ids, ww, mask, labels, out_attn = synth_batch(ocfg, B, L, T, seed)
+    mask[0] = 0
+    out_attn[0] = 0
+
+    def engine(sl):
+        m = build_model(be, ocfg, params, dtype)
+        m.eval()
+        nll = m(input_ids=ids[sl], whole_word_ids=ww[sl], attention_mask=mask[sl], labels=labels[sl], return_dict=True)["loss"]
+        loss = O.runner_loss(nll, out_attn[sl].to(nll.device))
+        loss.backward()
+        sync(be)
+        return float(loss), {n: p.grad.detach().cpu().double() for n, p in m.named_parameters()}
+
+    loss, grads = engine(slice(0, B))
+    loss_r, grads_r = engine(slice(1, B))
+    Pq = {k: v.clone().requires_grad_(True) for k, v in params.items()}
+    loss_o = O.runner_loss(O.p5_forward_nll(Pq, ocfg, ids, ww, mask, labels), out_attn)
+    loss_o.backward()
+    assert math.isfinite(loss) and abs(loss - float(loss_o)) <= loss_tol * max(1.0, abs(float(loss_o))), f"loss {loss} vs oracle {float(loss_o)}"
+    assert abs(loss * B - loss_r * (B - 1)) <= drop_tol * max(1.0, abs(loss_r)) * B, f"loss {loss} vs {loss_r} without the dead sample"
+    bad = [n for n, g_ in grads.items() if not bool(torch.isfinite(g_).all())]
+    assert not bad, f"{len(bad)} of {len(grads)} parameter gradients are not finite: {bad[:6]}"
+    gmax = max(float(v.grad.abs().max()) for v in Pq.values())
+    worst, worst_r = (0.0, ""), (0.0, "")
+    for name, g_ in grads.items():
+        go = Pq[name].grad.double()
+        rel = float((g_ - go).abs().max()) / (float(go.abs().max()) + 1e-2 * gmax + 1e-12)
+        gr = grads_r[name] * ((B - 1) / B)
+        rel_r = float((g_ - gr).abs().max()) / (float(gr.abs().max()) + 1e-2 * gmax + 1e-12)
+        worst = max(worst, (rel, name))
+        worst_r = max(worst_r, (rel_r, name))
+    assert worst[0] <= grad_tol, f"gradient mismatch against the oracle {worst}"
+    assert worst_r[0] <= drop_tol, f"gradients differ from the batch without the dead sample {worst_r}"
+    return worst, worst_r
 
 
 def golden_case(be, name, dtype="fp32", nll_tol=3e-5, grad_tol=3e-4, score_tol=2e-5):
