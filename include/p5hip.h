@@ -49,7 +49,8 @@ int p5_abi_version(void);
 /* In-run kernel profiler (measurement aid, bench.py): between p5_profile_begin() and p5_profile_end() every kernel launch of the library is
  * bracketed by two HIP events on its stream; p5_profile_end synchronises and writes a JSON array of {"kernel" (name + launch grid), "launches",
  * "total_us", "flops" (algorithmic FLOPs of the GEMM / attention launches, 0 elsewhere)} into `report` (NUL-terminated, `cap` bytes).
- * Durations include the dispatch gap of each launch (~1-2 us), i.e. they are upper bounds of the rocprofv3 kernel durations. */
+ * Durations include the dispatch gap of each launch (~1-2 us), i.e. they are upper bounds of the rocprofv3 kernel durations.  The test-only
+ * host emulation reports the same kernel keys with zero times and FLOPs. */
 int p5_profile_begin(void);
 int p5_profile_end(char* report, int cap);
 int p5_is_emulator(void);   /* 1 only for the test-only host emulation build under tests/emu */
@@ -261,6 +262,9 @@ int p5_encode(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_i
               int B, int L, void* enc_out /* T [B*L, d] */, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---- per-kernel entry points (parity tests) ---- */
+/* C[M, N] = epi(alpha A B^T), C (ldc) written in [0:M, 0:N] only.  A K-contiguous operand may have K % 8 (bf16) / K % 4 (fp32) != 0 when
+ * its leading dimension reaches the next multiple of 16 bytes: the elements in [K, round_up(K, 16 bytes)) of every row are padding, read but
+ * never multiplied in, and may hold anything (NaN included); so may everything else past K, M or N in the operands and aux. */
 int p5_op_gemm(int dtype, const void* A, const void* Bm, void* C, const void* aux, int M, int N, int K, int lda, int ldb,
                int ldc, int ldaux, int a_ks, int b_ks, int epi, int c_f32, int splitk, float alpha,
                const uint32_t* rng_state, uint32_t site, float drop_p, void* stream);

@@ -83,8 +83,28 @@ template <> struct TT<bf16> { static constexpr int EPF = 8; static constexpr int
 
 // ---- launch + block primitives -------------------------------------------------------------------
 #ifdef P5_EMU
-#define P5_LAUNCH(kern, grid, block, shmem, stream, ...) \
-  emu::launch((grid), (block), (shmem), [=]() { kern(__VA_ARGS__); })
+// The host emulation keeps the launch record of the in-run profiler (kernel text, tag, grid; no times), so that tests of which kernel a
+// route reaches run on the host as well.
+#include <string>
+#include <vector>
+struct P5EmuProf {
+  int on = 0;
+  const char* pending_tag = "";
+  std::vector<std::string> recs;
+  void note(const char* name, dim3 g, dim3 b) {
+    char k[512];
+    snprintf(k, sizeof(k), "%s%s%s%s grid=(%u,%u,%u) block=%u", name, pending_tag[0] ? " [" : "", pending_tag, pending_tag[0] ? "]" : "", g.x, g.y, g.z, b.x);
+    recs.push_back(k);
+  }
+};
+inline P5EmuProf& p5_emu_prof() { static thread_local P5EmuProf p; return p; }
+#define P5_LAUNCH(kern, grid, block, shmem, stream, ...)                     \
+  do {                                                                       \
+    P5EmuProf& _pf = p5_emu_prof();                                          \
+    if (_pf.on) _pf.note(#kern, dim3(grid), dim3(block));                    \
+    _pf.pending_tag = "";                                                    \
+    emu::launch((grid), (block), (shmem), [=]() { kern(__VA_ARGS__); });     \
+  } while (0)
 #define P5_DYN_SMEM(name) char* name = emu::B().dyn_smem
 #define P5_LANE() ((int)emu::lane())
 #else

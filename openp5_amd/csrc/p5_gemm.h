@@ -129,6 +129,20 @@ __device__ static __forceinline__ int kc_off(int row, int kc) {
   return row * 64 + ((kc ^ h) << 4);
 }
 
+// the first n (0 < n < EPF) elements of a 16-byte piece, the rest zeroed: the K tail of a K-contiguous operand whose K % EPF != 0
+// (the launcher accepts it when lda / ldb reach round_up(K, EPF); the elements in [K, round_up(K, EPF)) are padding, never data)
+template <class T>
+__device__ static __forceinline__ u32x4 keep_first(u32x4 v, int n) {
+  constexpr int EPW = 4 / (int)sizeof(T);         // elements per 32-bit word, the first one in the low bits
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int e = n - w * EPW;
+    if (e <= 0) v[w] = 0u;
+    else if (e < EPW) v[w] &= 0xFFFFu;
+  }
+  return v;
+}
+
 // loads ONE chunk (KCH elements of K starting at k0) of an R-row operand tile into registers
 template <class T, int R, bool KS>
 __device__ static __forceinline__ void stage_load(u32x4* regs, const T* __restrict__ p, int ld, int r0, int k0, int nrows,
@@ -142,6 +156,7 @@ __device__ static __forceinline__ void stage_load(u32x4* regs, const T* __restri
       const int row = c >> 2, kc = c & 3;
       const int gr = r0 + row, gk = k0 + kc * EPF;
       regs[i] = (gr < nrows && gk < K) ? ld16(p + (size_t)gr * ld + gk) : zero16();
+      if (gk < K && gk + EPF > K) regs[i] = keep_first<T>(regs[i], K - gk);
     }
   } else {
     constexpr int CPR = R / EPF;  // chunks per k-row

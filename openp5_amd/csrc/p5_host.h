@@ -18,7 +18,7 @@ static inline int fail(const std::string& m) { g_p5_err = m; return -1; }
 #ifdef P5_EMU
 #define P5_KCHECK() 0
 #define P5_PROF_FLOPS(x) ((void)0)
-#define P5_PROF_TAG(x) ((void)0)
+#define P5_PROF_TAG(x) (p5_emu_prof().pending_tag = (x))
 #define P5_PROF_SHAPE(m, n, k) ((void)0)
 #else
 static inline int kcheck(const char* where) {

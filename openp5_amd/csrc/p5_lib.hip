@@ -2301,12 +2301,40 @@ int p5_profile_begin(void) {
 #ifndef P5_EMU
   P5Prof& p = p5_prof();
   p.recs.clear(); p.used = 0; p.pending_flops = 0.0; p.on = 1;
+#else
+  p5_emu_prof().recs.clear();
+  p5_emu_prof().on = 1;
 #endif
   return 0;
 }
 int p5_profile_end(char* report, int cap) {
   if (report && cap > 0) report[0] = 0;
-#ifndef P5_EMU
+#ifdef P5_EMU
+  {   // (host emulation: the launch record only -- which kernels ran, how often; no durations, no FLOPs)
+    P5EmuProf& p = p5_emu_prof();
+    p.on = 0;
+    std::vector<std::pair<std::string, int>> agg;
+    for (const std::string& k : p.recs) {
+      size_t i = 0;
+      for (; i < agg.size(); ++i) if (agg[i].first == k) break;
+      if (i == agg.size()) agg.push_back({k, 0});
+      agg[i].second++;
+    }
+    p.recs.clear();
+    if (agg.empty()) return 0;
+    std::string out = "[";
+    for (size_t i = 0; i < agg.size(); ++i) {
+      std::string key;
+      for (char c : agg[i].first) { if (c == '"' || c == '\\') key += '\\'; key += c; }
+      out += (i ? ", " : "") + std::string("{\"kernel\": \"") + key + "\", \"launches\": " + std::to_string(agg[i].second) + ", \"total_us\": 0, \"flops\": 0}";
+    }
+    out += "]";
+    if (report && cap > 0) {
+      if ((int)out.size() + 1 > cap) return fail("profile: report buffer too small");
+      memcpy(report, out.c_str(), out.size() + 1);
+    }
+  }
+#else
   P5Prof& p = p5_prof();
   p.on = 0;
   if (p.recs.empty()) return 0;

@@ -77,6 +77,283 @@ def gemm_case(be, dtype, M, N, K, a_ks, b_ks, epi=0, c_f32=0, splitk=1, seed=0):
     return err
 
 
+# gemm_ref_case: |got - ref| <= GEMM_R[C is bf16] |ref| + GEMM_S S per element, S = sum_k |a_ik b_jk| (times the epilogue's scale) plus |aux| or
+# |C0| where those are added.  GEMM_R: one bf16 rounding of the result (unit roundoff 2^-8); the bf16 epilogues also round the product P
+# once before the residual add or the dropout rescale, so those get GEMM_R |P| more.  GEMM_S: fp32 accumulation (and the split-f16
+# products' dropped lo x lo terms, ~2^-22 each) at any K.
+GEMM_R = {True: 2.0 ** -8, False: 0.0}
+GEMM_S = 2.0 ** -16
+GEMM_SENT = {torch.bfloat16: (torch.int16, 0x7FA5), torch.float32: (torch.int32, 0x7FA5A5A5)}     # NaN bit patterns outside the output
+GEMM_STATE, GEMM_SITE = (4321, 9), 5
+
+
+def _sentinel(shape, tt):
+    it, v = GEMM_SENT[tt]
+    return torch.full(shape, v, dtype=it).view(tt)
+
+
+def _same_bits(a, b):
+    it = GEMM_SENT[a.dtype][0]
+    return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+def _stored(g, rows, inner, ks, pad, tt, scale=1.0):
+    """a logical [rows, inner] operand in dtype tt and its storage with the leading dimension padded by `pad` elements past the least legal
+    one (a multiple of 16 bytes): K-contiguous [rows, ld], K-strided [inner, ld]; every padding element is NaN"""
+    epf = 16 // torch.tensor([], dtype=tt).element_size()
+    x = (torch.randn(rows, inner, generator=g) * scale).to(tt)
+    used = rows if ks else inner
+    ld = (used + epf - 1) // epf * epf + pad
+    st = torch.full((inner, ld) if ks else (rows, ld), float("nan"), dtype=tt)
+    if ks:
+        st[:, :rows] = x.t()
+    else:
+        st[:, :inner] = x
+    return x, st, ld
+
+
+def _gemm_ref_out(A, B, epi, alpha, aux, C0, keep, drop_p, scale=None):
+    """float64 reference of one problem: returns (ref, S, P) -- P the product term before aux is added (bf16 epilogues round it once)"""
+    a, b = A.double(), B.double()
+    sc = torch.full((a.shape[0], 1), float(alpha), dtype=torch.float64) if scale is None else scale[:, None] * float(alpha)
+    prod = (a @ b.t()) * sc
+    S = (a.abs() @ b.abs().t()) * sc.abs()
+    zero = torch.zeros_like(prod, dtype=torch.bool)
+    if epi == 1:
+        zero = prod < -GEMM_S * S                  # clearly negative: ReLU gives an exact 0
+        prod = prod.clamp(min=0)
+    if epi in (1, 2) and keep is not None:
+        prod = torch.where(keep, prod / (1.0 - drop_p), torch.zeros_like(prod))
+        S = torch.where(keep, S / (1.0 - drop_p), torch.zeros_like(S))
+    ref = prod
+    if epi == 2:
+        ref = prod + aux.double()
+        S = S + aux.double().abs()
+    elif epi == 3:
+        ref = torch.where(aux.double() > 0, prod, torch.zeros_like(prod))
+        zero = aux.double() <= 0
+    elif epi in (4, 6):
+        ref = prod + C0.double()
+        S = S + C0.double().abs()
+    if epi == 1 and keep is not None:
+        zero = zero | ~keep
+    return ref, S, prod, zero
+
+
+def _gemm_check(tag, got_full, ref, S, P, zero, M, N, c_bf16, epi, aux, keep, extra=None):
+    """one output: sentinel outside [0:M, 0:N] intact, finite, within the bound, exact zeros; returns err / bound at its worst"""
+    it, v = GEMM_SENT[got_full.dtype]
+    bits = got_full.view(it).clone()
+    bits[:M, :N] = v
+    assert bool((bits == v).all()), f"{tag}: {int((bits != v).sum())} elements outside C[0:M, 0:N] were written"
+    got = got_full[:M, :N].double()
+    assert bool(torch.isfinite(got).all()), f"{tag}: {int((~torch.isfinite(got)).sum())} non-finite outputs (padding read, or unwritten)"
+    r = GEMM_R[c_bf16]
+    bound = r * ref.abs() + GEMM_S * S
+    if c_bf16 and (epi == 2 or (epi == 1 and keep is not None)):
+        bound = bound + r * P.abs()
+    if extra is not None:
+        bound = bound + extra
+    err = (got - ref).abs()
+    ratio = err / bound.clamp(min=1e-300)
+    worst = float(ratio.max())
+    if worst > 1.0:
+        i = int(ratio.argmax())
+        rr, cc = i // N, i % N
+        raise AssertionError(f"{tag}: err {float(err.max()):.3e}; worst at ({rr}, {cc}): got {float(got[rr, cc]):.6e} ref {float(ref[rr, cc]):.6e} "
+                             f"bound {float(bound[rr, cc]):.3e} ({int((ratio > 1).sum())} elements out of bound)")
+    assert bool((got[zero] == 0).all()), f"{tag}: {int((got[zero] != 0).sum())} elements that must be exact zeros (ReLU of a negative, dropped, aux <= 0) are not"
+    if epi == 2 and keep is not None:
+        assert torch.equal(got[~keep], aux.double()[~keep]), f"{tag}: dropped elements are not the residual itself"
+    return worst
+
+
+def _set_opts(be, opts):
+    """apply p5_set_option values; returns the (name, default) pairs to restore"""
+    undo = []
+    for k, v in opts.items():
+        undo.append((k, GEMM_OPT_DEFAULTS[k]))
+        be.check(be.lib.p5_set_option(k.encode(), v), f"p5_set_option {k}")
+    return undo
+
+
+GEMM_OPT_DEFAULTS = dict(gemm_v2=0, gemm_tile=0, gemm_ksdma=1, gemm_ring=1, gemm_small_ring=1, gemm_small_ring_tiles=256, gemm_ring32=128,
+                         gemm_wide=1, gemm_ws=3, gemm_ws128=1, gemm_ws128_min_k=512, gemm_wide_min_tiles=160, gemm_ring128_min_k=1024,
+                         gemm_ring128_min_tiles=128, gemm_ring_n512=1, g4_nst=3, g4_wgs=256, dec_nb=0)
+
+
+def prof_kernels(report):
+    """kernel keys of a p5_profile_end report"""
+    import json
+    return [e["kernel"] for e in json.loads(report)] if report else []
+
+
+def route_matches(keys, site, tag):
+    """True when a profiler key names the launch site (its P5_LAUNCH text, whitespace-insensitive) with the row's tag"""
+    want = "".join(site.split())
+    for k in keys:
+        name = k.split(" [")[0].split(" grid=")[0]
+        if "".join(name.split()).strip("()") != want:
+            continue
+        has = " [" in k.split(" grid=")[0]
+        if (tag == "" and not has) or (tag and f" [{tag}]" in k):
+            return True
+    return False
+
+
+def gemm_ref_case(be, row, seed=0, profile=True):
+    """One row of tests/gemm_matrix.py against a float64 reference on the same rounded inputs (p5_op_gemm, p5_op_gemm_group,
+    p5_op_skinny_gemm), with guard bands: operand padding is NaN, C is [M + 2, ldc] filled with a NaN sentinel that must survive outside
+    [0:M, 0:N], aux is padded the same way.  Bound per element: GEMM_R |ref| + GEMM_S S (see above).  Exact: zeros of the ReLU and of the
+    aux > 0 mask, dropout's keep set (O.dropout_keep_mask, row * N + col) with dropped elements exactly 0 (epilogue 1) or exactly the residual
+    (epilogue 2).  With `profile`, the call is bracketed by p5_profile_begin / p5_profile_end and the report must name the row's launch
+    site and tag.  Options set by the row are restored.  Returns the worst err / bound."""
+    g = torch.Generator().manual_seed(seed)
+    keepalive, checks = [], []
+    op = row["op"]
+    rng = None
+    if row.get("drop", 0.0) > 0 and op != "skinny":
+        rng = dev(be, torch.tensor(GEMM_STATE, dtype=torch.int32))
+    sd = (GEMM_STATE[0] + GEMM_STATE[1] * 0x632BE5AB) & 0xFFFFFFFF
+
+    def problem(M, N, K, a_ks, b_ks, epi, c_f32, dtype, pad, alpha, drop_p, stats_nt=0):
+        tt = torch.bfloat16 if dtype == 1 else torch.float32
+        A, Ast, lda = _stored(g, M, K, a_ks, pad[0], tt)
+        B, Bst, ldb = _stored(g, N, K, b_ks, pad[1], tt)
+        ct = torch.float32 if (c_f32 or dtype != 1) else torch.bfloat16
+        ldc = (N + 7) // 8 * 8 + pad[2]
+        Cst = _sentinel((M + 2, ldc), ct)
+        C0 = None
+        if epi in (4, 6):
+            C0 = torch.randn(M, N, generator=g).to(ct)
+            Cst[:M, :N] = C0
+        aux = auxst = None
+        ldaux = 0
+        if epi in (2, 3):
+            ldaux = (N + 7) // 8 * 8 + pad[3]
+            aux = torch.randn(M, N, generator=g).to(tt)
+            auxst = torch.full((M + 2, ldaux), float("nan"), dtype=tt)
+            auxst[:M, :N] = aux
+        keep = None
+        if epi in (1, 2) and drop_p > 0:
+            keep = O.dropout_keep_mask(sd, GEMM_SITE, M * N, drop_p).view(M, N)
+        scale = rowss = ssq = None
+        if stats_nt:
+            part = (torch.rand(M, stats_nt, generator=g) * (2.0 * K / stats_nt)).float()
+            ssum = torch.zeros(M, dtype=torch.float64)
+            for t in range(stats_nt):
+                ssum = ssum + part[:, t].double()
+            scale = 1.0 / torch.sqrt(ssum / K + 1e-6)
+            rowss = dev(be, part)
+            ssq = dev(be, torch.full((M + 1, (N + 63) // 64), float("nan")))
+        ref, S, Pt, zero = _gemm_ref_out(A, B, epi, alpha, aux, C0, keep, drop_p, scale)
+        Ad, Bd, Cd = dev(be, Ast), dev(be, Bst), dev(be, Cst)
+        auxd = dev(be, auxst) if auxst is not None else None
+        keepalive.extend([Ad, Bd, Cd, auxd, rowss, ssq])
+        checks.append(dict(Cd=Cd, ref=ref, S=S, P=Pt, zero=zero, M=M, N=N, c_bf16=ct == torch.bfloat16, epi=epi, aux=aux, keep=keep, ssq=ssq, alpha=alpha,
+                           tag=f"{row['id']} ({M}x{N}x{K} epi {epi})"))
+        return dict(A=Ad, B=Bd, C=Cd, aux=auxd, lda=lda, ldb=ldb, ldc=ldc, ldaux=ldaux, rowss=rowss, ssq=ssq)
+
+    undo = _set_opts(be, row["opts"])
+    report = None
+    try:
+        if profile:
+            be.check(be.lib.p5_profile_begin(), "p5_profile_begin")
+        if op == "gemm":
+            d = problem(row["M"], row["N"], row["K"], row["a_ks"], row["b_ks"], row["epi"], row["c_f32"], row["dtype"], row["pad"], row["alpha"],
+                        row["drop"])
+            be.check(be.lib.p5_op_gemm(row["dtype"], P(d["A"]), P(d["B"]), P(d["C"]), P(d["aux"]), row["M"], row["N"], row["K"], d["lda"], d["ldb"],
+                                       d["ldc"], d["ldaux"], row["a_ks"], row["b_ks"], row["epi"], row["c_f32"], row["splitk"], row["alpha"],
+                                       P(rng), GEMM_SITE, row["drop"], be.stream_ptr()), f"gemm {row['id']}")
+        elif op == "group":
+            from openp5_amd._abi import P5GemmProblem
+            arr = (P5GemmProblem * len(row["probs"]))()
+            for i, (M, N, K, epi, c_f32, splitk, pad) in enumerate(row["probs"]):
+                alpha = 0.75 if epi in (0, 3, 4, 6) else 1.0
+                nt = row["stats_nt"] if (row["stats_nt"] and epi in (0, 1, 2, 3) and not c_f32) else 0
+                d = problem(M, N, K, row["ks"], row["ks"], epi, c_f32, 1, pad, alpha, row["drop"], stats_nt=nt)
+                _gemm_problem(arr, i, A=d["A"], B=d["B"], C=d["C"], M=M, N=N, K=K, lda=d["lda"], ldb=d["ldb"], ldc=d["ldc"], ldaux=d["ldaux"], epi=epi,
+                              c_f32=c_f32, splitk=splitk, alpha=alpha)
+                if d["aux"] is not None:
+                    arr[i].aux = d["aux"].data_ptr()
+                if nt:
+                    q = arr[i]
+                    q.rowss, q.rowss_eps, q.rowss_nt = d["rowss"].data_ptr(), 1e-6, nt
+                    q.ssq_out, q.ssq_nt = d["ssq"].data_ptr(), (N + 63) // 64
+            be.check(be.lib.p5_op_gemm_group(row["cfg"], row["ks"], len(row["probs"]), arr, P(rng), GEMM_SITE, row["drop"], be.stream_ptr()),
+                     f"gemm_group {row['id']}")
+        else:
+            _skinny_problem(be, g, row, keepalive, checks)
+        sync(be)
+        if profile:
+            buf = ctypes.create_string_buffer(1 << 16)
+            be.check(be.lib.p5_profile_end(buf, len(buf)), "p5_profile_end")
+            report = buf.value.decode()
+            profile = False
+    finally:
+        if profile:
+            be.lib.p5_profile_end(None, 0)
+        for k, v in undo:
+            be.lib.p5_set_option(k.encode(), v)
+    if report is not None and row.get("site"):
+        keys = prof_kernels(report)
+        assert route_matches(keys, row["site"], row["tag"]), f"{row['id']}: expected {row['site']} [{row['tag']}], the profiler saw {keys}"
+    worst = 0.0
+    for c in checks:
+        got = c["Cd"].cpu()
+        worst = max(worst, _gemm_check(c["tag"], got, c["ref"], c["S"], c["P"], c["zero"], c["M"], c["N"], c["c_bf16"], c["epi"], c["aux"], c["keep"],
+                                       c.get("extra")))
+        if c.get("ssq") is not None:        # the output rows' partial sums per 64 columns: of the values as stored (MASK_POS: C * aux / alpha)
+            M, N = c["M"], c["N"]
+            s = c["ssq"].cpu().double()
+            assert bool(torch.isnan(s[M:]).all()), f"{c['tag']}: ssq_out written past row M"
+            v = got[:M, :N].double()
+            w = v * (c["aux"].double() / c["alpha"]) if c["epi"] == 3 else v * v
+            wa = w.abs()
+            want = torch.stack([w[:, j:j + 64].sum(1) for j in range(0, N, 64)], 1)
+            mag = torch.stack([wa[:, j:j + 64].sum(1) for j in range(0, N, 64)], 1)
+            e = float(((s[:M] - want).abs() / (GEMM_S * mag).clamp(min=1e-30)).max())
+            assert e <= 1.0, f"{c['tag']}: ssq_out off by {e:.3f} of its bound"
+    return worst
+
+
+def _skinny_problem(be, g, row, keepalive, checks):
+    """p5_op_skinny_gemm (decode-step projections, p5_decode2.h): amode 0 A = T [M, lda]; amode 1 A = fp32 rows normalised by the kernel
+    (T5LayerNorm with weight ln, the reference rounding order of p5_rmsnorm_fwd_kernel).  epi 0 store T * alpha, 1 ReLU store T, 2 fp32 +=
+    (atomics over K splits), 3 store fp32 * alpha, 4 fp32 += with one writer per element."""
+    dtype, amode, M, N, K, epi, alpha = row["dtype"], row["amode"], row["M"], row["N"], row["K"], row["epi"], row["alpha"]
+    tt = TT[dtype]
+    W, Wst, ldw = _stored(g, N, K, 0, row["pad"][1], tt, scale=K ** -0.5)
+    extra = None
+    if amode == 1:
+        x = torch.randn(M, K, generator=g) * 3.0
+        ln = (1.0 + 0.1 * torch.randn(K, generator=g)).float()
+        rstd = torch.rsqrt(x.double().pow(2).mean(-1, keepdim=True) + 1e-6)
+        A = (ln.double() * (x.double() * rstd).to(tt).double()).to(tt)
+        Ast, lda = x, K
+        # the kernel's fp32 rstd may round an element of x rstd or of ln * that to the neighbouring T value: allow two such flips per row
+        if dtype == 1:
+            extra = 2.0 ** -6 * (A.double().abs()[:, None, :] * W.double().abs()[None, :, :]).amax(-1)
+    else:
+        A, Ast, lda = _stored(g, M, K, 0, row["pad"][0], tt)
+    out_f32 = epi in (2, 3, 4)
+    ct = torch.float32 if out_f32 else tt
+    ldc = (N + 7) // 8 * 8 + row["pad"][2]
+    Cst = _sentinel((M + 2, ldc), ct)
+    C0 = None
+    if epi in (2, 4):
+        C0 = torch.randn(M, N, generator=g)
+        Cst[:M, :N] = C0
+    ref, S, Pt, zero = _gemm_ref_out(A, W, {2: 4, 4: 6}.get(epi, 0 if epi == 3 else epi), alpha, None, C0, None, 0.0)
+    Ad, Wd, Cd = dev(be, Ast), dev(be, Wst), dev(be, Cst)
+    lnd = dev(be, ln) if amode == 1 else None
+    keepalive.extend([Ad, Wd, Cd, lnd])
+    be.check(be.lib.p5_op_skinny_gemm(dtype, amode, P(Ad), lda, P(lnd), P(Wd), ldw, P(Cd), ldc, M, N, K, epi, alpha, 1e-6, be.stream_ptr()),
+             f"skinny {row['id']}")
+    checks.append(dict(Cd=Cd, ref=ref, S=S, P=Pt, zero=zero, M=M, N=N, c_bf16=ct == torch.bfloat16, epi=1 if epi == 1 else 0, aux=None, keep=None, ssq=None,
+                       alpha=alpha, extra=extra, tag=f"{row['id']}"))
+
+
 def gemm_split_case(be, M, N, K, epi=0, seed=0, scale_a=1.0, scale_b=0.05):
     """fp32 operands with the products on the f16 matrix cores (p5_gemm.h, two-term split; dtype code 2 of p5_op_gemm) against an fp64
     product: the error must be of the order of an fp32 GEMM's own (a few 2^-22 relative per product), nowhere near fp16's or bf16's."""

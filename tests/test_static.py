@@ -52,3 +52,30 @@ def test_engine_issues_atomic_gemms_with_one_split():
     assert len(sites) == 2, sites
     assert "g.splitk = g_opt_wgrad_split_atomic ? 0 : 1" in src
     assert "g.c_split_stride = (long long)Md * d" in src
+
+
+def _gemm_launch_sites():
+    """first argument of every P5_LAUNCH in p5_gemm_tu.hip, outside the P5_GEMM5_ABL lab build"""
+    src = open(os.path.join(CSRC, "p5_gemm_tu.hip")).read()
+    src = re.sub(r"#ifdef P5_GEMM5_ABL.*?#else", "", src, flags=re.S)
+    sites = []
+    for m in re.finditer(r"P5_LAUNCH\(\(", src):
+        i, depth = m.end(), 1
+        while depth:
+            depth += {"(": 1, ")": -1}.get(src[i], 0)
+            i += 1
+        sites.append("".join(src[m.end():i - 1].split()))
+    return sites
+
+
+def test_every_gemm_launch_site_has_a_route_row():
+    """tests/gemm_matrix.py names every launch site of the GEMM dispatcher (cases.gemm_ref_case checks the rows against float64 and, in
+    the profiler's report, that they reach their site): a new kernel instance or launch branch needs a row there."""
+    from tests.gemm_matrix import launch_sites
+    sites = _gemm_launch_sites()
+    assert len(sites) >= 25, sites
+    named = {"".join(s.split()) for s in launch_sites()}
+    missing = [s for s in sites if s not in named]
+    assert not missing, f"GEMM launch sites without a row in tests/gemm_matrix.py: {missing}"
+    stale = sorted(named - set(sites))
+    assert not stale, f"rows of tests/gemm_matrix.py name launch sites that no longer exist: {stale}"
