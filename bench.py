@@ -4,13 +4,17 @@ T5-small on ML-1M-shaped synthetic data (B=64/GPU, seq
 dropout 0.1, V=32100), one process per GPU.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = forward + runner masked-mean loss + backward (+ gradient all-reduce overlapped with it when N > 1) +
 global-norm clip + AdamW + schedule + zero_grad, i.e. DistributedRunner.py:56-93 minus the Python collator (inputs are
 resident in HBM before the timed region).  Prints ONE JSON line on rank 0.
 
-Besides the headline (C2) the line carries, at N = 1 only (`--legs none` drops them):
+A plain run does only what the headline needs: it builds the model, runs the warm-up steps, times the steps, writes the outputs
+of --dump-outputs and prints the line (metric, value, unit, ms_per_step, dtype, config, final loss, model TFLOP/s).  Everything
+else is measured with `--full` only: the profiled and staged steps, the generation numbers (`beam10_*`, `generation`,
+`generation_plain_bf16`), the communication wait of the data-parallel step (N > 1), and, at N = 1 (`--legs none` drops the legs):
   * `roofline` (dominant kernel of the step by time, profiles/README.md), `roofline_fwd`, `roofline_generation`;
     `traffic` and `mfma_busy` are measured by this run itself when rocprofv3 is on the box (separate `--pmc` subprocess passes over
     tools/gemm_one.py and tools/gen_bench.py, bench.pmc_live); otherwise they come from profiles/pmc_traffic.json with `traffic_stale: true`;
@@ -22,8 +26,8 @@ Besides the headline (C2) the line carries, at N = 1 only (`--legs none` drops t
 
 `--dump-outputs DIR` writes, on rank 0, what the timed path computed: the loss of the last timed training step, the norm of every
 parameter tensor after it and a fixed, seeded sample of the parameter values (`train_*.npy`), and the sequences and scores of the last
-timed headline generation call (`generation_*.npy`, unless --no-gen).  Inputs and weights are seeded, so two builds run with the same
-arguments can be compared output for output.
+timed headline generation call (`generation_*.npy`, unless --no-gen; a plain run makes that headline generation call for the dump, and
+reports nothing of it).  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -216,11 +220,12 @@ def kernel_classes(rows):
     return sorted(cls.values(), key=lambda c: -c["us_per_step"])
 
 
-def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, seed, vocab=V, mode=None, keep=None):
+def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, seed, vocab=V, mode=None, keep=None, extras=True):
     """`batches` generate() calls of `gB` users, beam `gK`, bracketed like the training step (barrier + synchronize).  mode (bf16 models):
     "verified" = the bf16 search with extra beams proposes, one fp32 pass decides (lists and scores are the fp32 search's: csrc/p5_verify.h),
     "draft" = the plain bf16 search.  Returns (seconds, decoded length, engine timing of the search kernels, per-call median ms, stats);
-    a dict `keep` receives the sequences and scores of the last timed call."""
+    a dict `keep` receives the sequences and scores of the last timed call.  extras=False skips the untimed calls after the timed region
+    (engine timing and per-call median are then None)."""
     from openp5_amd.trie import prefix_allowed_tokens_fn
     model.eval()
     if mode is not None:
@@ -249,6 +254,9 @@ def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, 
     if keep is not None:          # what the last timed call returned (copied before the untimed calls below run)
         keep.update(sequences=o["sequences"].clone(), sequences_scores=o["sequences_scores"].clone())
     stats = dict(model.verify_stats)
+    stats["lanes"] = lanes
+    if not extras:
+        return gdt, int(o["sequences"].shape[1]), None, None, stats
     # per-call wall times (each call ends with the read of the result lengths, i.e. is synchronous) and the device time of the search's
     # decode loop alone (engine-side HIP events around it), both on extra calls OUTSIDE the timed region
     per_call = []
@@ -272,7 +280,6 @@ def time_generation(model, gB, gK, L, trie, max_length, batches, world, device, 
         timing = {"encode_ms": sorted(enc)[1], "decode_ms": sorted(dec)[1], "forced_prefix_steps": ff,
                   "source": "HIP events recorded by p5_generate around its decode loop, median of 3 calls; encode_ms = encoder pass (or the cast of the "
                             "verification pass's encoder output) + the forced-prefix pass + cross-attention K/V + beam state"}
-    stats["lanes"] = lanes
     return gdt, int(o["sequences"].shape[1]), timing, sorted(per_call)[len(per_call) // 2], stats
 
 
@@ -736,11 +743,14 @@ def main():
     ap.add_argument("--seq-len", type=int, default=128)
     ap.add_argument("--tgt-len", type=int, default=8)
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--no-gen", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--legs", default="all", help="all | none | comma list of: configs,task_mix")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: profiled and staged steps, generation, roofline, legs, CPU baselines")
+    ap.add_argument("--no-gen", action="store_true", help="no generation (--full), no generation_*.npy (--dump-outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--legs", default="all", help="--full: all | none | comma list of: configs,task_mix")
     ap.add_argument("--gen-batches", type=int, default=20)
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc subprocess passes (roofline.traffic / mfma_busy then come from profiles/*.json, marked stale)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 --pmc subprocess passes (roofline.traffic / mfma_busy then come "
+                                                          "from profiles/*.json, marked stale)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed training step (and the last timed headline generation call) returned as DIR/<name>.npy")
     args = ap.parse_args()
@@ -763,9 +773,10 @@ def main():
     dt, final_loss = time_training(model, opt, batch, args.steps, args.warmup, world, device)
     samples_per_s = world * B * args.steps / dt
     dumps = training_outputs(model, final_loss) if (args.dump_outputs and rank == 0) else None      # before any untimed step changes the model
-    prof_rows = profile_training(be, model, opt, batch) if (rank == 0 and world == 1) else None      # outside the timed region
+    full = args.full
+    prof_rows = profile_training(be, model, opt, batch) if (full and rank == 0 and world == 1) else None      # outside the timed region
     staged = None
-    if world == 1 and args.legs != "none":
+    if full and world == 1 and args.legs != "none":
         # the data-parallel code path on ONE GPU: stage-by-stage backward (16 engine calls, gradient ranges reported per stage, the same
         # two-layer weight-gradient groups), no collective -- what staging itself costs against the single-call backward timed above
         # (a fixed number of steps: --steps sizes the timed headline only, so that a run sized from ms_per_step takes K x ms_per_step
@@ -776,7 +787,7 @@ def main():
         staged = {"ms_per_step": sdt / STAGED_STEPS * 1e3, "samples_per_s": B * STAGED_STEPS / sdt, "steps": STAGED_STEPS,
                   "note": "p5_backward_stage x 16 + p5_backward_final_range per stage, world size 1, no all-reduce"}
     comm_wait_ms = None
-    if world > 1:
+    if full and world > 1:
         # device time the main stream waits for the gradient exchange after the last backward stage (extra steps outside the timed region)
         model.ddp_timing, model.ddp_wait_ms = True, []
         for _ in range(5):
@@ -789,8 +800,9 @@ def main():
     # ---- beam-10 constrained generation: items/s (B=20 users/GPU, K=10, ML1M-sized trie of 3416 items) ----
     # HEADLINE = the bf16 model's default "verified" mode: ranked lists and scores are the fp32 search's (tests/test_gpu_dataset.py holds it to
     # the fp32 criteria against the oracle); the plain bf16 search ("draft": lists may differ at near-ties) is reported next to it.
+    # (a plain run makes only the headline call, and only for the arrays of --dump-outputs; on every rank, as the call holds barriers)
     gen = gen_draft = None
-    if not args.no_gen:
+    if not args.no_gen and (full or args.dump_outputs):
         gB, gK = 20, 10
         trie = synth_item_trie(3416, 7)
         # random-init weights of the architecture (as every generation number of rounds 1-4's fp32 leg and tools/gen_bench.py): the model the
@@ -799,28 +811,30 @@ def main():
         trained = model
         _, model, _ = build_model(args.backbone, args.dtype, device, be, world, rank)
         kept = {}
-        gdt, dec_len, timing, med, vst = time_generation(model, gB, gK, L, trie, 30, args.gen_batches, world, device, 500 + rank, mode="verified", keep=kept)
+        gdt, dec_len, timing, med, vst = time_generation(model, gB, gK, L, trie, 30, args.gen_batches, world, device, 500 + rank, mode="verified", keep=kept,
+                                                         extras=full)
         if dumps is not None:         # token ids < 2^24: exact in float32
             dumps.update(generation_sequences=kept["sequences"].float().cpu().numpy(), generation_sequences_scores=kept["sequences_scores"].float().cpu().numpy())
-        gen = {"mode": "verified (bf16 search with 6 extra beams proposes, one teacher-forced fp32 pass decides; csrc/p5_verify.h)",
-               "items_per_s": world * gB * gK * args.gen_batches / gdt, "ms_per_batch": gdt / args.gen_batches * 1e3, "ms_per_batch_median_call": med,
-               "lanes": vst.get("lanes"), "timing_note": "ms_per_batch = timed region / batches with `lanes` batches in flight (throughput); ms_per_batch_median_call = one "
-               "generate() call by itself (latency)", "users_per_batch": gB, "num_beams": gK, "max_length": 30, "trie_items": 3416, "decoded_len": dec_len, "draft_timing_ms": timing,
-               "verify_stats": vst, "weights": "random-init (near-flat item scores; `generation.trained_model` is the same call on trained weights)",
-               "fallback_users": vst.get("fallback_users", 0), "escalated_users": vst.get("escalated_users", 0), "users": vst.get("users", 0)}
-        gdt, dec_len, timing, med, _ = time_generation(model, gB, gK, L, trie, 30, args.gen_batches, world, device, 500 + rank, mode="draft")
-        gen_draft = {"mode": "draft (plain bf16 search)", "items_per_s": world * gB * gK * args.gen_batches / gdt, "ms_per_batch": gdt / args.gen_batches * 1e3,
-                     "ms_per_batch_median_call": med, "users_per_batch": gB, "num_beams": gK, "decoded_len": dec_len, "timing_ms": timing}
-        model.generation_mode = "verified"
-        # (the secondary generation legs -- the noise-trained model, the trained model -- are single-GPU extras: a multi-rank run keeps to the
-        #  training metric and the two headline generation numbers, so that no rank-local failure inside an extra can strand the others at a barrier)
-        if world == 1:
-          gdt, _, _, med, vst2 = time_generation(trained, gB, gK, L, trie, 30, 5, world, device, 500 + rank, mode="verified")
-          gen["after_noise_training"] = {"items_per_s": world * gB * gK * 5 / gdt, "ms_per_batch": gdt / 5 * 1e3, "verify_stats": vst2,
-                                       "note": "the same call on the model the timed training steps left behind (25 steps on random labels): near-uniform item scores, "
-                                               "so the fp32 top-K is not among the bf16 draft's beams for some users; they get a wider draft, then the fp32 search"}
+        if full:
+            gen = {"mode": "verified (bf16 search with 6 extra beams proposes, one teacher-forced fp32 pass decides; csrc/p5_verify.h)",
+                   "items_per_s": world * gB * gK * args.gen_batches / gdt, "ms_per_batch": gdt / args.gen_batches * 1e3, "ms_per_batch_median_call": med,
+                   "lanes": vst.get("lanes"), "timing_note": "ms_per_batch = timed region / batches with `lanes` batches in flight (throughput); ms_per_batch_median_call = one "
+                   "generate() call by itself (latency)", "users_per_batch": gB, "num_beams": gK, "max_length": 30, "trie_items": 3416, "decoded_len": dec_len, "draft_timing_ms": timing,
+                   "verify_stats": vst, "weights": "random-init (near-flat item scores; `generation.trained_model` is the same call on trained weights)",
+                   "fallback_users": vst.get("fallback_users", 0), "escalated_users": vst.get("escalated_users", 0), "users": vst.get("users", 0)}
+            gdt, dec_len, timing, med, _ = time_generation(model, gB, gK, L, trie, 30, args.gen_batches, world, device, 500 + rank, mode="draft")
+            gen_draft = {"mode": "draft (plain bf16 search)", "items_per_s": world * gB * gK * args.gen_batches / gdt, "ms_per_batch": gdt / args.gen_batches * 1e3,
+                         "ms_per_batch_median_call": med, "users_per_batch": gB, "num_beams": gK, "decoded_len": dec_len, "timing_ms": timing}
+            model.generation_mode = "verified"
+            # (the secondary generation legs -- the noise-trained model, the trained model -- are single-GPU extras: a multi-rank run keeps to the
+            #  training metric and the two headline generation numbers, so that no rank-local failure inside an extra can strand the others at a barrier)
+            if world == 1:
+                gdt, _, _, med, vst2 = time_generation(trained, gB, gK, L, trie, 30, 5, world, device, 500 + rank, mode="verified")
+                gen["after_noise_training"] = {"items_per_s": world * gB * gK * 5 / gdt, "ms_per_batch": gdt / 5 * 1e3, "verify_stats": vst2,
+                                               "note": "the same call on the model the timed training steps left behind (25 steps on random labels): near-uniform item scores, "
+                                                       "so the fp32 top-K is not among the bf16 draft's beams for some users; they get a wider draft, then the fp32 search"}
         model = trained
-        if world == 1:
+        if full and world == 1:
             try:
                 gen["trained_model"] = trained_generation_leg(be, device, args.backbone, args.dtype, world, rank, gB, gK, L, 3416, args.gen_batches)
             except Exception as ex:
@@ -830,13 +844,6 @@ def main():
         c = cfg
         inner = c.num_heads * c.d_kv
         flops = train_flops_per_sample(c.d_model, inner, c.d_ff, c.num_heads, c.num_layers, L, T, V)
-        Mg, Ng, Kg = B * L, c.d_ff, c.d_model
-        t_k = time_gemm_kernel(be, Mg, Ng, Kg)
-        ach = 2.0 * Mg * Ng * Kg / t_k / 1e12
-        t_w, fl_w, by_w = time_wgrad_group(be, Mg, c.d_model, c.d_ff, inner)
-        ach_w = fl_w / t_w / 1e12
-        k_fwd = "p5_gemm5_kernel<KC> (256x128 tiles, 4 loader + 4 compute waves, ring of 3 K-steps)"
-        k_wg = "p5_gemm5_kernel<KS> (256x128 tiles, 4 loader + 4 compute waves): the 8 weight gradients of two encoder layers in one launch"
         ddp = None
         if world > 1:
             half = str(getattr(model, "ddp_bucket_dtype", "fp32")).replace("torch.", "") in ("bf16", "bfloat16")
@@ -855,118 +862,128 @@ def main():
             "final_loss": final_loss,
             "model_tflops": samples_per_s * flops / 1e12,
             "model_flops_frac_of_bf16_peak": samples_per_s * flops / 1e12 / (BF16_PEAK_TFLOPS * world),
-            "beam10_items_per_sec": gen["items_per_s"] if gen else None,
-            # users the verification pass could not settle from the bf16 draft (re-run on the plain fp32 search) / users, for the headline call
-            # (random-init weights) and for the same call on a trained model -- the headline's regime is the friendly one only if both are small
-            "beam10_fallback_users_over_users": ([gen["fallback_users"], gen["users"]] if gen else None),
-            "beam10_items_per_sec_trained_model": (gen.get("trained_model", {}).get("items_per_s") if gen else None),
-            "beam10_fallback_users_over_users_trained_model": ([gen["trained_model"].get("fallback_users"), gen["trained_model"].get("users")]
-                                                                if gen and "error" not in gen.get("trained_model", {"error": 1}) else None),
-            "generation": gen,
-            "generation_plain_bf16": gen_draft,
             "distributed": ddp,
-            # `roofline` = the kernel with the largest share of the step's time IN THIS RUN (library profiler, HIP events around every
-            # launch of 3 extra steps outside the timed region): aggregate algorithmic FLOPs of its launches / their summed in-step
-            # durations.  `alone` = its largest shape timed by itself (operands warm) with the PMC HBM traffic of that launch.
-            # `roofline_wgrad`: the grouped weight-gradient launch (two encoder layers, round 3's `roofline`), `step_kernels`: the
-            # whole per-kernel table of the step.
         }
-        live = {}
-        if world == 1 and not args.no_pmc:
-            try:
-                live = pmc_live((Mg, Ng, Kg), want_decode=gen_draft is not None)
-            except Exception as ex:      # (never lose the bench line to a profiler hiccup)
-                live = {"error": repr(ex)[:200]}
-        cls = kernel_classes(prof_rows) if prof_rows else []
-        gemm_cls = [c for c in cls if c["flops_per_step"] > 0]
-        fwd_alone = {"shape": [Mg, Ng, Kg], "avg_launch_us": t_k * 1e6, "achieved": ach, "frac": ach / BF16_PEAK_TFLOPS,
-                     "traffic": pmc_traffic("fwd_wide", (Mg, Ng, Kg)), "algorithmic_bytes": 2.0 * (Mg * Kg + Ng * Kg + Mg * Ng), "traffic_stale": True,
-                     "traffic_source": "STALE: profiles/pmc_traffic.json, collected by an earlier run (profiles/collect_pmc.sh: separate FETCH_SIZE / WRITE_SIZE "
-                                       "passes, FETCH_SIZE x2 on gfx950) -- rocprofv3 was not available to this run or --no-pmc was given"}
-        if live.get("gemm"):
-            fwd_alone.update({"traffic": live["gemm"]["traffic_bytes"], "traffic_read": live["gemm"]["read_bytes"], "traffic_write": live["gemm"]["write_bytes"],
-                              "traffic_stale": False, "traffic_source": live["gemm"]["source"]})
-        if live.get("sq"):
-            fwd_alone.update({"mfma_busy": live["sq"]["mfma_busy"], "wait_frac_of_wave_cycles": live["sq"]["wait_frac_of_wave_cycles"],
-                              "issue_frac_of_wave_cycles": live["sq"]["issue_frac_of_wave_cycles"], "mfma_busy_source": live["sq"]["source"]})
-        wg_alone = {"shape": [[c.d_model, c.d_ff, Mg], [c.d_ff, c.d_model, Mg], [c.d_model, inner, Mg], [3 * inner, c.d_model, Mg]] * 2,
-                    "avg_launch_us": t_w * 1e6, "achieved": ach_w, "frac": ach_w / BF16_PEAK_TFLOPS, "flops_per_launch": fl_w,
-                    "traffic": pmc_traffic("wgrad_group2", (Mg, c.d_model, c.d_ff)), "algorithmic_bytes": by_w, "traffic_stale": True,
-                    "traffic_source": "STALE: profiles/pmc_traffic.json (an earlier run of profiles/collect_pmc.sh)"}
-        if cls:
-            top = cls[0]
-            tf = top["flops_per_step"] / max(top["us_per_step"], 1e-9) / 1e6
-            is_ks = "[KS" in top["kernel"] or " KS]" in top["kernel"]      # (the tag, not the template parameter's name)
-            line["roofline"] = {"bound": "mfma", "kernel": top["kernel"], "achieved": tf, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / BF16_PEAK_TFLOPS,
-                                "launches_per_step": top["launches_per_step"], "us_per_step": top["us_per_step"], "flops_per_step": top["flops_per_step"],
-                                "share_of_kernel_time": top["us_per_step"] / max(1e-9, sum(c["us_per_step"] for c in cls)),
-                                "by_grid": top["grids"], "alone": wg_alone if is_ks else fwd_alone, "traffic": (wg_alone if is_ks else fwd_alone)["traffic"],
-                                "traffic_source": (wg_alone if is_ks else fwd_alone)["traffic_source"], "traffic_stale": (wg_alone if is_ks else fwd_alone).get("traffic_stale", True),
-                                "traffic_of": "one launch of the kernel's largest shape in the step (`alone`), per launch like `alone.achieved`",
-                                "mfma_busy": (None if is_ks else fwd_alone.get("mfma_busy")), "mfma_busy_source": (None if is_ks else fwd_alone.get("mfma_busy_source")),
-                                "source": "p5_profile_begin/end in this run: HIP events around every launch of 3 steps (durations include the dispatch gap)"}
-            # which number to read: `frac` is computed from event-BRACKETED durations (each includes its launch's dispatch gap: an upper bound of
-            # the kernel time, so `frac` is a lower bound).  The smallest bracket of the step (a trivial kernel) bounds that gap from above;
-            # `frac_excl_dispatch` subtracts it per launch and is what a rocprofv3 kernel trace of the same step shows within a few per cent
-            # (profiles/r05_train_in_step.json holds the rocprofv3 durations of this build).
-            floor_us = min(r["total_us"] / max(1, r["launches"]) for r in prof_rows)
-            us_excl = max(1e-9, top["us_per_step"] - floor_us * top["launches_per_step"])
-            line["roofline"]["bracket_floor_us"] = floor_us
-            line["roofline"]["frac_excl_dispatch"] = top["flops_per_step"] / us_excl / 1e6 / BF16_PEAK_TFLOPS
-            ks = [c for c in cls if "p5_gemm5_kernel" in c["kernel"] and "[KS" in c["kernel"]]
-            if ks and not is_ks:
-                k0 = ks[0]
-                tfk = k0["flops_per_step"] / max(k0["us_per_step"], 1e-9) / 1e6
-                line["roofline_wgrad"] = {"bound": "mfma", "kernel": k0["kernel"], "achieved": tfk, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tfk / BF16_PEAK_TFLOPS,
-                                          "launches_per_step": k0["launches_per_step"], "us_per_step": k0["us_per_step"], "alone": wg_alone, "traffic": wg_alone["traffic"]}
-            line["gemm_family"] = {"tflops": sum(c["flops_per_step"] for c in gemm_cls) / max(1e-9, sum(c["us_per_step"] for c in gemm_cls)) / 1e6,
-                                   "us_per_step": sum(c["us_per_step"] for c in gemm_cls), "launches_per_step": sum(c["launches_per_step"] for c in gemm_cls)}
-            line["step_kernels"] = [{"kernel": c["kernel"], "launches_per_step": c["launches_per_step"], "us_per_step": round(c["us_per_step"], 2),
-                                     "tflops": (round(c["flops_per_step"] / max(c["us_per_step"], 1e-9) / 1e6, 1) if c["flops_per_step"] > 0 else None),
-                                     "by_grid": ([{"grid": g["grid"], "launches_per_step": g["launches_per_step"], "avg_us": round(g["avg_us"], 2), "tflops": round(g["tflops"], 1)}
-                                                  for g in c["grids"]] if c["flops_per_step"] > 0 and len(c["grids"]) > 1 else None)} for c in cls]
-            line["step_launches"] = sum(c["launches_per_step"] for c in cls)
-        else:
-            line["roofline"] = dict(bound="mfma", kernel=k_wg, peak=BF16_PEAK_TFLOPS, unit="TFLOP/s", **wg_alone)
-        line["roofline_fwd"] = dict(bound="mfma", kernel=k_fwd, peak=BF16_PEAK_TFLOPS, unit="TFLOP/s", **fwd_alone)
-        if gen_draft:
-            # the decode step of the plain bf16 search (K = 10): the steps the forced-prefix pass did not cover
-            timing = gen_draft["timing_ms"] or {}
-            S = gen_draft["decoded_len"] - 1 - int(timing.get("forced_prefix_steps", 0))
-            timed = timing.get("decode_ms")
-            step_ms = timed / max(1, S) if timed else gen_draft["ms_per_batch"] / max(1, S)
-            byts = gen_bytes_per_step(c.d_model, inner, c.d_ff, c.num_decoder_layers, V, 20, 10, L, (gen_draft["decoded_len"] - 1) // 2 + 1)
-            gbs = byts / (step_ms * 1e-3) / 1e9
-            line["roofline_generation"] = {"bound": "hbm", "kernel": "decode step (all launches of one step), plain bf16 search", "achieved": gbs, "peak": HBM_PEAK_GBS,
-                                           "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "algorithmic_bytes": byts, "ms_per_step": step_ms,
-                                           "steps": S, "forced_prefix_steps": int(timing.get("forced_prefix_steps", 0)),
-                                           "traffic": live["decode"]["traffic_bytes_per_step"] if live.get("decode") else decode_step_traffic(),
-                                           "traffic_stale": not live.get("decode"),
-                                           "traffic_source": live["decode"]["source"] if live.get("decode") else
-                                           "STALE: profiles/pmc_decode_step.json from an earlier run (FETCH_SIZE x2 + WRITE_SIZE over every kernel of the "
-                                           "decode steps of tools/gen_bench.py, separate --pmc passes, per step; fabric-side counters: L2-miss traffic)",
-                                           "time_source": "device time of the decode loop (engine HIP events) / decode steps" if timed else "whole generate() / steps",
-                                           "note": "bytes = decoder weights + tied head once + shared cross-KV + self-KV (SURVEY 8(d)); the steps every item id shares "
-                                                   "run as ONE teacher-forced pass before the loop (p5_decode.h) and are not decode steps"}
-        legs_on = [] if args.legs == "none" else (["configs", "task_mix"] if args.legs == "all" else args.legs.split(","))
-        if world == 1:
-            del model, opt
-            torch.cuda.empty_cache()
-            legs = {}
-            if staged:
-                legs["staged_backward_1gpu"] = staged
-            if "task_mix" in legs_on:
+        if full:
+            Mg, Ng, Kg = B * L, c.d_ff, c.d_model
+            t_k = time_gemm_kernel(be, Mg, Ng, Kg)
+            ach = 2.0 * Mg * Ng * Kg / t_k / 1e12
+            t_w, fl_w, by_w = time_wgrad_group(be, Mg, c.d_model, c.d_ff, inner)
+            ach_w = fl_w / t_w / 1e12
+            k_fwd = "p5_gemm5_kernel<KC> (256x128 tiles, 4 loader + 4 compute waves, ring of 3 K-steps)"
+            k_wg = "p5_gemm5_kernel<KS> (256x128 tiles, 4 loader + 4 compute waves): the 8 weight gradients of two encoder layers in one launch"
+            line.update({
+                "beam10_items_per_sec": gen["items_per_s"] if gen else None,
+                # users the verification pass could not settle from the bf16 draft (re-run on the plain fp32 search) / users, for the headline call
+                # (random-init weights) and for the same call on a trained model -- the headline's regime is the friendly one only if both are small
+                "beam10_fallback_users_over_users": ([gen["fallback_users"], gen["users"]] if gen else None),
+                "beam10_items_per_sec_trained_model": (gen.get("trained_model", {}).get("items_per_s") if gen else None),
+                "beam10_fallback_users_over_users_trained_model": ([gen["trained_model"].get("fallback_users"), gen["trained_model"].get("users")]
+                                                                    if gen and "error" not in gen.get("trained_model", {"error": 1}) else None),
+                "generation": gen,
+                "generation_plain_bf16": gen_draft,
+                # `roofline` = the kernel with the largest share of the step's time IN THIS RUN (library profiler, HIP events around every
+                # launch of 3 extra steps outside the timed region): aggregate algorithmic FLOPs of its launches / their summed in-step
+                # durations.  `alone` = its largest shape timed by itself (operands warm) with the PMC HBM traffic of that launch.
+                # `roofline_wgrad`: the grouped weight-gradient launch (two encoder layers, round 3's `roofline`), `step_kernels`: the
+                # whole per-kernel table of the step.
+            })
+            live = {}
+            if world == 1 and not args.no_pmc:
                 try:
-                    legs["task_mix"] = task_mix_leg(be, device)
-                except Exception as ex:
-                    legs["task_mix"] = {"error": repr(ex)[:300]}
-            if "configs" in legs_on:
-                legs.update(config_legs(be, device, args.dtype))
-            if legs:
-                line["legs"] = legs
-            if not args.no_cpu:
-                line["cpu_baseline"] = cpu_baseline_train_hf() or cpu_baseline_train()      # stock HF when transformers is importable, else the oracle port
-                line["cpu_baseline_generation"] = cpu_baseline_generation()
+                    live = pmc_live((Mg, Ng, Kg), want_decode=gen_draft is not None)
+                except Exception as ex:      # (never lose the bench line to a profiler hiccup)
+                    live = {"error": repr(ex)[:200]}
+            cls = kernel_classes(prof_rows) if prof_rows else []
+            gemm_cls = [c for c in cls if c["flops_per_step"] > 0]
+            fwd_alone = {"shape": [Mg, Ng, Kg], "avg_launch_us": t_k * 1e6, "achieved": ach, "frac": ach / BF16_PEAK_TFLOPS,
+                         "traffic": pmc_traffic("fwd_wide", (Mg, Ng, Kg)), "algorithmic_bytes": 2.0 * (Mg * Kg + Ng * Kg + Mg * Ng), "traffic_stale": True,
+                         "traffic_source": "STALE: profiles/pmc_traffic.json, collected by an earlier run (profiles/collect_pmc.sh: separate FETCH_SIZE / WRITE_SIZE "
+                                           "passes, FETCH_SIZE x2 on gfx950) -- rocprofv3 was not available to this run or --no-pmc was given"}
+            if live.get("gemm"):
+                fwd_alone.update({"traffic": live["gemm"]["traffic_bytes"], "traffic_read": live["gemm"]["read_bytes"], "traffic_write": live["gemm"]["write_bytes"],
+                                  "traffic_stale": False, "traffic_source": live["gemm"]["source"]})
+            if live.get("sq"):
+                fwd_alone.update({"mfma_busy": live["sq"]["mfma_busy"], "wait_frac_of_wave_cycles": live["sq"]["wait_frac_of_wave_cycles"],
+                                  "issue_frac_of_wave_cycles": live["sq"]["issue_frac_of_wave_cycles"], "mfma_busy_source": live["sq"]["source"]})
+            wg_alone = {"shape": [[c.d_model, c.d_ff, Mg], [c.d_ff, c.d_model, Mg], [c.d_model, inner, Mg], [3 * inner, c.d_model, Mg]] * 2,
+                        "avg_launch_us": t_w * 1e6, "achieved": ach_w, "frac": ach_w / BF16_PEAK_TFLOPS, "flops_per_launch": fl_w,
+                        "traffic": pmc_traffic("wgrad_group2", (Mg, c.d_model, c.d_ff)), "algorithmic_bytes": by_w, "traffic_stale": True,
+                        "traffic_source": "STALE: profiles/pmc_traffic.json (an earlier run of profiles/collect_pmc.sh)"}
+            if cls:
+                top = cls[0]
+                tf = top["flops_per_step"] / max(top["us_per_step"], 1e-9) / 1e6
+                is_ks = "[KS" in top["kernel"] or " KS]" in top["kernel"]      # (the tag, not the template parameter's name)
+                line["roofline"] = {"bound": "mfma", "kernel": top["kernel"], "achieved": tf, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / BF16_PEAK_TFLOPS,
+                                    "launches_per_step": top["launches_per_step"], "us_per_step": top["us_per_step"], "flops_per_step": top["flops_per_step"],
+                                    "share_of_kernel_time": top["us_per_step"] / max(1e-9, sum(c["us_per_step"] for c in cls)),
+                                    "by_grid": top["grids"], "alone": wg_alone if is_ks else fwd_alone, "traffic": (wg_alone if is_ks else fwd_alone)["traffic"],
+                                    "traffic_source": (wg_alone if is_ks else fwd_alone)["traffic_source"], "traffic_stale": (wg_alone if is_ks else fwd_alone).get("traffic_stale", True),
+                                    "traffic_of": "one launch of the kernel's largest shape in the step (`alone`), per launch like `alone.achieved`",
+                                    "mfma_busy": (None if is_ks else fwd_alone.get("mfma_busy")), "mfma_busy_source": (None if is_ks else fwd_alone.get("mfma_busy_source")),
+                                    "source": "p5_profile_begin/end in this run: HIP events around every launch of 3 steps (durations include the dispatch gap)"}
+                # which number to read: `frac` is computed from event-BRACKETED durations (each includes its launch's dispatch gap: an upper bound of
+                # the kernel time, so `frac` is a lower bound).  The smallest bracket of the step (a trivial kernel) bounds that gap from above;
+                # `frac_excl_dispatch` subtracts it per launch and is what a rocprofv3 kernel trace of the same step shows within a few per cent
+                # (profiles/r05_train_in_step.json holds the rocprofv3 durations of this build).
+                floor_us = min(r["total_us"] / max(1, r["launches"]) for r in prof_rows)
+                us_excl = max(1e-9, top["us_per_step"] - floor_us * top["launches_per_step"])
+                line["roofline"]["bracket_floor_us"] = floor_us
+                line["roofline"]["frac_excl_dispatch"] = top["flops_per_step"] / us_excl / 1e6 / BF16_PEAK_TFLOPS
+                ks = [c for c in cls if "p5_gemm5_kernel" in c["kernel"] and "[KS" in c["kernel"]]
+                if ks and not is_ks:
+                    k0 = ks[0]
+                    tfk = k0["flops_per_step"] / max(k0["us_per_step"], 1e-9) / 1e6
+                    line["roofline_wgrad"] = {"bound": "mfma", "kernel": k0["kernel"], "achieved": tfk, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tfk / BF16_PEAK_TFLOPS,
+                                              "launches_per_step": k0["launches_per_step"], "us_per_step": k0["us_per_step"], "alone": wg_alone, "traffic": wg_alone["traffic"]}
+                line["gemm_family"] = {"tflops": sum(c["flops_per_step"] for c in gemm_cls) / max(1e-9, sum(c["us_per_step"] for c in gemm_cls)) / 1e6,
+                                       "us_per_step": sum(c["us_per_step"] for c in gemm_cls), "launches_per_step": sum(c["launches_per_step"] for c in gemm_cls)}
+                line["step_kernels"] = [{"kernel": c["kernel"], "launches_per_step": c["launches_per_step"], "us_per_step": round(c["us_per_step"], 2),
+                                         "tflops": (round(c["flops_per_step"] / max(c["us_per_step"], 1e-9) / 1e6, 1) if c["flops_per_step"] > 0 else None),
+                                         "by_grid": ([{"grid": g["grid"], "launches_per_step": g["launches_per_step"], "avg_us": round(g["avg_us"], 2), "tflops": round(g["tflops"], 1)}
+                                                      for g in c["grids"]] if c["flops_per_step"] > 0 and len(c["grids"]) > 1 else None)} for c in cls]
+                line["step_launches"] = sum(c["launches_per_step"] for c in cls)
+            else:
+                line["roofline"] = dict(bound="mfma", kernel=k_wg, peak=BF16_PEAK_TFLOPS, unit="TFLOP/s", **wg_alone)
+            line["roofline_fwd"] = dict(bound="mfma", kernel=k_fwd, peak=BF16_PEAK_TFLOPS, unit="TFLOP/s", **fwd_alone)
+            if gen_draft:
+                # the decode step of the plain bf16 search (K = 10): the steps the forced-prefix pass did not cover
+                timing = gen_draft["timing_ms"] or {}
+                S = gen_draft["decoded_len"] - 1 - int(timing.get("forced_prefix_steps", 0))
+                timed = timing.get("decode_ms")
+                step_ms = timed / max(1, S) if timed else gen_draft["ms_per_batch"] / max(1, S)
+                byts = gen_bytes_per_step(c.d_model, inner, c.d_ff, c.num_decoder_layers, V, 20, 10, L, (gen_draft["decoded_len"] - 1) // 2 + 1)
+                gbs = byts / (step_ms * 1e-3) / 1e9
+                line["roofline_generation"] = {"bound": "hbm", "kernel": "decode step (all launches of one step), plain bf16 search", "achieved": gbs, "peak": HBM_PEAK_GBS,
+                                               "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "algorithmic_bytes": byts, "ms_per_step": step_ms,
+                                               "steps": S, "forced_prefix_steps": int(timing.get("forced_prefix_steps", 0)),
+                                               "traffic": live["decode"]["traffic_bytes_per_step"] if live.get("decode") else decode_step_traffic(),
+                                               "traffic_stale": not live.get("decode"),
+                                               "traffic_source": live["decode"]["source"] if live.get("decode") else
+                                               "STALE: profiles/pmc_decode_step.json from an earlier run (FETCH_SIZE x2 + WRITE_SIZE over every kernel of the "
+                                               "decode steps of tools/gen_bench.py, separate --pmc passes, per step; fabric-side counters: L2-miss traffic)",
+                                               "time_source": "device time of the decode loop (engine HIP events) / decode steps" if timed else "whole generate() / steps",
+                                               "note": "bytes = decoder weights + tied head once + shared cross-KV + self-KV (SURVEY 8(d)); the steps every item id shares "
+                                                       "run as ONE teacher-forced pass before the loop (p5_decode.h) and are not decode steps"}
+            legs_on = [] if args.legs == "none" else (["configs", "task_mix"] if args.legs == "all" else args.legs.split(","))
+            if world == 1:
+                del model, opt
+                torch.cuda.empty_cache()
+                legs = {}
+                if staged:
+                    legs["staged_backward_1gpu"] = staged
+                if "task_mix" in legs_on:
+                    try:
+                        legs["task_mix"] = task_mix_leg(be, device)
+                    except Exception as ex:
+                        legs["task_mix"] = {"error": repr(ex)[:300]}
+                if "configs" in legs_on:
+                    legs.update(config_legs(be, device, args.dtype))
+                if legs:
+                    line["legs"] = legs
+                if not args.no_cpu:
+                    line["cpu_baseline"] = cpu_baseline_train_hf() or cpu_baseline_train()      # stock HF when transformers is importable, else the oracle port
+                    line["cpu_baseline_generation"] = cpu_baseline_generation()
         if dumps is not None:
             dump_arrays(args.dump_outputs, dumps)
         print(json.dumps(line), flush=True)

@@ -6,7 +6,7 @@ export PYTHONDONTWRITEBYTECODE=1
 mkdir -p gpurun_out
 cp openp5_amd/libp5hip.so /tmp/libp5hip_product.so
 one() {   # label
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-gen --legs none 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-gen --legs none 2>/dev/null | python -c "
 import sys, json
 l = json.loads([x for x in sys.stdin if x.startswith('{')][-1])
 kc = [k for k in l.get('step_kernels', []) if 'KC' in k['kernel'] and 'gemm5' in k['kernel']]

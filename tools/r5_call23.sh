@@ -9,7 +9,7 @@ timeout 300 python -m pytest tests/test_gpu_parity.py -q -k "storing_masks" 2>&1
 timeout 400 python -m pytest tests/test_gpu_parity.py -q -k "head_resident or keep_masks or attention or L512" 2>&1 | tail -4
 for BITS in 1 0; do
   echo "C5 step, P5_ATTN_KEEP_BITS=$BITS"
-  P5_ATTN_KEEP_BITS=$BITS timeout 300 python bench.py --backbone t5-large --seq-len 512 --tgt-len 10 --steps 3 --warmup 1 --legs none --no-gen --no-cpu 2>&1 | grep '^{' | python -c "
+  P5_ATTN_KEEP_BITS=$BITS timeout 300 python bench.py --full --backbone t5-large --seq-len 512 --tgt-len 10 --steps 3 --warmup 1 --legs none --no-gen --no-cpu 2>&1 | grep '^{' | python -c "
 import sys, json
 l = json.loads(sys.stdin.read()); print('ms/step', l['ms_per_step'], 'samples/s', l['value'], 'final_loss', l.get('final_loss'))
 for c in l.get('step_kernels', []): 

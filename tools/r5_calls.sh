@@ -4,11 +4,12 @@
 cd "$(dirname "$0")/.."
 export PYTHONDONTWRITEBYTECODE=1
 mkdir -p gpurun_out
+export RES="${RES:-results}"; mkdir -p "$RES"      # where the bench lines and their summaries go
 case "$1" in
 2)
 # round 5, call 2: the gemm5 epilogue with every load issued before the first store (bench line), verified generation (timing + GPU tests)
-timeout 600 python bench.py --no-cpu --legs none --no-gen > gpurun_out/r5_bench1.log 2>&1
-grep '^{' gpurun_out/r5_bench1.log | tail -1 | python -c "
+timeout 600 python bench.py --full --no-cpu --legs none --no-gen > "$RES/r5_bench1.log" 2>&1
+grep '^{' "$RES/r5_bench1.log" | tail -1 | python -c "
 import sys, json
 l = json.loads(sys.stdin.read())
 kc = [k for k in l.get('step_kernels', []) if 'KC' in k['kernel'] and 'gemm5' in k['kernel']]
@@ -75,11 +76,11 @@ OUT=gpurun_out/r5_call7.txt; : > $OUT
 timeout 300 python tools/gemm_split_probe.py 2>&1 | tail -9 | tee -a $OUT
 timeout 2400 python -m pytest tests -q -m gpu -s --durations=15 > gpurun_out/r5_gpu_suite_full.log 2>&1
 grep "\[dataset\]\|\[verified\|passed\|failed\|FAILED\|slowest\|^[0-9.]*s call" gpurun_out/r5_gpu_suite_full.log | cut -c1-700 | tee -a $OUT
-timeout 900 python bench.py > gpurun_out/r5_bench_full.log 2>&1
-grep '^{' gpurun_out/r5_bench_full.log | tail -1 > gpurun_out/r5_bench_line.json
+timeout 900 python bench.py --full > "$RES/r5_bench_full.log" 2>&1
+grep '^{' "$RES/r5_bench_full.log" | tail -1 > "$RES/r5_bench_line.json"
 python - <<'PY' | tee -a $OUT
-import json
-l = json.load(open("gpurun_out/r5_bench_line.json"))
+import json, os
+l = json.load(open(os.environ["RES"] + "/r5_bench_line.json"))
 print("ms/step", l["ms_per_step"], "samples/s", l["value"], "roofline", {k: l["roofline"].get(k) for k in ("kernel", "frac", "frac_excl_dispatch", "bracket_floor_us", "us_per_step")})
 print("generation", {k: l["generation"].get(k) for k in ("items_per_s", "ms_per_batch", "ms_per_batch_median_call", "verify_stats")})
 print("plain bf16", {k: l["generation_plain_bf16"].get(k) for k in ("items_per_s", "ms_per_batch", "timing_ms")})
@@ -106,8 +107,8 @@ for m in verified draft; do for l in 2 3; do P5_GEN_MODE=$m timeout 200 python t
 11)
 OUT=gpurun_out/r5_call11.txt; : > $OUT
 timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_runner.py tests/test_gpu_ddp.py -x -q -k "lanes or runner or filtered or world2 or two_ranks or resume" 2>&1 | tail -5 | tee -a $OUT
-timeout 600 python bench.py --no-cpu --legs none --steps 5 --warmup 2 > gpurun_out/r5_bench_lanes.log 2>&1
-grep '^{' gpurun_out/r5_bench_lanes.log | tail -1 | python -c "
+timeout 600 python bench.py --full --no-cpu --legs none --steps 5 --warmup 2 > "$RES/r5_bench_lanes.log" 2>&1
+grep '^{' "$RES/r5_bench_lanes.log" | tail -1 | python -c "
 import sys, json
 l = json.loads(sys.stdin.read())
 g = l['generation']; d = l['generation_plain_bf16']
@@ -115,7 +116,7 @@ print('verified', {k: g.get(k) for k in ('items_per_s', 'ms_per_batch', 'ms_per_
 print('after noise', g.get('after_noise_training'))
 print('plain', {k: d.get(k) for k in ('items_per_s', 'ms_per_batch', 'ms_per_batch_median_call')})
 " | tee -a $OUT
-tail -3 gpurun_out/r5_bench_lanes.log | cut -c1-300
+tail -3 "$RES/r5_bench_lanes.log" | cut -c1-300
   ;;
 12)
 for m in verified draft; do for l in 2 3 4; do P5_GEN_LANES=$l P5_GEN_MODE=$m timeout 200 python tools/gen_bench.py 20 10 10 2>&1 | grep lanes: | sed "s/^/$m /"; done; done | tee gpurun_out/r5_call12.txt

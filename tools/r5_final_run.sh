@@ -4,6 +4,7 @@
 cd "$(dirname "$0")/.."
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 mkdir -p gpurun_out
+export RES="${RES:-results}"; mkdir -p "$RES"      # where the bench lines and their summaries go
 bash profiles/collect_pmc.sh > gpurun_out/r5_pmc.log 2>&1 || tail -5 gpurun_out/r5_pmc.log
 for CTR in FETCH_SIZE WRITE_SIZE; do
   D=gpurun_out/pmc_gen_$CTR; rm -rf $D
@@ -17,11 +18,11 @@ bash profiles/profile.sh r05_train_t5small_b64 python bench.py --steps 10 --warm
 P5_GEN_MODE=draft bash profiles/profile.sh r05_generate_t5small_b20_k10 python tools/gen_bench.py 20 10 10
 P5_GEN_MODE=verified bash profiles/profile.sh r05_generate_verified_t5small_b20_k10 python tools/gen_bench.py 20 10 10
 timeout 60 tools/probe/grid_barrier.bin > gpurun_out/r05_grid_barrier_probe.txt 2>&1
-timeout 900 python bench.py > gpurun_out/r5_bench_full.log 2>&1
-grep '^{' gpurun_out/r5_bench_full.log | tail -1 > gpurun_out/r05_bench_line.json
+timeout 900 python bench.py --full > "$RES/r5_bench_full.log" 2>&1
+grep '^{' "$RES/r5_bench_full.log" | tail -1 > "$RES/r05_bench_line.json"
 python -c "
 import json
-l = json.load(open('gpurun_out/r05_bench_line.json'))
+l = json.load(open('$RES/r05_bench_line.json'))
 print('ms/step', l['ms_per_step'], 'gen', l['generation']['items_per_s'], l['generation']['verify_stats'], 'after noise', l['generation'].get('after_noise_training'), 'plain', l['generation_plain_bf16']['items_per_s'])
 print('roofline_generation', l.get('roofline_generation'))
 "

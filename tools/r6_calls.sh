@@ -3,6 +3,7 @@
 cd "$(dirname "$0")/.."
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 mkdir -p gpurun_out
+export RES="${RES:-results}"; mkdir -p "$RES"      # where the bench lines and their summaries go
 case "$1" in
 1)
   # Round-6 call 1: the round's new parity tests on the hardware (verified generation at K = 20 / 22 / 23 on T5-base dims, split range guard,
@@ -11,10 +12,10 @@ case "$1" in
 python -c "import __graft_entry__ as g; g.build()" 2>&1 | tail -3
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -s -k "verified or adamw or abi or version or range_guard or generate" 2>&1 | grep -v "^W2026\|^E2026" | tail -25
 for a in "0 1" "1 1" "0 1" "1 1" "1 3"; do timeout 200 python tools/train_ab_side.py $a 2>&1 | grep side_stream; done
-timeout 600 python bench.py --legs none --no-cpu 2>gpurun_out/r6_call1_bench.err | grep '^{' > gpurun_out/r6_call1_bench.json
+timeout 600 python bench.py --full --legs none --no-cpu 2>"$RES/r6_call1_bench.err" | grep '^{' > "$RES/r6_call1_bench.json"
 python - <<'PY'
-import json
-l = json.load(open('gpurun_out/r6_call1_bench.json'))
+import json, os
+l = json.load(open(os.environ['RES'] + '/r6_call1_bench.json'))
 print('ms/step', l['ms_per_step'], 'gen', l['generation']['items_per_s'], l['generation']['verify_stats'], 'plain', l['generation_plain_bf16']['items_per_s'])
 print('roofline', {k: l['roofline'][k] for k in ('kernel', 'frac', 'frac_excl_dispatch', 'us_per_step', 'launches_per_step')})
 for c in l.get('step_kernels', [])[:24]: print('   ', c['kernel'][:100], c['launches_per_step'], round(c['us_per_step']), c.get('tflops'))
@@ -31,11 +32,11 @@ timeout 600 python tools/train_ab_opts.py base= stag4=gemm5_stagger:4 stag8=gemm
 cp openp5_amd/libp5hip.so /tmp/libp5hip_product.so
 cp tools/lab/ablate/libp5hip_nt.so openp5_amd/libp5hip.so && timeout 300 python tools/train_ab_opts.py nt_stores= nt_stag8=gemm5_stagger:8 2>&1 | grep "ms/step"
 cp /tmp/libp5hip_product.so openp5_amd/libp5hip.so
-timeout 900 python bench.py --legs none --no-cpu 2>gpurun_out/r6_call2_bench.err | grep '^{' > gpurun_out/r6_call2_bench.json
-tail -3 gpurun_out/r6_call2_bench.err
+timeout 900 python bench.py --full --legs none --no-cpu 2>"$RES/r6_call2_bench.err" | grep '^{' > "$RES/r6_call2_bench.json"
+tail -3 "$RES/r6_call2_bench.err"
 python - <<'PY'
-import json
-l = json.load(open('gpurun_out/r6_call2_bench.json'))
+import json, os
+l = json.load(open(os.environ['RES'] + '/r6_call2_bench.json'))
 print('ms/step', l['ms_per_step'], 'gen', l['generation']['items_per_s'], 'fallback/users', l.get('beam10_fallback_users_over_users'))
 print('trained', json.dumps(l['generation'].get('trained_model'))[:900])
 r = l['roofline']
@@ -52,11 +53,11 @@ PY
 python -c "import __graft_entry__ as g; g.build()" 2>&1 | tail -2
 timeout 1500 python -m pytest tests/test_gpu_parity.py -x -q -s -k "logit_free or adamw or gate or gated or reproducible or resume or trajectory or benchmark_shape or fused_loss or dropout_on or model_t5_small" 2>&1 | grep -v "^W2026\|^E2026" | tail -16
 timeout 600 python tools/train_ab_opts.py base= ce_mat=ce_free:0 adamflat=adam_tiles:0 both_old=ce_free:0,adam_tiles:0 2>&1 | grep "ms/step"
-timeout 900 python bench.py --legs none --no-cpu 2>gpurun_out/r6_call3_bench.err | grep '^{' > gpurun_out/r6_call3_bench.json
-tail -3 gpurun_out/r6_call3_bench.err
+timeout 900 python bench.py --full --legs none --no-cpu 2>"$RES/r6_call3_bench.err" | grep '^{' > "$RES/r6_call3_bench.json"
+tail -3 "$RES/r6_call3_bench.err"
 python - <<'PY'
-import json
-l = json.load(open('gpurun_out/r6_call3_bench.json'))
+import json, os
+l = json.load(open(os.environ['RES'] + '/r6_call3_bench.json'))
 print('ms/step', l['ms_per_step'], 'gen', l['generation']['items_per_s'], 'fallback/users', l.get('beam10_fallback_users_over_users'))
 t = l['generation'].get('trained_model', {})
 print('trained', {k: v for k, v in t.items() if k not in ('note', 'verify_stats')})
@@ -72,7 +73,7 @@ PY
 python -c "import __graft_entry__ as g; g.build()" 2>&1 | tail -2
 timeout 300 python tools/probe/tr_wait_probe.py 2>&1 | grep -v "^W2026\|^E2026" | tail -12
 timeout 400 python tools/train_ab_opts.py base= ring512=gemm_ring128_min_k:512 2>&1 | grep "ms/step"
-timeout 300 python bench.py --legs none --no-cpu --no-gen --no-pmc 2>/dev/null | grep '^{' | python -c "
+timeout 300 python bench.py --full --legs none --no-cpu --no-gen --no-pmc 2>/dev/null | grep '^{' | python -c "
 import sys, json
 l = json.loads(sys.stdin.read()); print('ms/step', l['ms_per_step'])
 for c in l.get('step_kernels', []): 
@@ -119,7 +120,7 @@ python profiles/timeline_rocpd.py "$DB" gpurun_out/r6_timeline.txt
 rm -rf $OUT/*.db
 timeout 900 python -m pytest tests/test_gpu_parity.py -q -x -k "generate or skinny or decode" 2>&1 | grep -v "^W2026\|^E2026" | tail -4
 for x in 1 0; do
-  P5_DEC_XCD=$x timeout 300 python bench.py --legs none --no-cpu --steps 5 --warmup 2 2>/dev/null | grep '^{' | python -c "
+  P5_DEC_XCD=$x timeout 300 python bench.py --full --legs none --no-cpu --steps 5 --warmup 2 2>/dev/null | grep '^{' | python -c "
 import sys, json
 l = json.loads(sys.stdin.read()); g = l['roofline_generation']
 print('dec_xcd=$x', 'ms/step', l['ms_per_step'], 'gen items/s', l['beam10_items_per_sec'], 'decode step ms', g['ms_per_step'], 'traffic MB', round((g.get('traffic') or 0) / 1e6, 1), 'stale', g.get('traffic_stale'), 'plain', l['generation_plain_bf16'].get('items_per_s'))

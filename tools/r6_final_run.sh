@@ -4,6 +4,7 @@
 cd "$(dirname "$0")/.."
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 mkdir -p gpurun_out
+export RES="${RES:-results}"; mkdir -p "$RES"      # where the bench lines and their summaries go
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" 2>&1 | grep -v "^W2026\|^E2026" | tail -6 > gpurun_out/r06_smoke.txt; cat gpurun_out/r06_smoke.txt
 bash profiles/collect_pmc.sh > gpurun_out/r6_pmc.log 2>&1 || tail -5 gpurun_out/r6_pmc.log
 for CTR in FETCH_SIZE WRITE_SIZE; do
@@ -16,11 +17,11 @@ rm -rf gpurun_out/pmc gpurun_out/pmc_gen_FETCH_SIZE gpurun_out/pmc_gen_WRITE_SIZ
 bash profiles/profile.sh r06_train_t5small_b64 python bench.py --steps 10 --warmup 3 --no-cpu --no-gen --no-pmc --legs none
 P5_GEN_MODE=draft bash profiles/profile.sh r06_generate_t5small_b20_k10 python tools/gen_bench.py 20 10 10
 P5_GEN_MODE=verified bash profiles/profile.sh r06_generate_verified_t5small_b20_k10 python tools/gen_bench.py 20 10 10
-timeout 1500 python bench.py > gpurun_out/r6_bench_full.log 2>&1
-grep '^{' gpurun_out/r6_bench_full.log | tail -1 > gpurun_out/r06_bench_line.json
+timeout 1500 python bench.py --full > "$RES/r6_bench_full.log" 2>&1
+grep '^{' "$RES/r6_bench_full.log" | tail -1 > "$RES/r06_bench_line.json"
 python -c "
 import json
-l = json.load(open('gpurun_out/r06_bench_line.json'))
+l = json.load(open('$RES/r06_bench_line.json'))
 print('ms/step', l['ms_per_step'], 'value', l['value'], 'gen', l['generation']['items_per_s'], 'fallback', l['beam10_fallback_users_over_users'], 'trained', l['beam10_items_per_sec_trained_model'], l['beam10_fallback_users_over_users_trained_model'], 'plain', l['generation_plain_bf16']['items_per_s'])
 r = l['roofline']; print('roofline', r['kernel'], r['frac'], r['frac_excl_dispatch'], r['us_per_step'], r['launches_per_step'], 'traffic', r['traffic'], r['traffic_stale'], 'mfma_busy', r['mfma_busy'])
 print('alone', {k: v for k, v in r['alone'].items() if k in ('shape', 'avg_launch_us', 'achieved', 'traffic', 'algorithmic_bytes', 'mfma_busy')})
