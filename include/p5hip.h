@@ -322,6 +322,48 @@ int p5_op_attn_bwd_dot(int dtype, const void* Q, const void* K, const void* V, c
                        int ldv, int ldo, int lddq, int lddk, int lddv, int causal, const uint32_t* rng_state, uint32_t site, float drop_p,
                        float* dot_out, void* stream);
 int p5_op_ce_fwd(float* nll, float* lse, const float* logits, const int64_t* labels, int rows, int V, int ldl, void* stream);
+/* ---- the row kernels with every argument their launchers take, at the engine's launch geometry (tests/elem_matrix.py).  Dropout as in
+ * p5_op_gemm: rng_state NULL or drop_p 0 = none; the element index is row * d + column. ---- */
+/* T5LayerNorm forward with dropout on y (the final norms) */
+int p5_op_rmsnorm_fwd_drop(int dtype, void* y, float* rstd, const void* x, const float* w, int rows, int d, float eps,
+                           const uint32_t* rng_state, uint32_t site, float drop_p, void* stream);
+/* T5LayerNorm backward: p5_op_rmsnorm_bwd plus dropout on the incoming dy (site_in) and on dy_next (site_next); ssq_part [rows, d / 64]
+ * partial sums of squares of x instead of rstd (the folded-norm forward; rstd may then be NULL, eps is used), n_out T [rows, d] = the
+ * forward norm's output recomputed (may be NULL) */
+int p5_op_rmsnorm_bwd_full(int dtype, float* dres_out, void* dy_next, float* dw, const void* dy, const void* x, const float* w,
+                           const float* rstd, const float* dres_in, int rows, int d, float* dw_partial, const uint32_t* rng_state,
+                           uint32_t site_in, float drop_in_p, uint32_t site_next, float drop_next_p, const float* ssq_part, void* n_out,
+                           float eps, void* stream);
+/* out T [rows, d] = dropout(E[ids] (+ WW[ww] when WW != NULL)); ssq_part [rows, d / 64] (may be NULL) = sums of squares of the stored row
+ * per 64 columns.  d a multiple of 64, <= 1024 */
+int p5_op_embed_fwd(int dtype, void* out, const void* E, const void* WW, const int64_t* ids, const int64_t* ww, int rows, int d,
+                    const uint32_t* rng_state, uint32_t site, float drop_p, float* ssq_part, void* stream);
+/* Gradient of embedding lookups: table[key[r], :] += dropout(dres[r, :]) over one or two sets (HOST array), each the concatenation of up
+ * to two key arrays with their own gradient rows and dropout sites.  mode 0: the fp32 atomic scatter (p5_set_option("embed_det", 0));
+ * mode 1: the fixed-order chain of openp5_amd/csrc/p5_embed.h (sort chunks, rank, segmented sum, fix-up), whose grids the FIRST set sizes
+ * (a later set may not be longer).  Scratch of mode 1, per set with n = n0 + n1, written by the chain and readable afterwards:
+ * idx int[4 * n] = perm | skey | sstart | slen, csort uint64[ceil(n / 256) * 256], part float[ceil(n / 32) * 2 * d]. */
+typedef struct P5EmbedBwdSet {
+  const int64_t *key0, *key1;
+  const float *dres0, *dres1;     /* fp32 [n0, d] / [n1, d] */
+  int n0, n1;
+  uint32_t site0, site1;
+  float drop_p0, drop_p1;
+  float* table;                   /* fp32 [*, d], += */
+  int* idx;
+  unsigned long long* csort;
+  float* part;
+} P5EmbedBwdSet;
+int p5_op_embed_bwd(int dtype, int mode, int nsets, int d, const P5EmbedBwdSet* sets, const uint32_t* rng_state, void* stream);
+/* p5_op_ce_fwd with the exponential of the mode (dtype 0: expf, 1: the fast exponential of the bf16 mode) */
+int p5_op_ce_fwd_t(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, int rows, int V, int ldl, void* stream);
+/* dlogits T [rows, ldd] = (softmax - onehot) * g, columns [V, ldd) zero; g = dnll[row], or with dnll NULL the masked-mean rule
+ * out_attn[row] != 0 ? gscale / max(count of the row's batch item, 1) : 0 (out_attn [rows / T, T]); 0 where the label is -100.
+ * grid_y = column slices per row (the engine: 1, 4 or 8 by row count).  g_out [rows] (may be NULL): the same g by p5_ce_gscale_kernel. */
+int p5_op_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const float* dnll, int rows,
+                 int V, int ldl, int ldd, const int64_t* out_attn, int T, float gscale, int grid_y, float* g_out, void* stream);
+/* loss[0] = mean_b(sum_t nll[b, t] m[b, t] / max(sum_t m[b, t], 1)), m = (out_attn != 0) */
+int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];
  * amode 1: A = fp32 residual stream [M, K], normalised with T5LayerNorm weight `ln` by the kernel itself.
  * epi: 0 store T (alpha), 1 relu store T, 2 fp32 atomic accumulate (split-K), 3 store fp32 (alpha) */

@@ -22,6 +22,11 @@ class P5GemmProblem(C.Structure):
                 ("nb_dot", vp), ("nb_dot_nt", i32), ("nb_rin", vp), ("nb_rout", vp), ("nb_w", vp), ("nb_dw", vp)]
 
 
+class P5EmbedBwdSet(C.Structure):
+    _fields_ = [("key0", vp), ("key1", vp), ("dres0", vp), ("dres1", vp), ("n0", i32), ("n1", i32), ("site0", u32), ("site1", u32),
+                ("drop_p0", f32), ("drop_p1", f32), ("table", vp), ("idx", vp), ("csort", vp), ("part", vp)]
+
+
 # name -> (restype, argtypes)
 PROTOTYPES = {
     "p5_last_error": (C.c_char_p, []),
@@ -90,6 +95,13 @@ PROTOTYPES = {
     "p5_op_attn_bwd_dot": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32,
                                 i32, i32, i32, i32, vp, u32, f32, vp, vp]),
     "p5_op_ce_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p5_op_rmsnorm_fwd_drop": (i32, [i32, vp, vp, vp, vp, i32, i32, f32, vp, u32, f32, vp]),
+    "p5_op_rmsnorm_bwd_full": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, u32, f32, u32, f32, vp, vp, f32, vp]),
+    "p5_op_embed_fwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, u32, f32, vp, vp]),
+    "p5_op_embed_bwd": (i32, [i32, i32, i32, i32, C.POINTER(P5EmbedBwdSet), vp, vp]),
+    "p5_op_ce_fwd_t": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "p5_op_ce_bwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, i32, vp, vp]),
+    "p5_op_masked_mean": (i32, [vp, vp, vp, i32, i32, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
     "p5_op_tr_probe": (i32, [vp, vp, vp]),

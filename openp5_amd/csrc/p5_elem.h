@@ -438,11 +438,13 @@ __global__ __launch_bounds__(256) void p5_ce_fwd_kernel(float* __restrict__ nll,
   for (int j = tid; j < V4; j += 256) {
     const f32x4 v = *(const f32x4*)(lr + 4 * j);
     const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+    if (mx == P5_NEG_INF) continue;      // four masked logits add nothing; while m is still -inf, exp(-inf - m) would be NaN and stay in s
     if (mx > m) { s *= p5_exp<T>(m - mx); m = mx; }
     s += p5_exp<T>(v[0] - m) + p5_exp<T>(v[1] - m) + p5_exp<T>(v[2] - m) + p5_exp<T>(v[3] - m);
   }
   for (int j = (V4 << 2) + tid; j < V; j += 256) {
     const float v = lr[j];
+    if (v == P5_NEG_INF) continue;
     if (v > m) { s *= p5_exp<T>(m - v); m = v; }
     s += p5_exp<T>(v - m);
   }

@@ -3084,6 +3084,113 @@ int p5_op_ce_fwd(float* nll, float* lse, const float* logits, const int64_t* lab
   P5_LAUNCH((p5_ce_fwd_kernel<float>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, V, ldl);
   return P5_KCHECK();
 }
+// ---- row kernels of p5_elem.h / p5_embed.h with everything their launchers take (tests/elem_matrix.py); launch geometry = the engine's ----
+int p5_op_rmsnorm_fwd_drop(int dtype, void* y, float* rstd, const void* x, const float* w, int rows, int d, float eps, const uint32_t* rng_state,
+                           uint32_t site, float drop_p, void* stream) {
+  P5_REQUIRE(rows >= 1, "rmsnorm: rows");
+  const P5Drop dp = op_drop(rng_state, site, drop_p);
+  return dtype == 1 ? rmsnorm_fwd<bf16>((hipStream_t)stream, y, rstd, x, w, rows, d, eps, dp) : rmsnorm_fwd<float>((hipStream_t)stream, y, rstd, x, w, rows, d, eps, dp);
+}
+int p5_op_rmsnorm_bwd_full(int dtype, float* dres_out, void* dy_next, float* dw, const void* dy, const void* x, const float* w, const float* rstd,
+                           const float* dres_in, int rows, int d, float* dw_partial, const uint32_t* rng_state, uint32_t site_in, float drop_in_p,
+                           uint32_t site_next, float drop_next_p, const float* ssq_part, void* n_out, float eps, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(rows >= 1 && (rstd || ssq_part), "rmsnorm_bwd: rows; rstd or ssq_part");
+  P5_REQUIRE(!ssq_part || d % 64 == 0, "rmsnorm_bwd: ssq_part holds one partial sum per 64 columns");
+  const P5Drop din = op_drop(rng_state, site_in, drop_in_p), dnx = op_drop(rng_state, site_next, drop_next_p);
+  int nblk = 0;
+  P5_TRY(dtype == 1 ? rmsnorm_bwd<bf16>(s, dres_out, dy_next, dw, dy, x, w, rstd, dres_in, rows, d, din, dnx, dw_partial, &nblk, ssq_part, n_out, eps)
+                    : rmsnorm_bwd<float>(s, dres_out, dy_next, dw, dy, x, w, rstd, dres_in, rows, d, din, dnx, dw_partial, &nblk, ssq_part, n_out, eps));
+  if (dw_partial) {
+    P5_LAUNCH(p5_reduce_rows_kernel, dim3((d + 15) / 16), dim3(256), 0, s, dw, (const float*)dw_partial, nblk, d);
+    P5_TRY(P5_KCHECK());
+  }
+  return 0;
+}
+int p5_op_embed_fwd(int dtype, void* out, const void* E, const void* WW, const int64_t* ids, const int64_t* ww, int rows, int d,
+                    const uint32_t* rng_state, uint32_t site, float drop_p, float* ssq_part, void* stream) {
+  P5_REQUIRE(rows >= 1 && d % 64 == 0 && d <= 1024, "embed_fwd: d_model must be a multiple of 64, <= 1024");
+  P5_REQUIRE(out && E && ids && (!WW || ww), "embed_fwd: null argument");
+  const P5Drop dp = op_drop(rng_state, site, drop_p);
+  if (dtype == 1) P5_LAUNCH((p5_embed_fwd_kernel<bf16>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16*)out, (const bf16*)E, (const bf16*)WW, ids, ww, rows, d, dp, ssq_part);
+  else P5_LAUNCH((p5_embed_fwd_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (float*)out, (const float*)E, (const float*)WW, ids, ww, rows, d, dp, ssq_part);
+  return P5_KCHECK();
+}
+int p5_op_embed_bwd(int dtype, int mode, int nsets, int d, const P5EmbedBwdSet* sets, const uint32_t* rng_state, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(sets && nsets >= 1 && nsets <= P5_EMB_MAXSETS && d % 64 == 0 && d >= 64 && d <= 1024, "embed_bwd: 1..2 sets, d_model a multiple of 64, <= 1024");
+  P5_REQUIRE(mode == 0 || mode == 1, "embed_bwd: mode 0 (atomic scatter) or 1 (fixed-order chain)");
+  int n[P5_EMB_MAXSETS] = {};
+  for (int k = 0; k < nsets; ++k) {
+    const P5EmbedBwdSet& q = sets[k];
+    n[k] = q.n0 + q.n1;
+    P5_REQUIRE(q.n0 >= 0 && q.n1 >= 0 && n[k] >= 1 && q.table && (q.n0 == 0 || (q.key0 && q.dres0)) && (q.n1 == 0 || (q.key1 && q.dres1)), "embed_bwd: keys / rows / table");
+    P5_REQUIRE(n[k] <= n[0], "embed_bwd: the first set sizes the grids, a later one may not be longer");
+    P5_REQUIRE(mode == 0 || (q.idx && q.csort && q.part), "embed_bwd: the fixed-order chain needs idx / csort / part");
+  }
+  if (mode == 0) {      // the scatter of p5_set_option("embed_det", 0): one launch per key array
+    for (int k = 0; k < nsets; ++k) {
+      const P5EmbedBwdSet& q = sets[k];
+      for (int h = 0; h < 2; ++h) {
+        const int rows = h ? q.n1 : q.n0;
+        if (rows == 0) continue;
+        const P5Drop dp = h ? op_drop(rng_state, q.site1, q.drop_p1) : op_drop(rng_state, q.site0, q.drop_p0);
+        const float* dres = h ? q.dres1 : q.dres0;
+        const int64_t* key = h ? q.key1 : q.key0;
+        if (dtype == 1) P5_LAUNCH((p5_embed_bwd_kernel<bf16>), dim3((rows + 3) / 4), dim3(256), 0, s, q.table, (float*)nullptr, dres, key, (const int64_t*)nullptr, rows, d, dp);
+        else P5_LAUNCH((p5_embed_bwd_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, s, q.table, (float*)nullptr, dres, key, (const int64_t*)nullptr, rows, d, dp);
+        P5_TRY(P5_KCHECK());
+      }
+    }
+    return 0;
+  }
+  P5EmbArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  ea.nsets = nsets; ea.d = d;
+  for (int k = 0; k < nsets; ++k) {
+    const P5EmbedBwdSet& q = sets[k];
+    P5EmbSet& o = ea.s[k];
+    o.key0 = q.key0; o.key1 = q.key1; o.dres0 = q.dres0; o.dres1 = q.dres1; o.n0 = q.n0; o.n1 = q.n1;
+    o.drop0 = op_drop(rng_state, q.site0, q.drop_p0); o.drop1 = op_drop(rng_state, q.site1, q.drop_p1);
+    o.table = q.table;
+    o.perm = q.idx; o.skey = o.perm + n[k]; o.sstart = o.skey + n[k]; o.slen = o.sstart + n[k];
+    o.part = q.part; o.csort = q.csort;
+  }
+  P5_LAUNCH(p5_embed_sortchunk_kernel, dim3((n[0] + P5_EMB_CHUNK - 1) / P5_EMB_CHUNK, nsets), dim3(256), 0, s, ea);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_embed_rank_kernel, dim3((n[0] + 63) / 64, nsets), dim3(256), 0, s, ea);
+  P5_TRY(P5_KCHECK());
+  const int nblk = (n[0] + P5_EMB_SEG - 1) / P5_EMB_SEG;
+  P5_LAUNCH(p5_embed_seg_kernel, dim3(nblk, nsets), dim3(256), 0, s, ea);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_embed_fix_kernel, dim3(nblk, nsets), dim3(256), 0, s, ea);
+  return P5_KCHECK();
+}
+int p5_op_ce_fwd_t(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, int rows, int V, int ldl, void* stream) {
+  P5_REQUIRE(rows >= 1 && V >= 1 && ldl >= V && ldl % 4 == 0, "ce_fwd: ldl >= V, a multiple of 4");
+  if (dtype == 1) P5_LAUNCH((p5_ce_fwd_kernel<bf16>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, V, ldl);
+  else P5_LAUNCH((p5_ce_fwd_kernel<float>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, V, ldl);
+  return P5_KCHECK();
+}
+int p5_op_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const float* dnll, int rows, int V, int ldl,
+                 int ldd, const int64_t* out_attn, int T, float gscale, int grid_y, float* g_out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(rows >= 1 && V >= 1 && ldd >= V && ldl >= ldd && ldl % 8 == 0 && ldd % 8 == 0, "ce_bwd: V <= ldd <= ldl, both multiples of 8");
+  P5_REQUIRE(dnll || (out_attn && T >= 1 && rows % T == 0), "ce_bwd: dnll, or out_attn [rows / T, T]");
+  P5_REQUIRE(grid_y >= 1 && grid_y <= 8, "ce_bwd: 1..8 column slices");
+  if (g_out) {
+    P5_LAUNCH(p5_ce_gscale_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, g_out, labels, dnll, out_attn, T, gscale, rows);
+    P5_TRY(P5_KCHECK());
+  }
+  if (dtype == 1) P5_LAUNCH((p5_ce_bwd_kernel<bf16>), dim3(rows, grid_y), dim3(256), 0, s, (bf16*)dlogits, logits, lse, labels, dnll, V, ldl, ldd, out_attn, T, gscale);
+  else P5_LAUNCH((p5_ce_bwd_kernel<float>), dim3(rows, grid_y), dim3(256), 0, s, (float*)dlogits, logits, lse, labels, dnll, V, ldl, ldd, out_attn, T, gscale);
+  return P5_KCHECK();
+}
+int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream) {
+  P5_REQUIRE(loss && nll && out_attn && B >= 1 && T >= 1, "masked_mean: arguments");
+  P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss, nll, out_attn, B, T);
+  return P5_KCHECK();
+}
 int p5_op_skinny_gemm(int dtype, int amode, const void* A, int lda, const float* ln, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                       int epi, float alpha, float eps, void* stream) {
   return dtype == 1 ? skinny<bf16>((hipStream_t)stream, amode, A, lda, ln, (const bf16*)W, ldw, C, ldc, M, N, K, epi, alpha, eps, nullptr)

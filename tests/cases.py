@@ -2451,3 +2451,525 @@ def dataset_gate(be, tmp, ocfg_of, K=10, min_users=200, max_fallback_frac=0.05, 
     assert len(unexplained) == 0, unexplained
     assert c16["same_gold_rank"] >= 0.95 * n_users and c16["same_topk_set"][5] >= 0.95 * n_users, c16
     return {"verify_stats": vstats, "cver": cver, "c16": c16, "set_diff": set_diff, "depth": depth, "levels": levels}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Row kernels (csrc/p5_elem.h) and the embedding gradient (csrc/p5_embed.h) against float64: the rows of tests/elem_matrix.py.
+# Every case builds its inputs in the kernel's storage types, computes the operation in float64 from those stored values and holds each
+# output element to  r |ref| + s S  (S: the same expression over absolute values; r, s: see the head of tests/elem_matrix.py), plus what is
+# exact: dropped elements, ignored labels, padding columns, sentinels past the logical extent, untouched table rows, the bf16 shadow.
+def _elem_seed():
+    return (GEMM_STATE[0] + GEMM_STATE[1] * 0x632BE5AB) & 0xFFFFFFFF
+
+
+def _elem_r(dtype):
+    from tests.elem_matrix import ELEM_R32
+    return GEMM_R[True] if dtype == 1 else ELEM_R32
+
+
+def _guarded(t, extra_rows=1):
+    """`t` ([n] or [rows, cols], bf16 / fp32) followed by `extra_rows` rows (or elements) of NaN sentinel"""
+    shape = (t.shape[0] + extra_rows,) + tuple(t.shape[1:])
+    out = _sentinel(shape, t.dtype)
+    out[:t.shape[0]] = t
+    return out
+
+
+def _guard_intact(tag, full, n):
+    it, v = GEMM_SENT[full.dtype]
+    assert bool((full[n:].contiguous().view(it) == v).all()), f"{tag}: written past its logical extent"
+
+
+def _elem_check(tag, got, ref, bound, zero=None):
+    """every element of `got` within `bound` of the float64 `ref` (finite everywhere: nothing is left out); `zero`: exact zeros.
+    Returns the worst err / bound."""
+    assert bool(torch.isfinite(ref).all()) and bool(torch.isfinite(bound).all()), f"{tag}: the float64 reference is not finite everywhere"
+    got = got.double()
+    assert got.shape == ref.shape, (tag, got.shape, ref.shape)
+    assert bool(torch.isfinite(got).all()), f"{tag}: {int((~torch.isfinite(got)).sum())} non-finite outputs"
+    err = (got - ref).abs()
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp(min=1e-300))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    if worst > 1.0:
+        i = int(ratio.argmax())
+        raise AssertionError(f"{tag}: worst at flat index {i}: got {float(got.flatten()[i]):.9e} ref {float(ref.flatten()[i]):.9e} bound "
+                             f"{float(bound.flatten()[i]):.3e} ({int((ratio > 1).sum())} of {ratio.numel()} elements out of bound, worst {worst:.3g} x)")
+    if zero is not None:
+        assert bool((got[zero] == 0).all()), f"{tag}: {int((got[zero] != 0).sum())} elements that must be exact zeros are not"
+    return worst
+
+
+def _keep(site, numel, p, shape):
+    if p <= 0:
+        return None
+    return O.dropout_keep_mask(_elem_seed(), site, numel, p).view(shape)
+
+
+def _dropped(x, keep, p):
+    return x if keep is None else torch.where(keep, x / (1.0 - p), torch.zeros_like(x))
+
+
+ELEM_OPT_DEFAULTS = dict(norm_bwd_blocks=1024)
+
+
+def rmsnorm_ref_case(be, row, seed=0):
+    """T5LayerNorm forward and backward (p5_rmsnorm_fwd_kernel, p5_rmsnorm_bwd_kernel<T, NCH>, p5_reduce_rows_kernel), one row of
+    elem_matrix.RMSNORM.  The backward is given rstd (or the d / 64 partial sums of squares) as stored values and runs with dw by atomics and
+    by per-workgroup partials; dw is pre-filled (+=).  Options set by the row are restored."""
+    for k, v in row["opts"].items():
+        be.check(be.lib.p5_set_option(k.encode(), v), f"p5_set_option {k}")
+    try:
+        return _rmsnorm_ref_run(be, row, seed)
+    finally:
+        for k in row["opts"]:
+            be.lib.p5_set_option(k.encode(), ELEM_OPT_DEFAULTS[k])
+
+
+def _rmsnorm_ref_run(be, row, seed):
+    from tests.elem_matrix import ELEM_R32
+    lib, st = be.lib, be.stream_ptr()
+    dtype, rows, d, eps = row["dtype"], row["rows"], row["d"], 1e-6
+    tt, r, tag = TT[dtype], _elem_r(dtype), row["id"]
+    g = torch.Generator().manual_seed(seed + 17)
+    x = torch.randn(rows, d, generator=g)
+    if row["edge"]:
+        x[0] = 0
+        x[1] *= 1e4
+        x[2] *= 1e-4
+        x[3] = 0
+        x[3, d // 2] = 1.5
+    x = x.to(tt)
+    w = (1.0 + 0.1 * torch.randn(d, generator=g)).float()
+    dy = torch.randn(rows, d, generator=g).to(tt)
+    dres = torch.randn(rows, d, generator=g).float() if row["dres"] else None
+    dw0 = torch.randn(d, generator=g).float()
+    rng = dev(be, torch.tensor(GEMM_STATE, dtype=torch.int32))
+    S_Y, S_IN, S_NX = 21, 22, 23
+    xd, wd, dyd = dev(be, x), dev(be, w), dev(be, dy)
+    dresd = dev(be, dres) if dres is not None else None
+    yd = dev(be, _sentinel((rows + 1, d), tt))
+    rd = dev(be, _sentinel((rows + 1,), torch.float32))
+    plain = not (row["drop_y"] or row["drop_in"] or row["drop_next"] or row["ssq"])
+
+    def fwd():
+        if plain:
+            return lib.p5_op_rmsnorm_fwd(dtype, P(yd), P(rd), P(xd), P(wd), rows, d, eps, st)
+        return lib.p5_op_rmsnorm_fwd_drop(dtype, P(yd), P(rd), P(xd), P(wd), rows, d, eps, P(rng), S_Y, row["drop_y"], st)
+
+    outs = dict(dres_out=dev(be, _sentinel((rows + 1, d), torch.float32)), dy_next=dev(be, _sentinel((rows + 1, d), tt)),
+                n_out=dev(be, _sentinel((rows + 1, d), tt)))
+    dwd = dev(be, _guarded(dw0))
+    rstd_in = ssq = None
+
+    def bwd(partial):
+        scratch = dev(be, torch.full((1024 * d,), float("nan"))) if partial else None      # (a partial row its workgroup did not write would show)
+        if plain:
+            return lib.p5_op_rmsnorm_bwd(dtype, P(outs["dres_out"]), P(outs["dy_next"]), P(dwd), P(dyd), P(xd), P(wd), P(rstd_in), P(dresd), rows, d,
+                                         P(scratch), st)
+        return lib.p5_op_rmsnorm_bwd_full(dtype, P(outs["dres_out"]), P(outs["dy_next"]), P(dwd), P(dyd), P(xd), P(wd), P(rstd_in), P(dresd), rows, d,
+                                          P(scratch), P(rng), S_IN, row["drop_in"], S_NX, row["drop_next"], P(ssq), P(outs["n_out"]) if row["ssq"] else None,
+                                          eps, st)
+
+    if row["error"]:      # the launcher refuses (P5_REQUIRE): an error code, nothing launched, nothing written
+        rstd_in = dev(be, torch.ones(rows))
+        assert fwd() != 0 and b"rmsnorm" in lib.p5_last_error(), f"{tag}: forward accepted d = {d}"
+        plain = False
+        assert bwd(False) != 0 and b"rmsnorm" in lib.p5_last_error(), f"{tag}: backward accepted d = {d}"
+        sync(be)
+        for name, t in (("y", yd), ("rstd", rd), ("dw", dwd)) + tuple(outs.items()):
+            _guard_intact(f"{tag} {name}", t.cpu(), d if name == "dw" else 0)
+        assert torch.equal(dwd.cpu()[:d], dw0)
+        return 0.0
+
+    # ---- forward ----
+    x64, w64 = x.double(), w.double()
+    rstd64 = 1.0 / torch.sqrt((x64 * x64).mean(1) + eps)
+    keep_y = _keep(S_Y, rows * d, row["drop_y"], (rows, d))
+    yref = _dropped(w64 * (x64 * rstd64[:, None]), keep_y, row["drop_y"])
+    be.check(fwd(), f"rmsnorm_fwd {tag}")
+    sync(be)
+    yh, rh = yd.cpu(), rd.cpu()
+    _guard_intact(f"{tag} y", yh, rows)
+    _guard_intact(f"{tag} rstd", rh, rows)
+    worst = _elem_check(f"{tag} rstd", rh[:rows], rstd64, (ELEM_R32 + GEMM_S) * rstd64)
+    # (x * rstd) is rounded to the activation type before * w, and the result once more: 2 r
+    worst = max(worst, _elem_check(f"{tag} y", yh[:rows], yref, (2 * r + GEMM_S) * yref.abs(), zero=None if keep_y is None else ~keep_y))
+
+    # ---- backward ----
+    if row["ssq"]:
+        part = torch.stack([(x64[:, j:j + 64] ** 2).sum(1) for j in range(0, d, 64)], 1).float()
+        ssq = dev(be, part)
+        rs = 1.0 / torch.sqrt(part.double().sum(1) / d + eps)
+    else:
+        rstd_in = dev(be, rstd64.float())
+        rs = rstd64.float().double()
+    keep_in = _keep(S_IN, rows * d, row["drop_in"], (rows, d))
+    keep_nx = _keep(S_NX, rows * d, row["drop_next"], (rows, d))
+    dyk = _dropped(dy.double(), keep_in, row["drop_in"])
+    xh = x64 * rs[:, None]
+    dwref, S_dw = dw0.double() + (dyk * xh).sum(0), dw0.double().abs() + (dyk * xh).abs().sum(0)
+    gw = dyk * w64
+    dot, S_dot = (gw * xh).mean(1, keepdim=True), (gw * xh).abs().mean(1, keepdim=True)
+    rout, S_r = rs[:, None] * (gw - xh * dot), rs[:, None] * (gw.abs() + xh.abs() * S_dot)
+    if dres is not None:
+        rout, S_r = rout + dres.double(), S_r + dres.double().abs()
+    nx, S_nx = _dropped(rout, keep_nx, row["drop_next"]), _dropped(S_r, keep_nx, row["drop_next"])
+    nref = w64 * xh
+    for partial in (False, True):
+        md = f"{tag} ({'partials' if partial else 'atomics'})"
+        for t in outs.values():
+            t.copy_(_sentinel(tuple(t.shape), t.dtype))
+        dwd.copy_(_guarded(dw0))
+        be.check(bwd(partial), f"rmsnorm_bwd {md}")
+        sync(be)
+        o = {k: v.cpu() for k, v in outs.items()}
+        for k, v in o.items():
+            _guard_intact(f"{md} {k}", v, rows if (k != "n_out" or row["ssq"]) else 0)
+        _guard_intact(f"{md} dw", dwd.cpu(), d)
+        worst = max(worst, _elem_check(f"{md} dres_out", o["dres_out"][:rows], rout, ELEM_R32 * rout.abs() + GEMM_S * S_r))
+        worst = max(worst, _elem_check(f"{md} dy_next", o["dy_next"][:rows], nx, r * nx.abs() + GEMM_S * S_nx, zero=None if keep_nx is None else ~keep_nx))
+        worst = max(worst, _elem_check(f"{md} dw", dwd.cpu()[:d], dwref, ELEM_R32 * dwref.abs() + GEMM_S * S_dw))
+        if row["ssq"]:
+            worst = max(worst, _elem_check(f"{md} n_out", o["n_out"][:rows], nref, (2 * r + GEMM_S) * nref.abs()))
+    return worst
+
+
+CE_KINDS = ("normal", "shifted", "constant", "dominant", "neginf", "neginf-head")
+
+
+def ce_ref_case(be, row, seed=0):
+    """Token cross-entropy on materialised logits (p5_ce_fwd_kernel<float> / <bf16>, p5_ce_bwd_kernel, p5_ce_gscale_kernel), one row of
+    elem_matrix.CE: 18 logit rows (six kinds x labels -100 / first finite column / V - 1) with NaN padding columns.  No label logit is -inf,
+    so the float64 reference is finite for every row (asserted)."""
+    from tests.elem_matrix import ELEM_R32, ELEM_TINY
+    lib, st = be.lib, be.stream_ptr()
+    V, tag = row["V"], row["id"]
+    ldd = (V + 63) // 64 * 64
+    ldl = ldd + row["pad"]
+    tau = ATTN_TAU[0]
+    g = torch.Generator().manual_seed(seed + 29)
+    R = 3 * len(CE_KINDS)
+    L = torch.full((R, ldl), float("nan"))
+    labels = torch.zeros(R, dtype=torch.int64)
+    ninf = float("-inf")
+    for k, kind in enumerate(CE_KINDS):
+        for j in range(3):
+            i = 3 * k + j
+            v = torch.randn(V, generator=g)
+            first = 0
+            if kind == "shifted":
+                v = v + 1e4
+            elif kind == "constant":
+                v = torch.full((V,), 2.5)
+            elif kind == "dominant":
+                v[(7 * i) % V] += 200.0
+            elif kind == "neginf" and V >= 3:
+                m = torch.rand(V, generator=g) < 0.3
+                m[1] = True
+                m[0] = m[V - 1] = False
+                v[m] = ninf
+            elif kind == "neginf-head":
+                first = min(1024, V - 1)
+                v[:first] = ninf
+            L[i, :V] = v
+            labels[i] = (-100, first, V - 1)[j]
+    x64 = L[:, :V].double()
+    mx = x64.max(1).values
+    lsum = torch.log(torch.exp(x64 - mx[:, None]).sum(1))
+    lse = mx + lsum
+    ign = labels == -100
+    xl = x64.gather(1, labels.clamp(min=0)[:, None])[:, 0]
+    nll = torch.where(ign, torch.zeros_like(lse), lse - xl)
+    S_lse = mx.abs() + lsum.abs()
+    S_nll = torch.where(ign, torch.zeros_like(lse), S_lse + xl.abs())
+    Ld, labd = dev(be, L), dev(be, labels)
+    worst = 0.0
+    for dtype in (0, 1):
+        nd, ld_ = dev(be, _sentinel((R + 1,), torch.float32)), dev(be, _sentinel((R + 1,), torch.float32))
+        if dtype == 0:
+            be.check(lib.p5_op_ce_fwd(P(nd), P(ld_), P(Ld), P(labd), R, V, ldl, st), f"ce_fwd {tag}")
+        else:
+            be.check(lib.p5_op_ce_fwd_t(dtype, P(nd), P(ld_), P(Ld), P(labd), R, V, ldl, st), f"ce_fwd_t {tag}")
+        sync(be)
+        nh, lh = nd.cpu(), ld_.cpu()
+        md = f"{tag} fwd {'bf16 mode' if dtype else 'fp32'}"
+        _guard_intact(f"{md} nll", nh, R)
+        _guard_intact(f"{md} lse", lh, R)
+        worst = max(worst, _elem_check(f"{md} lse", lh[:R], lse, ELEM_R32 * lse.abs() + tau * S_lse))
+        worst = max(worst, _elem_check(f"{md} nll", nh[:R], nll, ELEM_R32 * nll.abs() + tau * S_nll, zero=ign))
+
+    # ---- backward: lse as stored; g from dnll, or from the mask (rows = B x T) ----
+    lse_in = lse.float()
+    T = 3
+    B = R // T
+    attn = torch.tensor([0, 1, 1, 2, -1], dtype=torch.int64)[torch.randint(0, 5, (B, T), generator=g)]
+    attn[2] = 0
+    attn[0, 0] = 1
+    gscale = float(torch.tensor(1.0 / B, dtype=torch.float32))
+    dnll = torch.randn(R, generator=g).float()
+    cnt = (attn != 0).sum(1).double().clamp(min=1.0)
+    g_mask = torch.where(attn != 0, gscale / cnt[:, None].expand(B, T), torch.zeros(B, T, dtype=torch.float64)).reshape(R)
+    p = torch.exp(x64 - lse_in.double()[:, None])
+    onehot = torch.zeros_like(p)
+    onehot[~ign, labels[~ign]] = 1.0
+    lsed, attnd, dnlld = dev(be, lse_in), dev(be, attn), dev(be, dnll)
+    for dtype in (0, 1):
+        tt, r = TT[dtype], _elem_r(dtype)
+        for seeding in ("dnll", "mask"):
+            gref = torch.where(ign, torch.zeros(R, dtype=torch.float64), dnll.double() if seeding == "dnll" else g_mask)
+            ref = (p - onehot) * gref[:, None]
+            bound = r * ref.abs() + (tau * (p + onehot) + ELEM_TINY) * gref.abs()[:, None]
+            for gy in (1, 4, 8):
+                dl = dev(be, _sentinel((R + 1, ldd), tt))
+                go = dev(be, _sentinel((R + 1,), torch.float32))
+                be.check(lib.p5_op_ce_bwd(dtype, P(dl), P(Ld), P(lsed), P(labd), P(dnlld) if seeding == "dnll" else None, R, V, ldl, ldd, P(attnd), T,
+                                          gscale, gy, P(go), st), f"ce_bwd {tag}")
+                sync(be)
+                dh, gh = dl.cpu(), go.cpu()
+                md = f"{tag} bwd {'bf16' if dtype else 'fp32'} g from {seeding} gridDim.y {gy}"
+                _guard_intact(f"{md} dlogits", dh, R)
+                _guard_intact(f"{md} g", gh, R)
+                assert bool((dh[:R, V:].float() == 0).all()), f"{md}: padding columns [V, ldd) are not zero"
+                assert bool((dh[:R][ign].float() == 0).all()), f"{md}: rows with label -100 are not all zero"
+                # (one fp32 division, up to 2.5 ulp where the compiler does not emit the correctly rounded sequence: 4 ELEM_R32)
+                worst = max(worst, _elem_check(f"{md} g", gh[:R], gref, 4 * ELEM_R32 * gref.abs(), zero=ign))
+                worst = max(worst, _elem_check(f"{md} dlogits", dh[:R, :V], ref, bound))
+    return worst
+
+
+def masked_mean_ref_case(be, row, seed=0):
+    """The runner's loss (p5_masked_mean_kernel): mean over batch items of the masked mean of their tokens' NLL; items with an empty mask,
+    mask values other than 0 / 1."""
+    from tests.elem_matrix import ELEM_R32
+    B, T, tag = row["B"], row["T"], row["id"]
+    g = torch.Generator().manual_seed(seed + 31)
+    nll = (torch.randn(B, T, generator=g) * 3.0).float()
+    attn = torch.tensor([0, 1, 1, 2, -3], dtype=torch.int64)[torch.randint(0, 5, (B, T), generator=g)]
+    attn[B // 2] = 0
+    if B > 1:
+        attn[0] = 1
+    m = (attn != 0).double()
+    cnt = m.sum(1).clamp(min=1.0)
+    ref = ((nll.double() * m).sum(1) / cnt).mean().reshape(1)
+    S = ((nll.double().abs() * m).sum(1) / cnt).mean().reshape(1)
+    out = dev(be, _sentinel((2,), torch.float32))
+    nd, ad = dev(be, nll), dev(be, attn)
+    be.check(be.lib.p5_op_masked_mean(P(out), P(nd), P(ad), B, T, be.stream_ptr()), f"masked_mean {tag}")
+    sync(be)
+    oh = out.cpu()
+    _guard_intact(tag, oh, 1)
+    return _elem_check(tag, oh[:1], ref, ELEM_R32 * ref.abs() + GEMM_S * S)
+
+
+def embed_fwd_ref_case(be, row, seed=0):
+    """x = dropout(E[ids] (+ WW[ww])) in the activation type (p5_embed_fwd_kernel) and the rows' sums of squares per 64 columns; ids reach row 0
+    and the last row of the table; rows past `rows` keep a sentinel."""
+    from tests.elem_matrix import ELEM_R32
+    dtype, rows, d, tag = row["dtype"], row["rows"], row["d"], row["id"]
+    tt, r, p = TT[dtype], _elem_r(dtype), row["drop"]
+    g = torch.Generator().manual_seed(seed + 37)
+    Vt, Wt, SITE = 50, 20, 31
+    E, WW = torch.randn(Vt, d, generator=g).to(tt), torch.randn(Wt, d, generator=g).to(tt)
+    ids, ww = torch.randint(0, Vt, (rows,), generator=g), torch.randint(0, Wt, (rows,), generator=g)
+    ids[0], ids[-1] = 0, Vt - 1
+    ww[0], ww[-1] = Wt - 1, 0
+    val = E.double()[ids] + (WW.double()[ww] if row["ww"] else 0.0)
+    S = E.double().abs()[ids] + (WW.double().abs()[ww] if row["ww"] else 0.0)
+    keep = _keep(SITE, rows * d, p, (rows, d))
+    ref, S = _dropped(val, keep, p), _dropped(S, keep, p)
+    out = dev(be, _sentinel((rows + 2, d), tt))
+    ssq = dev(be, _sentinel((rows + 1, d // 64), torch.float32)) if row["ssq"] else None
+    rng = dev(be, torch.tensor(GEMM_STATE, dtype=torch.int32))
+    Ed, Wd, idd, wwd = dev(be, E), dev(be, WW), dev(be, ids), dev(be, ww)
+    be.check(be.lib.p5_op_embed_fwd(dtype, P(out), P(Ed), P(Wd) if row["ww"] else None, P(idd), P(wwd) if row["ww"] else None, rows, d, P(rng), SITE, p,
+                                    P(ssq), be.stream_ptr()), f"embed_fwd {tag}")
+    sync(be)
+    oh = out.cpu()
+    _guard_intact(tag, oh, rows)
+    # one rounding to the stored type; before it five fp32 roundings (p, 1 - p, its reciprocal, the add, the multiply)
+    worst = _elem_check(tag, oh[:rows], ref, r * ref.abs() + 5 * ELEM_R32 * S, zero=None if keep is None else ~keep)
+    if ssq is not None:
+        sh = ssq.cpu()
+        _guard_intact(f"{tag} ssq", sh, rows)
+        want = torch.stack([(oh[:rows, j:j + 64].double() ** 2).sum(1) for j in range(0, d, 64)], 1)
+        worst = max(worst, _elem_check(f"{tag} ssq_part", sh[:rows], want, (ELEM_R32 + GEMM_S) * want))
+    return worst
+
+
+def _embed_keys(pattern, n, g):
+    """keys [n] int64 and the number of table rows for one pattern of elem_matrix.EMBED"""
+    if pattern == "equal":
+        return torch.full((n,), 7, dtype=torch.int64), 40
+    if pattern == "distinct":
+        return torch.randperm(n + 9, generator=g)[:n].clone(), n + 9
+    if pattern == "pad70":
+        Vt = max(50, n // 8)
+        k = torch.randint(0, Vt, (n,), generator=g)
+        k[torch.rand(n, generator=g) < 0.7] = 0
+        return k, Vt
+    assert pattern == "blocks"
+    counts, pos = [], 0
+
+    def seg(c):
+        nonlocal pos
+        counts.append(c)
+        pos += c
+
+    def fill_to_last_of_block():
+        while pos % 32 != 31:
+            seg(1)
+    seg(min(32, n))                                   # ends exactly on a block boundary
+    for blocks in (4, 5, 9):                          # starts on the last position of a block, ends on the first of the blocks-th
+        c = 1 + 32 * (blocks - 2) + 1
+        if pos + 31 + c > n:
+            break
+        fill_to_last_of_block()
+        seg(c)
+    while pos < n - 3:
+        seg(1)
+    if pos < n:
+        seg(n - pos)                                  # the largest table row closes the array (a segment of up to 3)
+    keys = torch.cat([torch.full((c,), i + 2, dtype=torch.int64) for i, c in enumerate(counts)])
+    assert keys.numel() == n
+    return keys[torch.randperm(n, generator=g)], len(counts) + 2
+
+
+def embed_ref_case(be, row, seed=0, dump=None):
+    """Gradient of the embedding lookups (p5_embed.h: sort chunks, rank, segmented sum, fix-up; p5_embed_bwd_kernel), one row of
+    elem_matrix.EMBED.  The fixed-order chain must leave perm / skey / sstart / slen equal to a stable argsort of the concatenated keys, give
+    the same bits on a second run (over scratch that still holds the first run's pieces; idx starts as zeros, so that a position a wrong
+    rank leaves unwritten still names a row and a key inside the arrays), and stay within the bound of float64, as must the
+    atomic scatter; table rows no key refers to keep their bits.  Returns (worst err / bound, sha256 of the chain's table gradients); `dump`
+    (a dict) receives the sets' inputs as numpy arrays, for tests/emu/embed_chain_digest.py."""
+    import hashlib
+    import numpy as np
+    from openp5_amd._abi import P5EmbedBwdSet
+    from tests.elem_matrix import ELEM_R32
+    d, tag = row["d"], row["id"]
+    g = torch.Generator().manual_seed(seed + 41)
+    rng = dev(be, torch.tensor(GEMM_STATE, dtype=torch.int32))
+    sets = []
+    for k, (n, n0, pat, p0, p1) in enumerate(row["sets"]):
+        keys, Vt = _embed_keys(pat, n, g)
+        n1 = n - n0
+        dres = torch.randn(n, d, generator=g).float()
+        table0 = torch.randn(Vt + 1, d, generator=g).float()
+        s0, s1 = 41 + 2 * k, 42 + 2 * k
+        vals = dres.double().clone()
+        for lo, hi, site, p in ((0, n0, s0, p0), (n0, n, s1, p1)):
+            if hi > lo and p > 0:
+                keep = _keep(site, (hi - lo) * d, p, (hi - lo, d))
+                vals[lo:hi] = _dropped(vals[lo:hi], keep, p)
+        ref = table0.double().index_add(0, keys, vals)
+        S = table0.double().abs().index_add(0, keys, vals.abs())
+        kn = keys.numpy()
+        perm = np.argsort(kn, kind="stable").astype(np.int32)
+        skey = kn[perm].astype(np.int32)
+        uniq, start, count = np.unique(skey, return_index=True, return_counts=True)
+        which = np.searchsorted(uniq, skey)
+        want_idx = torch.from_numpy(np.concatenate([perm, skey, start[which].astype(np.int32), count[which].astype(np.int32)]))
+        q = dict(n=n, n0=n0, n1=n1, Vt=Vt, keys=keys, table0=table0, ref=ref, S=S, want_idx=want_idx, used=torch.zeros(Vt + 1, dtype=torch.bool),
+                 key0=dev(be, keys[:n0].contiguous()) if n0 else None, key1=dev(be, keys[n0:].contiguous()) if n1 else None,
+                 dres0=dev(be, dres[:n0].contiguous()) if n0 else None, dres1=dev(be, dres[n0:].contiguous()) if n1 else None,
+                 s0=s0, s1=s1, p0=p0, p1=p1,
+                 idx=dev(be, torch.cat([torch.zeros(4 * n, dtype=torch.int32), torch.full((4,), -7, dtype=torch.int32)])), csort=dev(be, torch.zeros((n + 255) // 256 * 256, dtype=torch.int64)),
+                 part=dev(be, torch.full(((n + 31) // 32 * 2 * d,), float("nan"))))
+        q["used"][keys] = True
+        sets.append(q)
+        if dump is not None:
+            dump.setdefault(row["id"], []).append(dict(keys=kn, dres=dres.numpy(), table0=table0.numpy(), n0=n0, s0=s0, s1=s1, p0=p0, p1=p1))
+
+    def run(mode):
+        arr = (P5EmbedBwdSet * len(sets))()
+        tabs = []
+        for k, q in enumerate(sets):
+            t = dev(be, q["table0"].clone())
+            tabs.append(t)
+            a = arr[k]
+            for f in ("key0", "key1", "dres0", "dres1", "idx", "csort", "part"):
+                setattr(a, f, q[f].data_ptr() if q[f] is not None else None)
+            a.n0, a.n1, a.site0, a.site1, a.drop_p0, a.drop_p1, a.table = q["n0"], q["n1"], q["s0"], q["s1"], q["p0"], q["p1"], t.data_ptr()
+        be.check(be.lib.p5_op_embed_bwd(0, mode, len(sets), d, arr, P(rng), be.stream_ptr()), f"embed_bwd {tag} mode {mode}")
+        sync(be)
+        return [t.cpu() for t in tabs]
+
+    first, second, atomic = run(1), run(1), run(0)
+    worst, h = 0.0, hashlib.sha256()
+    for k, q in enumerate(sets):
+        st = f"{tag} set {k}"
+        idx = q["idx"].cpu()
+        assert bool((idx[4 * q["n"]:] == -7).all()), f"{st}: idx written past 4 n"
+        for j, name in enumerate(("perm", "skey", "sstart", "slen")):
+            a, b = idx[j * q["n"]:(j + 1) * q["n"]], q["want_idx"][j * q["n"]:(j + 1) * q["n"]]
+            assert torch.equal(a, b), f"{st}: {name} differs from the stable argsort at {int((a != b).nonzero()[0])} ({int((a != b).sum())} positions)"
+        assert _same_bits(first[k], second[k]), f"{st}: the fixed-order chain gave different bits on its second run"
+        h.update(first[k].numpy().tobytes())
+        bound = ELEM_R32 * q["ref"].abs() + GEMM_S * q["S"]
+        for name, got in (("chain", first[k]), ("atomic scatter", atomic[k])):
+            assert _same_bits(got[~q["used"]], q["table0"][~q["used"]]), f"{st} {name}: table rows no key refers to were written"
+            worst = max(worst, _elem_check(f"{st} {name}", got, q["ref"], bound))
+    return worst, h.hexdigest()
+
+
+ADAMW_HYPER = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.01, max_norm=1.0)
+
+
+def adamw_ref_case(be, row, seed=0, tol=2e-6):
+    """p5_grad_sumsq + p5_adamw_step (p5_sumsq_kernel, p5_adamw_kernel) over consecutive steps against the same arithmetic in float64
+    (transformers-4.26 AdamW.step after torch's clip_grad_norm_, as tests/golden/make_adamw_426.py writes it): p, m, v within `tol` of each
+    tensor's largest |ref| (adamw_golden_case's bound), the sum of squares within cases.GEMM_S, the bf16 shadow == bf16(p) bit for bit,
+    nothing written past n."""
+    from tests.elem_matrix import ELEM_R32
+    lib, st, h = be.lib, be.stream_ptr(), ADAMW_HYPER
+    n, gs, tag = row["n"], row["grad_scale"], row["id"]
+    g = torch.Generator().manual_seed(seed + 43)
+    G = 8
+    p0 = (torch.randn(n, generator=g) * 0.1).float()
+    pd, md, vd = dev(be, _guarded(p0, G)), dev(be, _guarded(torch.zeros(n), G)), dev(be, _guarded(torch.zeros(n), G))
+    sh = dev(be, _sentinel((n + G,), torch.bfloat16)) if row["shadow"] else None
+    ssd = dev(be, _sentinel((1024 + G,), torch.float32))
+    p, m, v = p0.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+    worst = 0.0
+    for t in row["steps"]:
+        gr = torch.randn(n, generator=g)
+        if row["zero"]:
+            gr = torch.zeros(n)
+        else:
+            gr = (gr * (h["max_norm"] * row["factor"] / (gs * float(gr.double().norm())))).float()
+        g64 = gr.double()
+        gd = dev(be, gr)
+        be.check(lib.p5_grad_sumsq(P(gd), n, P(ssd), st), "p5_grad_sumsq")
+        be.check(lib.p5_adamw_step(P(pd), P(gd), P(md), P(vd), P(sh), n, P(ssd) if row["sumsq"] else None, h["max_norm"], gs, h["lr"], h["beta1"],
+                                   h["beta2"], h["eps"], h["weight_decay"], t, st), "p5_adamw_step")
+        sync(be)
+        ssq = (g64 * g64).sum().reshape(1)
+        ssh = ssd.cpu()
+        _guard_intact(f"{tag} sumsq", ssh, 1024)
+        worst = max(worst, _elem_check(f"{tag} step {t} sum of squares", ssh[:1024].double().sum().reshape(1), ssq, (ELEM_R32 + GEMM_S) * ssq))
+        coef = gs
+        if row["sumsq"]:
+            coef = gs * min(1.0, h["max_norm"] / (math.sqrt(float(ssq)) * gs + 1e-6))
+        gg = g64 * coef
+        m = h["beta1"] * m + (1.0 - h["beta1"]) * gg
+        v = h["beta2"] * v + (1.0 - h["beta2"]) * gg * gg
+        step_size = h["lr"] * math.sqrt(1.0 - h["beta2"] ** t) / (1.0 - h["beta1"] ** t)
+        p = p - step_size * (m / (v.sqrt() + h["eps"]))
+        p = p - h["lr"] * h["weight_decay"] * p
+        ph = pd.cpu()
+        for name, got, ref in (("p", ph, p), ("m", md.cpu(), m), ("v", vd.cpu(), v)):
+            _guard_intact(f"{tag} {name}", got, n)
+            worst = max(worst, _elem_check(f"{tag} step {t} {name}", got[:n], ref, torch.full_like(ref, tol * float(ref.abs().max()))))
+        if sh is not None:
+            shh = sh.cpu()
+            _guard_intact(f"{tag} shadow", shh, n)
+            assert _same_bits(shh[:n], ph[:n].to(torch.bfloat16)), f"{tag} step {t}: the bf16 shadow is not the updated parameter rounded once"
+    return worst
+
+
+def elem_ref_case(be, row, seed=0):
+    """dispatch one row of tests/elem_matrix.py to its family's case; returns the worst err / bound"""
+    fam = row["fam"]
+    if fam == "embed":
+        return embed_ref_case(be, row, seed)[0]
+    return {"rmsnorm": rmsnorm_ref_case, "ce": ce_ref_case, "masked": masked_mean_ref_case, "embed_fwd": embed_fwd_ref_case,
+            "adamw": adamw_ref_case}[fam](be, row, seed)

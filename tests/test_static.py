@@ -79,3 +79,40 @@ def test_every_gemm_launch_site_has_a_route_row():
     assert not missing, f"GEMM launch sites without a row in tests/gemm_matrix.py: {missing}"
     stale = sorted(named - set(sites))
     assert not stale, f"rows of tests/gemm_matrix.py name launch sites that no longer exist: {stale}"
+
+
+def _launch_sites(fn):
+    """first argument of every P5_LAUNCH in a source file, whitespace removed"""
+    src = open(os.path.join(CSRC, fn)).read()
+    sites = []
+    for m in re.finditer(r"P5_LAUNCH\(", src):
+        i, depth = m.end(), 0
+        while depth or src[i] != ",":
+            depth += {"(": 1, ")": -1, "<": 1, ">": -1}.get(src[i], 0)
+            i += 1
+        sites.append("".join(src[m.end():i].split()))
+    return sites
+
+
+def test_every_row_kernel_launch_is_named_in_the_elem_table():
+    """tests/elem_matrix.py names every kernel of p5_elem.h / p5_embed.h that p5_lib.hip launches: with rows checked against float64
+    (cases.*_ref_case) or with the existing test that reaches it (`checked_by`), so a new row kernel cannot arrive without either."""
+    from tests.elem_matrix import KERNELS, ROWS
+    defined = set()
+    for fn in ("p5_elem.h", "p5_embed.h"):
+        defined |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(p5_\w+)\s*\(", open(os.path.join(CSRC, fn)).read()))
+    assert len(defined) >= 23, sorted(defined)
+    launched = set()
+    for site in _launch_sites("p5_lib.hip"):
+        name = re.match(r"\(*(\w+)", site).group(1)
+        if name in defined:
+            launched.add(name)
+    assert len(launched) >= 20, sorted(launched)
+    missing = sorted(launched - set(KERNELS))
+    assert not missing, f"kernels launched by p5_lib.hip without an entry in tests/elem_matrix.py: {missing}"
+    stale = sorted(set(KERNELS) - defined)
+    assert not stale, f"tests/elem_matrix.py names kernels that p5_elem.h / p5_embed.h no longer define: {stale}"
+    fams = {r["fam"] for r in ROWS}
+    for k, v in KERNELS.items():
+        assert ("fam" in v) != ("checked_by" in v), k
+        assert "fam" not in v or v["fam"] in fams, f"{k}: no row of family {v.get('fam')}"
