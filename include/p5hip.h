@@ -235,6 +235,30 @@ int p5_verify_row_capacity(int Kw, int max_len);           /* rows per user the 
 const int* p5_verify_plan_header(const P5Engine* e);     /* device int[4]: max rows per user, draft steps, total rows, overflow */
 int p5_verify_run(P5Engine* e, int rows_per_user, const uint32_t* excluded_nodes, int* out_seq, float* out_score, int* out_len,
                   int* out_missing, void* stream);
+/* ---- exhaustive catalogue ranking: the beam-search score of EVERY item of the trie in one pass (openp5_amd/csrc/p5_rank.h) ----
+ * HF's beam search ranks an item by the sum of its tokens' log-probabilities up to and including </s>, divided by their number.  With one
+ * decoder row per non-leaf trie node behind the decoder start token (the prefix that leads to it), ONE teacher-forced pass yields the
+ * log-probability of every trie edge, an item's score is a sum along its path, and the ranked list is an exact top-N selection: what
+ * p5_generate approaches as num_beams grows (DistributedRunner.py:204-269 widens the beam by the longest history), without a search.
+ *   plan (host arrays on the device, ONE per trie, shared by all users -- openp5_amd/trie.py::CompiledTrie.rank_plan builds it):
+ *     row_tok / row_depth / row_node [rows_per_user]: decoder input token, number of generated tokens, trie node of each prefix; parents
+ *     precede children; row 0 = the decoder start token.  row_anc [rows_per_user][max_depth]: row of the ancestor at depth t < depth.
+ *   item_edges [n_items][path_len]: edge ids (index into child_tok) of each item's path behind the start token, -1 beyond its </s>.
+ *   excluded_items: optional uint32 [B, ceil(n_items / 32)]; bit i of row b set = item i is not ranked for user b (its score is still
+ *     computed).  NULL = nothing excluded.
+ *   out_index int32 / out_score fp32 [B, top_n]: the top_n items by (score desc, item index asc); fewer candidates: index -1, score -1e9.
+ *   out_scores_all: optional fp32 [B, n_items], every item's score.  out_flagged int32 [B]: 1 = a value of the split-product pass left
+ *     the range the two-term fp16 split covers (see verified generation above) -- that user's numbers are NOT to be used; call again for
+ *     the user with exact_products = 1 (exact fp32 MFMAs; openp5_amd/model.py does).  Always 0 on a bf16 engine or with exact_products.
+ * The pass lays its rows out [chunk][user][<= 512] so that each chunk is one cross-attention launch per layer; the tied head and the
+ * scoring run in row chunks whose buffers do not grow with the catalogue.  Limits: top_n <= 4096, L <= 512, max_depth <= the half length of the bucket LUT bound to the engine, a tree-shaped
+ * trie (no appended trie), B x rows_per_user x n_heads < 2^31.  Enqueues everything on `stream` and returns without synchronising. */
+int64_t p5_rank_workspace_bytes(const P5Engine* e, int B, int L, int rows_per_user, int64_t n_edges, int n_items, int top_n);
+int p5_rank_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                  const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                  const int* row_anc, int rows_per_user, int max_depth, const int* item_edges, int n_items, int path_len,
+                  const uint32_t* excluded_items, int top_n, int exact_products, float* out_scores_all, int* out_index, float* out_score,
+                  int* out_flagged, void* ws, int64_t ws_bytes, void* stream);
 /* Device-time brackets of p5_generate for benchmarks: p5_generate_timing(e, 1, NULL, NULL) arms it; after a p5_generate call,
  * p5_generate_timing(e, enable, &encode_ms, &decode_ms) WAITS for that call to finish and returns the time between its start and
  * its first decode step (encoder pass + cross-attention K/V projection + beam state) and the time of the decode loop itself. */

@@ -22,6 +22,7 @@
 #include "p5_decode2.h"
 #include "p5_decode_wide.h"
 #include "p5_verify.h"
+#include "p5_rank.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -1906,19 +1907,21 @@ static int verify_encode_impl(P5Engine* e, const int64_t* input_ids, const int64
   return 0;
 }
 
-// SCORE + REPLAY.  PU: rows per user of this pass (>= the plan's largest row count, a multiple of 16, <= cap): the decoder runs on
-// [B x PU] rows -- self-attention sees them as B*PU single positions with ancestor lists, cross-attention as B sequences of PU queries.
-template <class T>
-static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* out_seq, float* out_score, int* out_len, int* out_missing, hipStream_t s) {
-  VerifyCtx& v = *e->ver;
-  VerifyWs& w = v.w;
+// The teacher-forced decoder pass over a forest of prefixes, shared by verified generation (rows = what a draft kept alive) and exhaustive
+// ranking (rows = the trie, p5_rank.h): rows are laid out [nchunk][B][CQ] -- self-attention sees B * CQ * nchunk single positions with
+// ancestor lists (`tree_attn` launches the kernel that knows them), cross-attention sees, per chunk, B sequences of CQ <= 512 queries
+// against the user's encoder keys.  Ends with the final T5LayerNorm of every row in w.hn.
+struct RowsPassBufs {
+  const int64_t* ids;       // decoder input token of every row
+  void *x, *y, *n, *qkv, *q, *o, *h, *hn;
+  float* lse;               // [B, H, CQ] scratch of the cross-attention kernels
+  const void* kv_all;       // cross-attention K/V of every decoder layer, [B * L, n_dec_layers * 2 * inner]
+};
+template <class T, class TreeAttn>
+static int decoder_rows_pass(P5Engine* e, const RowsPassBufs& w, int B, int CQ, int nchunk, int L, TreeAttn tree_attn, hipStream_t s) {
   const P5Config& c = e->c;
-  SplitScope split(sizeof(T) == 4 ? g_opt_verify_split : 0);
-  const int d = c.d_model, in = e->inner, H = c.n_heads, F = c.d_ff, B = v.B, K = v.K, max_len = v.max_len;
-  const int rows = B * PU, R = B * K, ldkv = c.n_dec_layers * 2 * in;
-  const int Vp = (c.vocab_size + 63) / 64 * 64;
-  P5_LAUNCH(p5_verify_rows_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, w.ids, w.node_flat, w.depth_flat, w.pl, B, PU, c.pad_id);
-  P5_TRY(P5_KCHECK());
+  const int d = c.d_model, in = e->inner, H = c.n_heads, F = c.d_ff;
+  const int rows = B * CQ * nchunk, ldkv = c.n_dec_layers * 2 * in;
   void* x = w.x; void* y = w.y;
   P5_LAUNCH((p5_embed_fwd_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (T*)x, Wc<T>(e, e->off_E), (const T*)nullptr, (const int64_t*)w.ids,
             (const int64_t*)nullptr, rows, d, no_drop(), (float*)nullptr);
@@ -1928,21 +1931,22 @@ static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* o
     // self-attention over the row's own prefix
     P5_TRY(rmsnorm_fwd<T>(s, w.n, nullptr, x, e->P + lo.sa.ln, rows, d, c.eps, no_drop()));
     P5_TRY(linear_fwd<T>(s, w.n, d, Wc<T>(e, lo.sa.q), w.qkv, 3 * in, rows, 3 * in, d));
-    P5_LAUNCH((p5_tree_attn_kernel<T>), dim3((rows * H + 3) / 4), dim3(256), 0, s, (T*)w.o, (const T*)w.qkv, w.pl, (const int*)w.depth_flat,
-              (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, B, PU, H);
-    P5_TRY(P5_KCHECK());
+    P5_TRY(tree_attn((T*)w.o, (const T*)w.qkv));
     P5_TRY(linear_fwd<T>(s, w.o, in, Wc<T>(e, lo.sa.o), y, d, rows, d, in, P5_EPI_RESID_DROP, x, d));
     std::swap(x, y);
-    // cross-attention: the user's PU rows are PU queries against the user's encoder keys (zero position bias, padding mask)
+    // cross-attention: a user's CQ rows of a chunk are CQ queries against the user's encoder keys (zero position bias, padding mask)
     P5_TRY(rmsnorm_fwd<T>(s, w.n, nullptr, x, e->P + lo.ca.ln, rows, d, c.eps, no_drop()));
     P5_TRY(linear_fwd<T>(s, w.n, d, Wc<T>(e, lo.ca.q), w.q, in, rows, in, d));
-    P5AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.Q = w.q; a.K = (const T*)w.kv_all + (size_t)i * 2 * in; a.V = (const T*)w.kv_all + (size_t)i * 2 * in + in; a.O = w.o; a.lse = w.lse;
-    a.rel_table = nullptr; a.bucket_lut = nullptr; a.kmask = e->mask;
-    a.B = B; a.H = H; a.Lq = PU; a.Lk = v.L; a.ldq = in; a.ldk = a.ldv = ldkv; a.ldo = in; a.causal = 0;
-    a.drop = no_drop();
-    P5_TRY(launch_attn_fwd<T>(a, s));
+    for (int ch = 0; ch < nchunk; ++ch) {
+      P5AttnArgs a;
+      memset(&a, 0, sizeof(a));
+      a.Q = (const T*)w.q + (size_t)ch * B * CQ * in; a.K = (const T*)w.kv_all + (size_t)i * 2 * in; a.V = (const T*)w.kv_all + (size_t)i * 2 * in + in;
+      a.O = (T*)w.o + (size_t)ch * B * CQ * in; a.lse = w.lse;
+      a.rel_table = nullptr; a.bucket_lut = nullptr; a.kmask = e->mask;
+      a.B = B; a.H = H; a.Lq = CQ; a.Lk = L; a.ldq = in; a.ldk = a.ldv = ldkv; a.ldo = in; a.causal = 0;
+      a.drop = no_drop();
+      P5_TRY(launch_attn_fwd<T>(a, s));
+    }
     P5_TRY(linear_fwd<T>(s, w.o, in, Wc<T>(e, lo.ca.o), y, d, rows, d, in, P5_EPI_RESID_DROP, x, d));
     std::swap(x, y);
     // feed-forward
@@ -1959,7 +1963,30 @@ static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* o
     P5_TRY(linear_fwd<T>(s, w.h, F, Wc<T>(e, lo.wo), y, d, rows, d, F, P5_EPI_RESID_DROP, x, d));
     std::swap(x, y);
   }
-  P5_TRY(rmsnorm_fwd<T>(s, w.hn, nullptr, x, e->P + e->off_dec_fln, rows, d, c.eps, no_drop()));
+  return rmsnorm_fwd<T>(s, w.hn, nullptr, x, e->P + e->off_dec_fln, rows, d, c.eps, no_drop());
+}
+
+// SCORE + REPLAY.  PU: rows per user of this pass (>= the plan's largest row count, a multiple of 16, <= cap): the decoder runs on
+// [B x PU] rows (decoder_rows_pass, one chunk).
+template <class T>
+static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* out_seq, float* out_score, int* out_len, int* out_missing, hipStream_t s) {
+  VerifyCtx& v = *e->ver;
+  VerifyWs& w = v.w;
+  const P5Config& c = e->c;
+  SplitScope split(sizeof(T) == 4 ? g_opt_verify_split : 0);
+  const int d = c.d_model, H = c.n_heads, B = v.B, K = v.K, max_len = v.max_len;
+  const int rows = B * PU, R = B * K;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  P5_LAUNCH(p5_verify_rows_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, w.ids, w.node_flat, w.depth_flat, w.pl, B, PU, c.pad_id);
+  P5_TRY(P5_KCHECK());
+  RowsPassBufs pb;
+  pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
+  auto tree_attn = [&](T* o, const T* qkv) -> int {
+    P5_LAUNCH((p5_tree_attn_kernel<T>), dim3((rows * H + 3) / 4), dim3(256), 0, s, o, qkv, w.pl, (const int*)w.depth_flat,
+              (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, B, PU, H);
+    return P5_KCHECK();
+  };
+  P5_TRY((decoder_rows_pass<T>(e, pb, B, PU, 1, v.L, tree_attn, s)));
   // log-sum-exp over the full vocabulary per row + the log-probabilities of the row's trie children (running score 0)
   hipMemsetAsync(w.zeros, 0, (size_t)rows * 4, s);
   const float alpha = 1.0f / sqrtf((float)d);
@@ -2006,6 +2033,138 @@ static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* o
   P5_TRY(P5_KCHECK());
   hipMemcpyAsync(out_missing, w.missing, (size_t)B * 4, hipMemcpyDeviceToDevice, s);
   v.begun = v.encoded = v.planned = false;
+  return 0;
+}
+
+// ---- exhaustive catalogue ranking (p5_rank.h): encoder -> decoder_rows_pass over the trie's rows -> edge log-probabilities -> item
+// scores -> per-user top N.  One call, nothing kept between calls. ----
+struct RankWs {
+  void* kv_all;
+  int64_t* ids;
+  void *x, *y, *n, *qkv, *q, *o, *h, *hn;
+  float *lse, *head, *edge_lp, *scores;
+  unsigned long long* part;
+  int CQ, nchunk;        // layout of the pass: [nchunk][B][CQ]
+  int HC_stream, HC_logits;      // rows per launch of the head + score phase (streaming head / materialised logits)
+  int G, S;              // first selection stage: G workgroups per user over slices of S items
+};
+#define P5_RANK_LOGITS_BYTES ((size_t)256 << 20)      // the [rows, V] logits of one head chunk never exceed this
+static int64_t layout_rank(P5Engine* e, char* base, int B, int L, int rows, int64_t n_edges, int n_items, int top_n, RankWs* out) {
+  const P5Config& c = e->c;
+  const size_t sz = c.dtype == 1 ? 2 : 4;
+  const int d = c.d_model, in = e->inner, F = c.d_ff, H = c.n_heads;
+  RankWs tmp;
+  RankWs& w = out ? *out : tmp;
+  // at most 512 rows of a user per chunk (the cross-attention kernels' query limit), chunks of equal size in whole 16-row tiles
+  w.nchunk = (rows + 511) / 512;
+  w.CQ = ((rows + w.nchunk - 1) / w.nchunk + 15) / 16 * 16;
+  const size_t R = (size_t)B * w.CQ * w.nchunk;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  const int64_t enc_bytes = layout_ws(e, base, B, L, 0, false);
+  Bump b{base, (size_t)enc_bytes};
+  w.kv_all = b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz);
+  w.ids = (int64_t*)b.take(R * 8);
+  w.x = b.take(R * d * sz); w.y = b.take(R * d * sz); w.n = b.take(R * d * sz);
+  w.qkv = b.take(R * 3 * in * sz); w.q = b.take(R * in * sz); w.o = b.take(R * in * sz);
+  w.h = b.take(R * (c.gated_gelu ? 3 : 1) * F * sz); w.hn = b.take(R * d * sz);
+  w.lse = (float*)b.take((size_t)B * H * w.CQ * 4);
+  // head + score phase in row chunks: per-tile partials of the streaming head, or the logits of the materialised route
+  const int nv = head_nv(e);
+  const size_t nt = nv > 0 ? (size_t)(c.vocab_size + nv - 1) / nv : 0;
+  size_t hl = P5_RANK_LOGITS_BYTES / ((size_t)Vp * 4) / 16 * 16;
+  hl = hl < 16 ? 16 : hl;
+  w.HC_logits = (int)(hl < R ? hl : R);
+  w.HC_stream = (int)(R < 8192 ? R : 8192);
+  const size_t head_bytes_l = (size_t)w.HC_logits * Vp * 4, head_bytes_s = 2 * (size_t)w.HC_stream * nt * 4;
+  w.head = (float*)b.take(head_bytes_l > head_bytes_s ? head_bytes_l : head_bytes_s);
+  w.edge_lp = (float*)b.take((size_t)B * n_edges * 4);
+  w.scores = (float*)b.take((size_t)B * n_items * 4);
+  const int slice = top_n * 4 > 1024 ? top_n * 4 : 1024;
+  w.G = (n_items + slice - 1) / slice;
+  w.G = w.G < 1 ? 1 : (w.G > 64 ? 64 : w.G);
+  w.S = (n_items + w.G - 1) / w.G;
+  w.part = (unsigned long long*)b.take((size_t)B * w.G * top_n * 8);
+  return (int64_t)((b.off + 255) & ~(size_t)255);
+}
+
+struct RankArgs {
+  const int64_t *input_ids, *whole_word_ids, *attention_mask;
+  int B, L;
+  const int *child_off, *child_tok;
+  int64_t n_edges;
+  P5RankPlan pl;
+  const int* item_edges;
+  int n_items, path_len;
+  const uint32_t* excluded;
+  int top_n, exact;
+  float* out_scores_all; int* out_index; float* out_score; int* out_flagged;
+  char* ws;
+};
+template <class T>
+static int rank_items_impl(P5Engine* e, RankArgs& r, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int split_on = (sizeof(T) == 4 && !r.exact) ? g_opt_verify_split : 0;
+  SplitScope split(split_on);
+  RankWs w;
+  layout_rank(e, r.ws, r.B, r.L, r.pl.rows, r.n_edges, r.n_items, r.top_n, &w);
+  const int d = c.d_model, in = e->inner, H = c.n_heads, B = r.B;
+  P5RankPlan pl = r.pl;
+  pl.B = B; pl.CQ = w.CQ; pl.nchunk = w.nchunk;
+  const int R = B * w.CQ * w.nchunk;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  // encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl)
+  layout_ws(e, r.ws, B, r.L, 0, false);
+  e->B = B; e->L = r.L; e->T = 0; e->M = B * r.L; e->Md = 0; e->training = 0;
+  e->ids = r.input_ids; e->ww = r.whole_word_ids; e->mask = r.attention_mask; e->labels = nullptr;
+  P5_TRY(encoder_fwd<T>(e, s));
+  P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * r.L, c.n_dec_layers * 2 * in, c.d_model));
+  // the decoder over every prefix of the trie
+  P5_LAUNCH(p5_rank_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, w.ids, pl, c.pad_id);
+  P5_TRY(P5_KCHECK());
+  RowsPassBufs pb;
+  pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
+  auto tree_attn = [&](T* o, const T* qkv) -> int {
+    P5_LAUNCH((p5_rank_tree_attn_kernel<T>), dim3((unsigned)(((long long)R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, (const float*)(e->P + e->off_dec_rel),
+              e->lut_dec, e->lut_half, H);
+    return P5_KCHECK();
+  };
+  P5_TRY((decoder_rows_pass<T>(e, pb, B, w.CQ, w.nchunk, r.L, tree_attn, s)));
+  hipMemsetAsync(r.out_flagged, 0, (size_t)B * 4, s);
+  if (split_on) {     // (ordered behind the clear on this stream)
+    P5_LAUNCH((p5_rank_range_kernel<T>), dim3(B, w.nchunk), dim3(256), 0, s, r.out_flagged, (const T*)w.hn, B, w.CQ, d);
+    P5_TRY(P5_KCHECK());
+  }
+  // tied head + the log-probability of every edge, in row chunks (the buffers of this phase do not grow with the catalogue)
+  hipMemsetAsync(w.edge_lp, 0, (size_t)B * r.n_edges * 4, s);
+  const float alpha = 1.0f / sqrtf((float)d);
+  const bool streaming = head_nv(e) > 0 && !split_on;     // (with split products the head is a throughput GEMM into logits, as in verify_run_impl)
+  const int HC = streaming ? w.HC_stream : w.HC_logits;
+  for (int g0 = 0; g0 < R; g0 += HC) {
+    const int nr = R - g0 < HC ? R - g0 : HC;
+    const T* hn = (const T*)w.hn + (size_t)g0 * d;
+    if (streaming) {
+      const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
+      float* part_m = w.head; float* part_s = w.head + (size_t)w.HC_stream * nt;
+      P5_TRY(launch_head_lse<T>(e, part_m, part_s, hn, nr, nullptr, s));
+      P5_LAUNCH((p5_rank_score_kernel<T>), dim3(nr), dim3(256), 0, s, w.edge_lp, (long long)r.n_edges, (const float*)part_m, (const float*)part_s, nt,
+                (const T*)w.hn, Wc<T>(e, e->off_E), d, alpha, pl, g0, r.child_off, r.child_tok);
+    } else {
+      P5_TRY(linear_fwd<T>(s, hn, d, Wc<T>(e, e->off_E), w.head, Vp, nr, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
+      P5_LAUNCH(p5_rank_score_logits_kernel, dim3(nr), dim3(256), 0, s, w.edge_lp, (long long)r.n_edges, (const float*)w.head, Vp, c.vocab_size, pl, g0,
+                r.child_off, r.child_tok);
+    }
+    P5_TRY(P5_KCHECK());
+  }
+  // item scores and the per-user top N
+  P5_LAUNCH(p5_rank_items_kernel, dim3((r.n_items + 255) / 256, B), dim3(256), 0, s, w.scores, (const float*)w.edge_lp, (long long)r.n_edges, r.item_edges,
+            r.n_items, r.path_len);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_rank_select_part_kernel, dim3(w.G, B), dim3(256), 0, s, w.part, (const float*)w.scores, r.excluded, (r.n_items + 31) / 32, r.n_items, w.S,
+            r.top_n);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_rank_select_kernel, dim3(B), dim3(256), 0, s, r.out_index, r.out_score, (const unsigned long long*)w.part, w.G, r.top_n);
+  P5_TRY(P5_KCHECK());
+  if (r.out_scores_all) hipMemcpyAsync(r.out_scores_all, w.scores, (size_t)B * r.n_items * 4, hipMemcpyDeviceToDevice, s);
   return 0;
 }
 
@@ -2921,6 +3080,33 @@ int p5_verify_run(P5Engine* e, int rows_per_user, const uint32_t* excluded_nodes
                          : verify_run_impl<float>(e, rows_per_user, excluded_nodes, out_seq, out_score, out_len, out_missing, (hipStream_t)stream);
 }
 int p5_generate_set_encoder_output(P5Engine* e, const float* enc_out_f32) { e->enc_ext_next = enc_out_f32; return 0; }
+int64_t p5_rank_workspace_bytes(const P5Engine* e, int B, int L, int rows_per_user, int64_t n_edges, int n_items, int top_n) {
+  return layout_rank(const_cast<P5Engine*>(e), nullptr, B, L, rows_per_user, n_edges, n_items, top_n, nullptr);
+}
+int p5_rank_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                  const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                  const int* row_anc, int rows_per_user, int max_depth, const int* item_edges, int n_items, int path_len,
+                  const uint32_t* excluded_items, int top_n, int exact_products, float* out_scores_all, int* out_index, float* out_score,
+                  int* out_flagged, void* ws, int64_t ws_bytes, void* stream) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_REQUIRE(B >= 1 && L >= 1 && L <= 512, "rank_items: B >= 1, 1 <= L <= 512");
+  P5_REQUIRE(child_off && child_tok && n_edges >= 1 && row_tok && row_depth && row_node && row_anc && item_edges, "rank_items: trie / plan / path arrays");
+  P5_REQUIRE(rows_per_user >= 1 && max_depth >= 1 && max_depth <= e->lut_half, "rank_items: rows_per_user >= 1, 1 <= max_depth <= the bucket LUT's half length");
+  P5_REQUIRE((int64_t)B * ((rows_per_user + 15) / 16 * 16 + 16 * ((rows_per_user + 511) / 512)) * e->c.n_heads < ((int64_t)1 << 31), "rank_items: B x rows_per_user x heads must stay below 2^31 (rank fewer users per call)");
+  P5_REQUIRE(n_items >= 1 && path_len >= 1, "rank_items: n_items, path_len");
+  P5_REQUIRE(top_n >= 1 && top_n <= P5_WIDE_MAX_K, "rank_items: 1 <= top_n <= 4096");
+  P5_REQUIRE(out_index && out_score && out_flagged, "rank_items: out_index / out_score / out_flagged");
+  const int64_t need = layout_rank(e, nullptr, B, L, rows_per_user, n_edges, n_items, top_n, nullptr);
+  P5_REQUIRE(ws && ws_bytes >= need, "workspace too small");
+  RankArgs r;
+  r.input_ids = input_ids; r.whole_word_ids = whole_word_ids; r.attention_mask = attention_mask; r.B = B; r.L = L;
+  r.child_off = child_off; r.child_tok = child_tok; r.n_edges = n_edges;
+  r.pl.row_tok = row_tok; r.pl.row_depth = row_depth; r.pl.row_node = row_node; r.pl.anc = row_anc; r.pl.rows = rows_per_user; r.pl.max_depth = max_depth;
+  r.pl.B = B; r.pl.CQ = 0; r.pl.nchunk = 0;
+  r.item_edges = item_edges; r.n_items = n_items; r.path_len = path_len; r.excluded = excluded_items; r.top_n = top_n; r.exact = exact_products;
+  r.out_scores_all = out_scores_all; r.out_index = out_index; r.out_score = out_score; r.out_flagged = out_flagged; r.ws = (char*)ws;
+  return e->c.dtype == 1 ? rank_items_impl<bf16>(e, r, (hipStream_t)stream) : rank_items_impl<float>(e, r, (hipStream_t)stream);
+}
 int p5_generate_timing(P5Engine* e, int enable, float* encode_ms, float* decode_ms) {
 #ifndef P5_EMU
   if (encode_ms || decode_ms) {

@@ -143,19 +143,15 @@ __global__ __launch_bounds__(256) void p5_verify_rows_kernel(int64_t* __restrict
 // ---- 3. self-attention of a row over its ancestors (the causal decoder self-attention of HF modeling_t5.py:217-279 restricted to the
 // row's own prefix; unidirectional relative-position bias by depth difference).  One wave per (row, head); lane = (key slot lane / 8,
 // dims (lane % 8) * 8 ..): eight ancestors per pass, 16-byte loads. ----
-template <class T>
-__global__ __launch_bounds__(256) void p5_tree_attn_kernel(T* __restrict__ out, const T* __restrict__ qkv, P5VerifyPlan pl,
-                                                          const int* __restrict__ depth_flat, const float* __restrict__ rel_table,
-                                                          const int* __restrict__ lut, int lut_half, int B, int PU, int H) {
+// the wave's work for row r, head h: `anc[t]` names the ancestor at depth t < depth, `row_of` turns that name into a row of qkv / out
+// (shared with the exhaustive ranking pass, p5_rank.h, whose ancestor table is one per trie and whose rows are laid out in chunks)
+template <class T, class RowOf>
+__device__ static __forceinline__ void p5_tree_attn_row(T* __restrict__ out, const T* __restrict__ qkv, int r, int h, int depth,
+                                                        const int* __restrict__ anc, RowOf row_of, const float* __restrict__ rel_table,
+                                                        const int* __restrict__ lut, int lut_half, int H) {
   const int lane = threadIdx.x & 63;
-  const int rh = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (rh >= B * PU * H) return;
-  const int r = rh / H, h = rh % H;
-  const int b = r / PU, ri = r % PU;
   const int inner = H * 64;
   const int ts = lane >> 3, dc = lane & 7;
-  const int depth = depth_flat[r];
-  const int* __restrict__ anc = pl.anc + ((size_t)b * pl.cap + (ri < pl.cap ? ri : 0)) * pl.max_len;
   auto ld8 = [](const T* p, float* o) {
     if constexpr (sizeof(T) == 2) unpack16<T>(ld16(p), o);
     else { unpack16<T>(ld16(p), o); unpack16<T>(ld16(p + 4), o + 4); }
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(256) void p5_tree_attn_kernel(T* __restrict__ out, 
     for (int e = 0; e < 8; ++e) { kk[e] = 0.f; vv[e] = 0.f; }
     float s = P5_NEG_INF;
     if (t <= depth) {
-      const int ar = (t == depth) ? r : b * PU + anc[t];
+      const int ar = (t == depth) ? r : row_of(anc[t]);
       const T* base = qkv + (size_t)ar * 3 * inner + inner + h * 64 + dc * 8;
       ld8(base, kk);
       ld8(base + inner, vv);
@@ -208,6 +204,17 @@ __global__ __launch_bounds__(256) void p5_tree_attn_kernel(T* __restrict__ out, 
     for (int e = 0; e < 8; ++e) o[e] *= inv;
     st8(out + (size_t)r * inner + h * 64 + dc * 8, o);
   }
+}
+template <class T>
+__global__ __launch_bounds__(256) void p5_tree_attn_kernel(T* __restrict__ out, const T* __restrict__ qkv, P5VerifyPlan pl,
+                                                          const int* __restrict__ depth_flat, const float* __restrict__ rel_table,
+                                                          const int* __restrict__ lut, int lut_half, int B, int PU, int H) {
+  const int rh = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rh >= B * PU * H) return;
+  const int r = rh / H, h = rh % H;
+  const int b = r / PU, ri = r % PU;
+  const int* __restrict__ anc = pl.anc + ((size_t)b * pl.cap + (ri < pl.cap ? ri : 0)) * pl.max_len;
+  p5_tree_attn_row<T>(out, qkv, r, h, depth_flat[r], anc, [=](int a) { return b * PU + a; }, rel_table, lut, lut_half, H);
 }
 
 // ---- 4. REPLAY: one beam-search step of the real width Kb on the fp32 row scores; one workgroup per user ----

@@ -153,6 +153,7 @@ class P5T5Native(nn.Module):
     prefix_fast_forward = True    # the steps every item shares ("<dataset> item _") as one teacher-forced pass (p5_generate_set_forced_prefix)
     NARROW_MAX_K = 64             # widest search of the narrow beam step (csrc/p5_decode.h); up to WIDE_MAX_K beams run the wide one (p5_decode_wide.h)
     WIDE_MAX_K = 4096
+    rank_max_bytes = 4 << 30      # rank_items(): users per pass are as many as fit a workspace of this many bytes (p5_rank_workspace_bytes)
     wide_max_rows = 4096          # a wide search (K > 64) runs over at most this many decode rows (users x beams) per call: larger batches go in user
                                   # chunks (the step KV cache alone is n_dec_layers x max_len x rows x 2 x inner x sizeof(T): ~3 GiB for fp32
                                   # T5-small at max_len 30)
@@ -194,7 +195,8 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
-        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran
+        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("rank_fp32" | "rank_bf16": rank_items())
+        self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}
         self._warned_wide_verified = False
         self._shadow_t = None       # transposed bf16 copy of the layer weights (data gradients run on the forward GEMM kernel)
         self._grads_dead = False    # zero_grad(set_to_none=True) was called and no backward has run since: `.grad` holds stale values
@@ -755,17 +757,7 @@ class P5T5Native(nn.Module):
                 roots = trie._roots
         if trie is None:
             raise ValueError("generate() needs a trie / prefix_allowed_tokens_fn (OpenP5 always decodes under the item trie)")
-        if isinstance(trie, Trie) or (hasattr(trie, "trie_dict") and not isinstance(trie, CompiledTrie)):
-            app = getattr(trie, "append_trie", None)
-            key = (getattr(trie, "len", None), id(app), getattr(app, "len", None), getattr(trie, "bos_token_id", None))
-            cache = getattr(trie, "_p5_compiled", None)
-            if cache is None or cache[0] != key:
-                cache = (key, CompiledTrie.from_trie(trie))        # (grafts an appended trie, trie.py)
-                try:
-                    trie._p5_compiled = cache
-                except Exception:
-                    pass
-            trie = cache[1]
+        trie = self._compiled_trie(trie)
         off, tok, nxt = trie.device_arrays(dev)
         input_ids = self._i64(input_ids, dev)
         B, L = input_ids.shape
@@ -837,6 +829,138 @@ class P5T5Native(nn.Module):
         if return_dict_in_generate:
             return {"sequences": sequences, "sequences_scores": scores if output_scores else None}
         return sequences
+
+    @staticmethod
+    def _compiled_trie(trie):
+        """The CompiledTrie of a `Trie` (ours or the reference's), compiled once and cached on it; a CompiledTrie passes through."""
+        if isinstance(trie, Trie) or (hasattr(trie, "trie_dict") and not isinstance(trie, CompiledTrie)):
+            app = getattr(trie, "append_trie", None)
+            key = (getattr(trie, "len", None), id(app), getattr(app, "len", None), getattr(trie, "bos_token_id", None))
+            cache = getattr(trie, "_p5_compiled", None)
+            if cache is None or cache[0] != key:
+                cache = (key, CompiledTrie.from_trie(trie))        # (grafts an appended trie, trie.py)
+                try:
+                    trie._p5_compiled = cache
+                except Exception:
+                    pass
+            trie = cache[1]
+        return trie
+
+    # ------------------------------------------------------------------ exhaustive catalogue ranking (csrc/p5_rank.h)
+    @torch.no_grad()
+    def rank_items(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, top_n: int = 10, excluded_items=None,
+                   return_all_scores: bool = False, generation_mode: Optional[str] = None, roots=None):
+        """Rank the WHOLE catalogue for every user, exactly: one teacher-forced decoder pass over every prefix of the item trie gives each
+        item the score HF's beam search would assign it (sum of its tokens' log-probabilities up to and including </s>, divided by their
+        number), then an exact top-`top_n` per user -- what `generate(num_beams = number of items + 1)` returns, without a search.
+        `trie`: Trie / CompiledTrie; items are indexed on demand (`CompiledTrie.index_items`; an unindexed trie's items are numbered in
+        lexicographic order).  `excluded_items`: per-user lists of item indices that are not ranked (their scores are still computed).
+        Arithmetic follows `generation_mode` as generate() does: a bf16 model in "verified" mode ranks with the fp32 verification engine,
+        in "draft" mode with the bf16 engine; an fp32 model ranks in fp32.  fp32 passes multiply with split products; a user whose pass
+        leaves their range is rescored with exact fp32 products.  Users go through in chunks whose workspace fits `rank_max_bytes`.
+        Returns {"sequences" int64 [B * top_n, S] (decoder start first, pad-filled), "sequences_scores" [B * top_n], "item_index"
+        [B, top_n] (-1 and score -1e9 where a user has fewer than top_n candidates), "scores" [B, n_items] or None}."""
+        lib, dev = self._lib, self._be.device
+        if roots is not None:
+            raise ValueError("rank_items: per-user roots are not supported (one trie, shared by all users)")
+        if trie is None:
+            raise ValueError("rank_items() needs the item trie (Trie / CompiledTrie)")
+        N = int(top_n)
+        if not 1 <= N <= self.WIDE_MAX_K:
+            raise ValueError(f"rank_items(top_n={N}): 1 <= top_n <= {self.WIDE_MAX_K}")
+        trie = self._compiled_trie(trie)
+        if trie.grafted:
+            raise ValueError("rank_items: a trie with an appended trie (Trie.append) is a DAG; exhaustive ranking needs a tree of items")
+        if getattr(trie, "item_edges", None) is None:
+            trie.index_items(trie.enumerate_items())
+        mode = self.generation_mode if generation_mode is None else generation_mode
+        if mode not in ("verified", "draft"):
+            raise ValueError(f"generation_mode={mode!r} (verified | draft)")
+        start = self.config.decoder_start_token_id
+        plan = trie.rank_plan(start)
+        if plan["levels"] > self.LUT_HALF:
+            raise ValueError(f"rank_items: items longer than {self.LUT_HALF} tokens")
+        off, tok, _ = trie.device_arrays(dev)
+        row_tok, row_depth, row_node, row_anc, item_edges, item_tokens = trie.rank_device_arrays(dev, start)
+        n_items, n_edges, rows = int(item_edges.shape[0]), int(tok.numel()), int(plan["rows"])
+        input_ids = self._i64(input_ids, dev)
+        B, L = input_ids.shape
+        if whole_word_ids is None:
+            whole_word_ids = torch.zeros_like(input_ids)
+        whole_word_ids = self._i64(whole_word_ids, dev)
+        if attention_mask is None:
+            attention_mask = (input_ids != self.config.pad_token_id).long()
+        attention_mask = self._i64(attention_mask, dev)
+        excl_t = None
+        if excluded_items is not None:
+            if len(excluded_items) != B:
+                raise ValueError(f"excluded_items: one list of item indices per user ({B}), got {len(excluded_items)}")
+            bm = np.zeros((B, (n_items + 31) // 32), dtype=np.uint32)
+            for b, items in enumerate(excluded_items):
+                it = np.unique(np.asarray(list(items), dtype=np.int64))
+                if it.size and (it[0] < 0 or it[-1] >= n_items):
+                    raise ValueError(f"excluded_items[{b}]: item indices must be in 0 .. {n_items - 1}")
+                np.bitwise_or.at(bm[b], it >> 5, (np.uint32(1) << (it & 31).astype(np.uint32)))
+            excl_t = torch.from_numpy(bm.view(np.int32)).to(dev)
+        self._sync_shadow()
+        self._sync_transposed()
+        lane = self._cur_lane()
+        if self.compute_dtype == 1 and mode == "draft":
+            engine, path = lane.engine, "rank_bf16"
+        elif self.compute_dtype == 1:
+            engine, path = self._verify_engine(lane), "rank_fp32"
+        else:
+            engine, path = lane.engine, "rank_fp32"
+        need = lambda nb: int(lib.p5_rank_workspace_bytes(engine, nb, L, rows, n_edges, n_items, N))      # noqa: E731
+        budget = int(self.rank_max_bytes)
+        if need(1) > budget:
+            raise ValueError(f"rank_items: one user of this catalogue needs a workspace of {need(1)} bytes, rank_max_bytes is {budget}")
+        per = B
+        while need(per) > budget:
+            per = max(1, min(per - 1, per * budget // need(per)))
+        index = torch.empty(B, N, dtype=torch.int32, device=dev)
+        score = torch.empty(B, N, dtype=torch.float32, device=dev)
+        scores_all = torch.empty(B, n_items, dtype=torch.float32, device=dev) if return_all_scores else None
+        sp = self._be.stream_ptr()
+
+        def run(users, exact):
+            nb = int(users.numel())
+            whole = nb == B and bool((users == torch.arange(B, device=users.device)).all())
+            cut = lambda t: None if t is None else (t if whole else t[users].contiguous())      # noqa: E731
+            ids_c, ww_c, mask_c, ex_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(excl_t)
+            o_idx = torch.empty(nb, N, dtype=torch.int32, device=dev)
+            o_sc = torch.empty(nb, N, dtype=torch.float32, device=dev)
+            o_all = torch.empty(nb, n_items, dtype=torch.float32, device=dev) if return_all_scores else None
+            flagged = torch.zeros(nb, dtype=torch.int32, device=dev)
+            ws = self._lane_workspace(lane, need(nb), "rank")
+            self._be.check(lib.p5_rank_items(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, _ptr(off), _ptr(tok), n_edges, _ptr(row_tok),
+                                             _ptr(row_depth), _ptr(row_node), _ptr(row_anc), rows, int(row_anc.shape[1]), _ptr(item_edges), n_items,
+                                             int(item_edges.shape[1]), _ptr(ex_c), N, 1 if exact else 0, _ptr(o_all), _ptr(o_idx), _ptr(o_sc),
+                                             _ptr(flagged), _ptr(ws), ws.numel(), sp), "p5_rank_items")
+            return o_idx, o_sc, o_all, flagged
+
+        rescored = 0
+        for a in range(0, B, per):
+            users = torch.arange(a, min(B, a + per), device=dev)
+            o_idx, o_sc, o_all, flagged = run(users, False)
+            index[users], score[users] = o_idx, o_sc
+            if scores_all is not None:
+                scores_all[users] = o_all
+            bad = users[flagged.nonzero().flatten()]
+            if bad.numel():
+                # a value of the split-product pass left the range of the two-term fp16 split: these users again, with exact fp32 products
+                rescored += int(bad.numel())
+                o_idx, o_sc, o_all, flagged = run(bad, True)
+                index[bad], score[bad] = o_idx, o_sc
+                if scores_all is not None:
+                    scores_all[bad] = o_all
+        with self._stats_lock:
+            st = self.rank_stats
+            st["calls"] += 1; st["users"] += B; st["rescored_users"] += rescored; st["users_per_pass"] = per; st["rows_per_user"] = rows
+        self.last_generate_path = path
+        item_index = index.to(torch.int64)
+        sequences = item_tokens[item_index.clamp(min=0)] * (item_index >= 0).unsqueeze(-1)       # (a missing candidate: the all-pad sequence)
+        return {"sequences": sequences.reshape(B * N, -1), "sequences_scores": score.reshape(B * N), "item_index": item_index, "scores": scores_all}
 
     def _in_user_chunks(self, fn, args):
         """fn(*args) for a search wider than the narrow step, over consecutive chunks of users of at most `wide_max_rows` decode rows each,

@@ -48,7 +48,11 @@ def parse_runner_args(parser):
     parser.add_argument("--test_before_train", type=int, default=1, help="whether test before training")
     parser.add_argument("--test_filtered", type=int, default=0, help="whether filter out the items in the training data.")
     parser.add_argument("--test_filtered_batch", type=int, default=1, help="whether testing with filtered data in batch (1 = the reference's widened beam, "
-                        "up to 64 beams; 2 = history excluded inside the search, any history length; 0 = per-user protocol).")
+                        "up to 4096 beams; 2 = history excluded inside the search, any history length; 0 = per-user protocol).")
+    parser.add_argument("--test_exhaustive", type=int, default=0, help="1 = rank the whole catalogue exactly instead of searching it "
+                        "(P5T5Native.rank_items: one pass scores every item of the trie, then an exact top generate_num; with --test_filtered "
+                        "the user's history is left out of the ranking, whichever --test_filtered_batch is set): the limit the widened-beam "
+                        "protocol approaches, at any catalogue size and history length.  0 = the beam-search protocols, untouched.")
     parser.add_argument("--gen_lanes", type=int, default=3, help="evaluation batches in flight (P5T5Native.map_lanes): each lane has its own search / "
                         "verification engines, workspaces and HIP stream over the one set of weights, so one batch's latency-bound beam search overlaps "
                         "the next one's; 1 = one batch at a time")
@@ -177,6 +181,7 @@ class DistributedRunner:
         self.test_epoch, self.valid_select = args.test_epoch, args.valid_select
         self.test_before_train = args.test_before_train
         self.test_filtered, self.test_filtered_batch = args.test_filtered, args.test_filtered_batch
+        self.test_exhaustive = int(getattr(args, "test_exhaustive", 0))
         self.id_metrics = int(getattr(args, "id_metrics", 1))
         self.gen_lanes = int(getattr(args, "gen_lanes", 3))
         self.metrics = args.metrics.split(",")
@@ -438,6 +443,19 @@ class DistributedRunner:
                                    return_dict_in_generate=True, **kw)
         return evaluate.rel_results_ids(pred["sequences"], pred["sequences_scores"], batch[3].to(pred["sequences"].device), num_beams)
 
+    def _rank_metrics(self, batch, ct, excluded_items=None):
+        """--test_exhaustive 1: the batch's metric sums from an exact ranking of the whole catalogue (top generate_num, the items of
+        `excluded_items` left out), in either metric form."""
+        pred = self.model.rank_items(input_ids=batch[0], attention_mask=batch[1], whole_word_ids=batch[2], trie=ct, top_n=self.generate_num,
+                                     excluded_items=excluded_items)
+        if self.id_metrics:
+            rel = evaluate.rel_results_ids(pred["sequences"], pred["sequences_scores"], batch[3].to(pred["sequences"].device), self.generate_num)
+            return evaluate.get_metrics_results_ids(rel, self.metrics), len(rel)
+        gold = self.tokenizer.batch_decode(batch[3], skip_special_tokens=True)
+        gen = self.tokenizer.batch_decode(pred["sequences"], skip_special_tokens=True)
+        rel = evaluate.rel_results(gen, gold, pred["sequences_scores"].detach().cpu().tolist(), self.generate_num)
+        return evaluate.get_metrics_results(rel, self.metrics), len(rel)
+
     def _lanes_map(self, fn, batches):
         """fn(batch) for every batch in order, several batches in flight when the model offers generation lanes (P5T5Native.map_lanes)."""
         ml = getattr(self.model, "map_lanes", None)
@@ -483,6 +501,8 @@ class DistributedRunner:
 
         def one(batch):          # runs on a generation lane (its own stream): everything up to the batch's metric sums
             batch = self._to_dev(batch)
+            if self.test_exhaustive:
+                return self._rank_metrics(batch, ct)
             if self.id_metrics:
                 rel = self._generate_ids(batch, self.generate_num, 50, trie=ct)
                 return evaluate.get_metrics_results_ids(rel, self.metrics), len(rel)
@@ -510,7 +530,10 @@ class DistributedRunner:
             # the reference rebuilds Trie(all_items - positive) per user (hence its eval_batch_size == 1); here the shared
             # device trie is used with one excluded-node bitmap per user, so any batch size works
             users = [ds.id2user[int(u)] for u in batch[5].detach().cpu().tolist()]
-            excluded = ct.excluded_bitmap([[index[i] for i in ds.positive[u] if i in index] for u in users])
+            history = [[index[i] for i in ds.positive[u] if i in index] for u in users]
+            if self.test_exhaustive:
+                return self._rank_metrics(batch, ct, excluded_items=history)
+            excluded = ct.excluded_bitmap(history)
             if self.id_metrics:
                 rel = self._generate_ids(batch, self.generate_num, 30, trie=ct, excluded=excluded)
                 return evaluate.get_metrics_results_ids(rel, self.metrics), len(rel)
@@ -538,6 +561,9 @@ class DistributedRunner:
         trie, ct, index = self._dataset_trie(ds)
         fn = prefix_allowed_tokens_fn(trie)
         width = self.generate_num + ds.max_positive
+        if self.test_exhaustive:
+            # the widened beam ranks the catalogue and drops the history afterwards; an exact ranking without the history is its limit
+            return self.test_dataset_task_filtered(testloader)
         if self.test_filtered_batch >= 2:
             # OPT-IN (--test_filtered_batch 2): exclude each user's history INSIDE the constrained search (shared device trie + per-user
             # excluded-node bitmap, batched) instead of widening the beam -- history never appears, the top generate_num are kept.  This is

@@ -219,15 +219,23 @@ class CompiledTrie:
         off, tok, nxt = self.child_off, self.child_tok, self.child_node
         for n in range(self.n_nodes):
             for e in range(off[n], off[n + 1]):
-                edge[(n, int(tok[e]))] = int(nxt[e])
+                edge[(n, int(tok[e]))] = e
         depth = max((len(q) for q in seqs), default=0)
         paths = np.full((len(seqs), depth), -1, dtype=np.int32)
+        edges = np.full((len(seqs), depth), -1, dtype=np.int32)
+        tokens = np.zeros((len(seqs), depth), dtype=np.int64)
         for i, q in enumerate(seqs):
             n = 0
             for j, t in enumerate(q):
-                n = edge[(n, int(t))]
+                e = edge[(n, int(t))]
+                n = int(nxt[e])
                 paths[i, j] = n
+                edges[i, j] = e
+                tokens[i, j] = int(t)
         self.item_paths = paths
+        self.item_edges = edges          # the edge taken at each position (index into child_tok / child_node): what `rank_items` sums over
+        self.item_tokens = tokens        # the sequences themselves, pad-filled (token 0)
+        self._dev_items = {}
         cnt = np.zeros(self.n_nodes, dtype=np.int64)
         np.add.at(cnt, paths[paths >= 0], 1)
         self.items_under = cnt
@@ -246,6 +254,84 @@ class CompiledTrie:
             dead = u[self.items_under[u] == c]
             np.bitwise_or.at(bm[b], dead >> 5, (np.uint32(1) << (dead & 31).astype(np.uint32)))
         return bm
+
+    def enumerate_items(self) -> List[List[int]]:
+        """Every root-to-leaf token sequence, in lexicographic order (children are sorted by token)."""
+        if self.grafted:
+            raise ValueError("enumerate_items: a trie with an appended trie is a DAG, its items are not enumerated")
+        out, stack = [], [(0, [])]
+        while stack:
+            n, prefix = stack.pop()
+            lo, hi = int(self.child_off[n]), int(self.child_off[n + 1])
+            if lo == hi:
+                if prefix:
+                    out.append(prefix)
+                continue
+            for e in range(hi - 1, lo - 1, -1):
+                stack.append((int(self.child_node[e]), prefix + [int(self.child_tok[e])]))
+        return out
+
+    def rank_plan(self, start_id: int):
+        """The plan of the exhaustive ranking pass (csrc/p5_rank.h), ONE per trie: a row for every non-leaf node reachable from the start
+        node (the prefix that leads to it -- the node behind </s> has no children and needs no row), level by level, so parents precede
+        children.  dict of int32 arrays: row_tok (decoder input), row_parent, row_depth (generated tokens in the prefix), row_node, and
+        row_anc [rows, levels] (row of the ancestor at depth t < depth).  Cached per start token."""
+        cache = self.__dict__.setdefault("_rank_plans", {})
+        key = int(start_id)
+        if key in cache:
+            return cache[key]
+        if self.grafted:
+            raise ValueError("rank_plan: a trie with an appended trie is a DAG (one node, several prefixes); exhaustive ranking needs a tree")
+        off = self.child_off.astype(np.int64)
+        node = -1
+        for c in range(int(off[0]), int(off[1])) if self.n_nodes > 0 else ():
+            if int(self.child_tok[c]) == key:
+                node = int(self.child_node[c])
+        if node < 0 or off[node + 1] == off[node]:
+            raise ValueError(f"rank_plan: no item of the trie starts with the decoder start token {key}")
+        f_node, f_tok, f_par = np.asarray([node], dtype=np.int64), np.asarray([key], dtype=np.int64), np.asarray([-1], dtype=np.int64)
+        toks, pars, deps, nodes = [], [], [], []
+        n_rows, depth = 0, 0
+        while f_node.size:
+            rows = n_rows + np.arange(f_node.size, dtype=np.int64)
+            toks.append(f_tok); pars.append(f_par); deps.append(np.full(f_node.size, depth, dtype=np.int64)); nodes.append(f_node)
+            n_rows += f_node.size
+            lo, cnt = off[f_node], off[f_node + 1] - off[f_node]
+            total = int(cnt.sum())
+            e = np.repeat(lo - np.concatenate(([0], np.cumsum(cnt)[:-1])), cnt) + np.arange(total, dtype=np.int64)
+            c_node = self.child_node[e].astype(np.int64)
+            keep = off[c_node + 1] > off[c_node]
+            f_node, f_tok, f_par = c_node[keep], self.child_tok[e].astype(np.int64)[keep], np.repeat(rows, cnt)[keep]
+            depth += 1
+            assert depth <= self.n_nodes, "CompiledTrie: the child table has a cycle"
+        row_parent, row_depth = np.concatenate(pars), np.concatenate(deps)
+        anc = np.zeros((n_rows, depth), dtype=np.int32)
+        first = 0
+        for lvl in pars:                 # (level by level: a row's ancestors are its parent's, then the parent)
+            r = np.arange(first, first + lvl.size)
+            d = int(row_depth[first])
+            if d > 0:
+                anc[r, :d - 1] = anc[lvl, :d - 1]
+                anc[r, d - 1] = lvl
+            first += lvl.size
+        plan = {"row_tok": np.concatenate(toks).astype(np.int32), "row_parent": row_parent.astype(np.int32), "row_depth": row_depth.astype(np.int32),
+                "row_node": np.concatenate(nodes).astype(np.int32), "row_anc": np.ascontiguousarray(anc), "rows": int(n_rows), "levels": int(depth)}
+        cache[key] = plan
+        return plan
+
+    def rank_device_arrays(self, device, start_id: int):
+        """(plan tensors row_tok, row_depth, row_node, row_anc; item_edges behind the start token [n_items, depth - 1]; item_tokens int64) on
+        `device`, cached per (device, start token)."""
+        import torch
+        key = (str(device), int(start_id))
+        if key not in self._dev_items:
+            plan = self.rank_plan(start_id)
+            if self.item_tokens.shape[1] < 2 or not bool((self.item_tokens[:, 0] == int(start_id)).all()):
+                raise ValueError(f"rank_items: every indexed item must start with the decoder start token {int(start_id)}")
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
+            self._dev_items[key] = (t(plan["row_tok"]), t(plan["row_depth"]), t(plan["row_node"]), t(plan["row_anc"]),
+                                    t(self.item_edges[:, 1:]), t(self.item_tokens))
+        return self._dev_items[key]
 
     def children(self, node: int):
         a, b = self.child_off[node], self.child_off[node + 1]
