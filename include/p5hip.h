@@ -259,6 +259,29 @@ int p5_rank_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_wo
                   const int* row_anc, int rows_per_user, int max_depth, const int* item_edges, int n_items, int path_len,
                   const uint32_t* excluded_items, int top_n, int exact_products, float* out_scores_all, int* out_index, float* out_score,
                   int* out_flagged, void* ws, int64_t ws_bytes, void* stream);
+/* ---- per-user candidate lists: the exact score and order of C chosen items per user in one pass (openp5_amd/csrc/p5_cand.h) ----
+ * The sampled-candidates evaluation protocol and re-ranking ask for the scores of a few items per user, not of the catalogue.  A user's
+ * decoder rows are the non-leaf prefixes of that user's candidates only -- a subset of the rows of the exhaustive plan above that
+ * contains every row's ancestors -- so the work and every buffer follow the candidates; none has a size that depends on the catalogue.
+ *   candidates int32 [B, C]: item indices, -1 = empty slot; a user's items are distinct.
+ *   item_rows int32 [n_items][path_len]: plan row (CompiledTrie.rank_plan numbering) of the item's prefix at each depth, -1 beyond its
+ *     last non-leaf prefix.  item_tokens int64 [n_items][token_stride]: the sequences, column 0 = the decoder start token.
+ *   row_tok / row_depth / row_anc: the trie's plan arrays, as above.
+ * Protocol: (1) the plan call finds every user's rows on the device (sorted, distinct; integer sort and scan, no atomics) and writes
+ * the largest row count of the batch into the first int32 of the workspace; (2) the host reads that ONE integer and makes sure the
+ * workspace holds the workspace-bytes function's value for it -- the plan's part leads the workspace, is what that function returns
+ * for rows_per_user = 0, and must be kept (or copied to the head of a larger workspace); (3) the score call runs encoder, decoder pass
+ * ([chunk][user][<= 512] rows), head and scoring, and orders the slots.
+ *   out_scores fp32 [B, C] in slot order (-1e9 for an empty slot); out_order int32 [B, top_n] slots by (score desc, item index asc),
+ *   out_index / out_score their items and scores; ranks beyond a user's candidates: -1, -1, -1e9.  out_flagged / exact_products as above.
+ * Limits: top_n <= C <= 4096, L <= 512, rows_per_user <= C x path_len, a tree-shaped trie.  Both calls enqueue on `stream` only. */
+int64_t p5_cand_workspace_bytes(const P5Engine* e, int B, int L, int C, int path_len, int rows_per_user);
+int p5_cand_plan(P5Engine* e, const int* candidates, int B, int C, const int* item_rows, int n_items, int path_len, void* ws, int64_t ws_bytes,
+                 void* stream);
+int p5_cand_score(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                  const int* row_tok, const int* row_depth, const int* row_anc, int max_depth, const int* candidates, int C, const int* item_rows,
+                  const int64_t* item_tokens, int n_items, int path_len, int token_stride, int rows_per_user, int top_n, int exact_products,
+                  float* out_scores, int* out_order, int* out_index, float* out_score, int* out_flagged, void* ws, int64_t ws_bytes, void* stream);
 /* Device-time brackets of p5_generate for benchmarks: p5_generate_timing(e, 1, NULL, NULL) arms it; after a p5_generate call,
  * p5_generate_timing(e, enable, &encode_ms, &decode_ms) WAITS for that call to finish and returns the time between its start and
  * its first decode step (encoder pass + cross-attention K/V projection + beam state) and the time of the decode loop itself. */

@@ -23,6 +23,7 @@
 #include "p5_decode_wide.h"
 #include "p5_verify.h"
 #include "p5_rank.h"
+#include "p5_cand.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -2168,6 +2169,146 @@ static int rank_items_impl(P5Engine* e, RankArgs& r, hipStream_t s) {
   return 0;
 }
 
+// ---- per-user candidate lists (p5_cand.h): PLAN on the device (p5_cand_plan: the users' rows, the largest row count in the header word
+// the host reads) -> encoder -> decoder_rows_pass over each user's own rows -> the requested edges only -> per-user order.  The plan's
+// buffers lead the workspace and depend on B, C and path_len alone; nothing depends on the size of the catalogue. ----
+struct CandWs {
+  int *hdr, *n_rows, *sel;
+  unsigned long long* keys;
+  int cap, P;            // stride of sel; keys per user of the plan's sort (a power of two)
+  size_t plan_bytes;
+  void* kv_all;
+  int64_t* ids;
+  void *x, *y, *n, *qkv, *q, *o, *h, *hn;
+  float *lse, *head, *row_lse, *scores;
+  int CQ, nchunk, HC_stream, HC_logits;
+};
+static int64_t layout_cand(P5Engine* e, char* base, int B, int L, int C, int path_len, int rows, CandWs* out) {
+  const P5Config& c = e->c;
+  const size_t sz = c.dtype == 1 ? 2 : 4;
+  const int d = c.d_model, in = e->inner, F = c.d_ff, H = c.n_heads;
+  CandWs tmp;
+  CandWs& w = out ? *out : tmp;
+  Bump p{base, 0};
+  w.cap = C * path_len;
+  w.P = 256;
+  while (w.P < w.cap) w.P <<= 1;
+  w.hdr = (int*)p.take(64);
+  w.n_rows = (int*)p.take((size_t)B * 4);
+  w.sel = (int*)p.take((size_t)B * w.cap * 4);
+  w.keys = (unsigned long long*)p.take((size_t)B * w.P * 8);
+  w.plan_bytes = (p.off + 255) & ~(size_t)255;
+  if (rows <= 0) return (int64_t)w.plan_bytes;
+  w.nchunk = (rows + 511) / 512;
+  w.CQ = ((rows + w.nchunk - 1) / w.nchunk + 15) / 16 * 16;
+  const size_t R = (size_t)B * w.CQ * w.nchunk;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  char* pass = base ? base + w.plan_bytes : nullptr;
+  const int64_t enc_bytes = layout_ws(e, pass, B, L, 0, false);
+  Bump b{pass, (size_t)enc_bytes};
+  w.kv_all = b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz);
+  w.ids = (int64_t*)b.take(R * 8);
+  w.x = b.take(R * d * sz); w.y = b.take(R * d * sz); w.n = b.take(R * d * sz);
+  w.qkv = b.take(R * 3 * in * sz); w.q = b.take(R * in * sz); w.o = b.take(R * in * sz);
+  w.h = b.take(R * (c.gated_gelu ? 3 : 1) * F * sz); w.hn = b.take(R * d * sz);
+  w.lse = (float*)b.take((size_t)B * H * w.CQ * 4);
+  const int nv = head_nv(e);
+  const size_t nt = nv > 0 ? (size_t)(c.vocab_size + nv - 1) / nv : 0;
+  size_t hl = P5_RANK_LOGITS_BYTES / ((size_t)Vp * 4) / 16 * 16;
+  hl = hl < 16 ? 16 : hl;
+  w.HC_logits = (int)(hl < R ? hl : R);
+  w.HC_stream = (int)(R < 8192 ? R : 8192);
+  const size_t head_bytes_l = (size_t)w.HC_logits * Vp * 4, head_bytes_s = 2 * (size_t)w.HC_stream * nt * 4;
+  w.head = (float*)b.take(head_bytes_l > head_bytes_s ? head_bytes_l : head_bytes_s);
+  w.row_lse = (float*)b.take(R * 4);
+  w.scores = (float*)b.take((size_t)B * C * 4);
+  return (int64_t)(w.plan_bytes + ((b.off + 255) & ~(size_t)255));
+}
+
+static int cand_plan_impl(P5Engine* e, const int* cand, int B, int C, const int* item_rows, int n_items, int path_len, char* ws, hipStream_t s) {
+  CandWs w;
+  layout_cand(e, ws, B, 1, C, path_len, 0, &w);
+  P5_LAUNCH(p5_cand_plan_kernel, dim3(B), dim3(256), 0, s, w.sel, w.n_rows, w.keys, cand, item_rows, C, n_items, path_len, w.cap, w.P);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, B);
+  return P5_KCHECK();
+}
+
+struct CandArgs {
+  const int64_t *input_ids, *whole_word_ids, *attention_mask;
+  int B, L;
+  const int *row_tok, *row_depth, *row_anc;
+  int max_depth;
+  const int *cand, *item_rows;
+  const int64_t* item_tokens;
+  int C, n_items, path_len, ldt, rows, top_n, exact;
+  float* out_scores; int* out_order; int* out_index; float* out_score; int* out_flagged;
+  char* ws;
+};
+template <class T>
+static int cand_score_impl(P5Engine* e, CandArgs& r, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int split_on = (sizeof(T) == 4 && !r.exact) ? g_opt_verify_split : 0;
+  SplitScope split(split_on);
+  CandWs w;
+  layout_cand(e, r.ws, r.B, r.L, r.C, r.path_len, r.rows, &w);
+  const int d = c.d_model, in = e->inner, H = c.n_heads, B = r.B;
+  P5CandPlan pl;
+  pl.g.row_tok = r.row_tok; pl.g.row_depth = r.row_depth; pl.g.row_node = nullptr; pl.g.anc = r.row_anc;
+  pl.g.rows = r.rows; pl.g.max_depth = r.max_depth; pl.g.B = B; pl.g.CQ = w.CQ; pl.g.nchunk = w.nchunk;
+  pl.sel = w.sel; pl.n_rows = w.n_rows; pl.cap = w.cap;
+  const int R = B * w.CQ * w.nchunk;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  // encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl); its buffers follow the plan's
+  layout_ws(e, r.ws + w.plan_bytes, B, r.L, 0, false);
+  e->B = B; e->L = r.L; e->T = 0; e->M = B * r.L; e->Md = 0; e->training = 0;
+  e->ids = r.input_ids; e->ww = r.whole_word_ids; e->mask = r.attention_mask; e->labels = nullptr;
+  P5_TRY(encoder_fwd<T>(e, s));
+  P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * r.L, c.n_dec_layers * 2 * in, c.d_model));
+  // the decoder over every user's own prefixes
+  P5_LAUNCH(p5_cand_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, w.ids, pl, c.pad_id);
+  P5_TRY(P5_KCHECK());
+  RowsPassBufs pb;
+  pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
+  auto tree_attn = [&](T* o, const T* qkv) -> int {
+    P5_LAUNCH((p5_cand_tree_attn_kernel<T>), dim3((unsigned)(((long long)R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, (const float*)(e->P + e->off_dec_rel),
+              e->lut_dec, e->lut_half, H);
+    return P5_KCHECK();
+  };
+  P5_TRY((decoder_rows_pass<T>(e, pb, B, w.CQ, w.nchunk, r.L, tree_attn, s)));
+  hipMemsetAsync(r.out_flagged, 0, (size_t)B * 4, s);
+  if (split_on) {     // (ordered behind the clear on this stream)
+    P5_LAUNCH((p5_rank_range_kernel<T>), dim3(B, w.nchunk), dim3(256), 0, s, r.out_flagged, (const T*)w.hn, B, w.CQ, d);
+    P5_TRY(P5_KCHECK());
+  }
+  // tied head: the log-sum-exp of every row, in row chunks (the two routes of rank_items_impl, chosen by the same condition)
+  const float alpha = 1.0f / sqrtf((float)d);
+  const bool streaming = head_nv(e) > 0 && !split_on;
+  const int HC = streaming ? w.HC_stream : w.HC_logits;
+  for (int g0 = 0; g0 < R; g0 += HC) {
+    const int nr = R - g0 < HC ? R - g0 : HC;
+    const T* hn = (const T*)w.hn + (size_t)g0 * d;
+    if (streaming) {
+      const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
+      float* part_m = w.head; float* part_s = w.head + (size_t)w.HC_stream * nt;
+      P5_TRY(launch_head_lse<T>(e, part_m, part_s, hn, nr, nullptr, s));
+      P5_LAUNCH(p5_cand_lse_kernel, dim3(nr), dim3(256), 0, s, w.row_lse, (const float*)part_m, (const float*)part_s, nt, g0);
+    } else {
+      P5_TRY(linear_fwd<T>(s, hn, d, Wc<T>(e, e->off_E), w.head, Vp, nr, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
+      P5_LAUNCH(p5_cand_lse_logits_kernel, dim3(nr), dim3(256), 0, s, w.row_lse, (const float*)w.head, Vp, c.vocab_size, g0);
+    }
+    P5_TRY(P5_KCHECK());
+  }
+  // the candidates' scores and the per-user order
+  P5_LAUNCH((p5_cand_score_kernel<T>), dim3((r.C + 31) / 32, B), dim3(256), 0, s, w.scores, (const T*)w.hn, Wc<T>(e, e->off_E), d, alpha,
+            (const float*)w.row_lse, pl, r.cand, r.C, r.item_rows, r.item_tokens, r.ldt, r.n_items, r.path_len);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_cand_order_kernel, dim3(B), dim3(256), 0, s, r.out_order, r.out_index, r.out_score, (const float*)w.scores, r.cand, r.C, r.n_items, r.top_n);
+  P5_TRY(P5_KCHECK());
+  hipMemcpyAsync(r.out_scores, w.scores, (size_t)B * r.C * 4, hipMemcpyDeviceToDevice, s);
+  return 0;
+}
+
 // =====================================================================================================
 // C ABI
 // =====================================================================================================
@@ -3106,6 +3247,39 @@ int p5_rank_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_wo
   r.item_edges = item_edges; r.n_items = n_items; r.path_len = path_len; r.excluded = excluded_items; r.top_n = top_n; r.exact = exact_products;
   r.out_scores_all = out_scores_all; r.out_index = out_index; r.out_score = out_score; r.out_flagged = out_flagged; r.ws = (char*)ws;
   return e->c.dtype == 1 ? rank_items_impl<bf16>(e, r, (hipStream_t)stream) : rank_items_impl<float>(e, r, (hipStream_t)stream);
+}
+int64_t p5_cand_workspace_bytes(const P5Engine* e, int B, int L, int C, int path_len, int rows_per_user) {
+  return layout_cand(const_cast<P5Engine*>(e), nullptr, B, L, C, path_len, rows_per_user, nullptr);
+}
+int p5_cand_plan(P5Engine* e, const int* candidates, int B, int C, const int* item_rows, int n_items, int path_len, void* ws, int64_t ws_bytes,
+                 void* stream) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_REQUIRE(candidates && item_rows && B >= 1 && n_items >= 1 && path_len >= 1, "cand_plan: candidates / item_rows / B / n_items / path_len");
+  P5_REQUIRE(C >= 1 && C <= P5_WIDE_MAX_K, "cand_plan: 1 <= C <= 4096");
+  P5_REQUIRE(ws && ws_bytes >= layout_cand(e, nullptr, B, 1, C, path_len, 0, nullptr), "workspace too small");
+  return cand_plan_impl(e, candidates, B, C, item_rows, n_items, path_len, (char*)ws, (hipStream_t)stream);
+}
+int p5_cand_score(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                  const int* row_tok, const int* row_depth, const int* row_anc, int max_depth, const int* candidates, int C, const int* item_rows,
+                  const int64_t* item_tokens, int n_items, int path_len, int token_stride, int rows_per_user, int top_n, int exact_products,
+                  float* out_scores, int* out_order, int* out_index, float* out_score, int* out_flagged, void* ws, int64_t ws_bytes, void* stream) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_REQUIRE(B >= 1 && L >= 1 && L <= 512, "cand_score: B >= 1, 1 <= L <= 512");
+  P5_REQUIRE(row_tok && row_depth && row_anc && candidates && item_rows && item_tokens, "cand_score: plan / candidate / item arrays");
+  P5_REQUIRE(max_depth >= 1 && max_depth <= e->lut_half, "cand_score: 1 <= max_depth <= the bucket LUT's half length");
+  P5_REQUIRE(C >= 1 && C <= P5_WIDE_MAX_K && top_n >= 1 && top_n <= C, "cand_score: 1 <= top_n <= C <= 4096");
+  P5_REQUIRE(n_items >= 1 && path_len >= 1 && token_stride > path_len, "cand_score: n_items, path_len, token_stride > path_len");
+  P5_REQUIRE(rows_per_user >= 1 && rows_per_user <= C * path_len, "cand_score: 1 <= rows_per_user <= C x path_len");
+  P5_REQUIRE((int64_t)B * ((rows_per_user + 15) / 16 * 16 + 16 * ((rows_per_user + 511) / 512)) * e->c.n_heads < ((int64_t)1 << 31), "cand_score: B x rows_per_user x heads must stay below 2^31 (score fewer users per call)");
+  P5_REQUIRE(out_scores && out_order && out_index && out_score && out_flagged, "cand_score: outputs");
+  P5_REQUIRE(ws && ws_bytes >= layout_cand(e, nullptr, B, L, C, path_len, rows_per_user, nullptr), "workspace too small");
+  CandArgs r;
+  r.input_ids = input_ids; r.whole_word_ids = whole_word_ids; r.attention_mask = attention_mask; r.B = B; r.L = L;
+  r.row_tok = row_tok; r.row_depth = row_depth; r.row_anc = row_anc; r.max_depth = max_depth;
+  r.cand = candidates; r.item_rows = item_rows; r.item_tokens = item_tokens; r.C = C; r.n_items = n_items; r.path_len = path_len; r.ldt = token_stride;
+  r.rows = rows_per_user; r.top_n = top_n; r.exact = exact_products;
+  r.out_scores = out_scores; r.out_order = out_order; r.out_index = out_index; r.out_score = out_score; r.out_flagged = out_flagged; r.ws = (char*)ws;
+  return e->c.dtype == 1 ? cand_score_impl<bf16>(e, r, (hipStream_t)stream) : cand_score_impl<float>(e, r, (hipStream_t)stream);
 }
 int p5_generate_timing(P5Engine* e, int enable, float* encode_ms, float* decode_ms) {
 #ifndef P5_EMU

@@ -145,17 +145,9 @@ __global__ __launch_bounds__(256) void p5_rank_score_kernel(float* __restrict__ 
   }
 }
 
-// ---- SCORE over materialised logits (toy widths, and the split-product head): logits hold rows g0 .. of the pass; lse as
-// p5_dec_score_kernel computes it ----
-__global__ __launch_bounds__(256) void p5_rank_score_logits_kernel(float* __restrict__ edge_lp, long long n_edges, const float* __restrict__ logits,
-                                                                  int ldl, int V, P5RankPlan pl, int g0, const int* __restrict__ child_off,
-                                                                  const int* __restrict__ child_tok) {
-  __shared__ float sm[4], ss[4];
-  const int g = g0 + blockIdx.x, tid = threadIdx.x;
-  int b;
-  const int ru = p5_rank_user_row(pl, g, b);
-  if (ru >= pl.rows) return;
-  const float* lr = logits + (size_t)blockIdx.x * ldl;
+// log-sum-exp of one row of materialised logits, as p5_dec_score_kernel computes it (sm, ss: 4 floats of LDS each)
+__device__ static __forceinline__ float p5_rank_lse_from_logits(const float* __restrict__ lr, int V, float* sm, float* ss) {
+  const int tid = threadIdx.x;
   float m = P5_NEG_INF, sum = 0.f;
   const int V4 = V >> 2;
   for (int j = tid; j < V4; j += 256) {
@@ -178,7 +170,21 @@ __global__ __launch_bounds__(256) void p5_rank_score_logits_kernel(float* __rest
     sum = 0.f;
     for (int w = 0; w < 4; ++w) sum += ss[w] * expf(sm[w] - m);
   }
-  const float lse = m + logf(sum);
+  return m + logf(sum);
+}
+
+// ---- SCORE over materialised logits (toy widths, and the split-product head): logits hold rows g0 .. of the pass; lse as
+// p5_dec_score_kernel computes it ----
+__global__ __launch_bounds__(256) void p5_rank_score_logits_kernel(float* __restrict__ edge_lp, long long n_edges, const float* __restrict__ logits,
+                                                                  int ldl, int V, P5RankPlan pl, int g0, const int* __restrict__ child_off,
+                                                                  const int* __restrict__ child_tok) {
+  __shared__ float sm[4], ss[4];
+  const int g = g0 + blockIdx.x, tid = threadIdx.x;
+  int b;
+  const int ru = p5_rank_user_row(pl, g, b);
+  if (ru >= pl.rows) return;
+  const float* lr = logits + (size_t)blockIdx.x * ldl;
+  const float lse = p5_rank_lse_from_logits(lr, V, sm, ss);
   const int nd = pl.row_node[ru];
   const int c0 = child_off[nd], nc = child_off[nd + 1] - c0;
   float* __restrict__ out = edge_lp + (size_t)b * n_edges + c0;

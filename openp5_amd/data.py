@@ -196,10 +196,11 @@ class TestDataset(Dataset):
                 self.new_token += re.findall(r"\<.*?\>", idx)
         self.all_items = list(self.item_map.values())
         self.test_prompt, self.test_filtered = args.test_prompt, args.test_filtered
-        if args.test_filtered > 0:
+        self.with_users = args.test_filtered > 0 or int(getattr(args, "test_candidates", 0)) > 0      # protocols that need the user of a row
+        if self.with_users:
             self.user2id = {u: i for i, u in enumerate(self.reindex_user_seq_dict)}
             self.id2user = {i: u for u, i in self.user2id.items()}
-            if args.test_filtered_batch > 0:
+            if args.test_filtered > 0 and args.test_filtered_batch > 0:
                 self.positive_text, self.max_positive = self.get_positive_batch()
             self.positive = self.get_positive()
         want_his = "history" in self.info
@@ -230,6 +231,6 @@ class TestDataset(Dataset):
 
     def __getitem__(self, idx):
         item = {"input": self.data["input"][idx], "output": self.data["output"][idx]}
-        if self.test_filtered > 0:
+        if self.with_users:
             item["user_idx"] = self.user2id[self.data_samples[idx]["user_id"]]
         return item

@@ -35,6 +35,19 @@ def rel_results_filtered(user_positive, id2user, user_idx, return_num, predictio
     return out
 
 
+def sample_candidates(all_items, positive, gold, n, seed, dataset, user):
+    """The sampled-candidates protocol's list of one user: [gold] + n negatives drawn without replacement, uniformly, from
+    all_items - positive - {gold} in the order of `all_items` (all of them when fewer than n exist).  The generator is seeded from
+    (seed, dataset, user) alone, so the list does not depend on the rank, the run, the batch size or the other users."""
+    import hashlib
+    import random
+    pool = [i for i in all_items if i != gold and i not in positive]
+    if len(pool) <= n:
+        return [gold] + pool
+    rnd = random.Random(int.from_bytes(hashlib.sha256(f"{seed}\0{dataset}\0{user}".encode()).digest()[:8], "little"))
+    return [gold] + rnd.sample(pool, n)
+
+
 def hit_at_k(relevance, k):
     return float(sum(1 for row in relevance if sum(row[:k]) > 0))
 

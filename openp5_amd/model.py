@@ -195,8 +195,9 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
-        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("rank_fp32" | "rank_bf16": rank_items())
+        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}
+        self.cand_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}      # score_candidates()
         self._warned_wide_verified = False
         self._shadow_t = None       # transposed bf16 copy of the layer weights (data gradients run on the forward GEMM kernel)
         self._grads_dead = False    # zero_grad(set_to_none=True) was called and no backward has run since: `.grad` holds stale values
@@ -961,6 +962,153 @@ class P5T5Native(nn.Module):
         item_index = index.to(torch.int64)
         sequences = item_tokens[item_index.clamp(min=0)] * (item_index >= 0).unsqueeze(-1)       # (a missing candidate: the all-pad sequence)
         return {"sequences": sequences.reshape(B * N, -1), "sequences_scores": score.reshape(B * N), "item_index": item_index, "scores": scores_all}
+
+    # ------------------------------------------------------------------ per-user candidate lists (csrc/p5_cand.h)
+    @torch.no_grad()
+    def score_candidates(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, candidates=None, top_n: Optional[int] = None,
+                         generation_mode: Optional[str] = None):
+        """The exact score and order of C chosen items per user (sampled-candidates evaluation, re-ranking a first stage's short list):
+        one teacher-forced decoder pass over the prefixes of each user's OWN candidates -- the numbers `rank_items` gives those items,
+        at a cost that follows the candidates, with no buffer that grows with the catalogue.
+        `candidates`: LongTensor [B, C] or a list of B lists (ragged lists are padded with -1 = empty slot) of item indices in the order
+        given to `CompiledTrie.index_items` (an unindexed trie is indexed on demand in lexicographic order); a user's items are distinct.
+        Engine choice, split products and the exact rescoring of flagged users follow `rank_items`; users go through in chunks whose
+        workspace fits `rank_max_bytes`.  `top_n` defaults to C.
+        Returns {"scores" fp32 [B, C] in slot order (-1e9 for an empty slot), "order" int64 [B, top_n] slots by (score desc, item index
+        asc) with -1 beyond the user's candidates, "item_index" [B, top_n], "sequences" int64 [B * top_n, S], "sequences_scores"
+        [B * top_n] (as rank_items returns them)}."""
+        lib, dev = self._lib, self._be.device
+        if trie is None:
+            raise ValueError("score_candidates() needs the item trie (Trie / CompiledTrie)")
+        if candidates is None:
+            raise ValueError("score_candidates() needs `candidates`: item indices per user")
+        trie = self._compiled_trie(trie)
+        if trie.grafted:
+            raise ValueError("score_candidates: a trie with an appended trie (Trie.append) is a DAG; candidate scoring needs a tree of items")
+        if getattr(trie, "item_edges", None) is None:
+            trie.index_items(trie.enumerate_items())
+        mode = self.generation_mode if generation_mode is None else generation_mode
+        if mode not in ("verified", "draft"):
+            raise ValueError(f"generation_mode={mode!r} (verified | draft)")
+        input_ids = self._i64(input_ids, dev)
+        B, L = input_ids.shape
+        if torch.is_tensor(candidates):
+            cand = candidates.detach().cpu().numpy().astype(np.int64)
+        else:
+            rows_ = [list(map(int, c)) for c in candidates]
+            width = max((len(c) for c in rows_), default=0)
+            cand = np.full((len(rows_), max(width, 1)), -1, dtype=np.int64)
+            for b, c in enumerate(rows_):
+                cand[b, :len(c)] = c
+        if cand.ndim != 2 or cand.shape[0] != B or cand.shape[1] < 1:
+            raise ValueError(f"candidates: one list of item indices per user ([B={B}, C]), got shape {tuple(cand.shape)}")
+        C = int(cand.shape[1])
+        if C > self.WIDE_MAX_K:
+            raise ValueError(f"score_candidates: C = {C} candidates per user, at most {self.WIDE_MAX_K}")
+        N = C if top_n is None else int(top_n)
+        if not 1 <= N <= C:
+            raise ValueError(f"score_candidates(top_n={N}): 1 <= top_n <= C = {C}")
+        n_items = int(trie.item_edges.shape[0])
+        if bool(((cand < -1) | (cand >= n_items)).any()):
+            raise ValueError(f"candidates: item indices must be in 0 .. {n_items - 1} (-1 = empty slot)")
+        srt = np.sort(cand, axis=1)
+        if bool(((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any()):
+            raise ValueError("candidates: the same item twice in one user's list")
+        start = self.config.decoder_start_token_id
+        plan = trie.rank_plan(start)
+        if plan["levels"] > self.LUT_HALF:
+            raise ValueError(f"score_candidates: items longer than {self.LUT_HALF} tokens")
+        row_tok, row_depth, row_anc, item_rows, item_tokens = trie.cand_device_arrays(dev, start)
+        path_len, ldt = int(item_rows.shape[1]), int(item_tokens.shape[1])
+        cand_t = torch.from_numpy(cand.astype(np.int32)).to(dev)
+        if whole_word_ids is None:
+            whole_word_ids = torch.zeros_like(input_ids)
+        whole_word_ids = self._i64(whole_word_ids, dev)
+        if attention_mask is None:
+            attention_mask = (input_ids != self.config.pad_token_id).long()
+        attention_mask = self._i64(attention_mask, dev)
+        self._sync_shadow()
+        self._sync_transposed()
+        lane = self._cur_lane()
+        if self.compute_dtype == 1 and mode == "draft":
+            engine, path = lane.engine, "cand_bf16"
+        elif self.compute_dtype == 1:
+            engine, path = self._verify_engine(lane), "cand_fp32"
+        else:
+            engine, path = lane.engine, "cand_fp32"
+        need = lambda nb, rows: int(lib.p5_cand_workspace_bytes(engine, nb, L, C, path_len, rows))      # noqa: E731
+        budget = int(self.rank_max_bytes)
+        sp = self._be.stream_ptr()
+
+        def fit(rows):          # users per pass
+            if need(1, rows) > budget:
+                what = f"one user's {rows} rows need" if rows else "the plan of one user's candidates needs"
+                raise ValueError(f"score_candidates: {what} a workspace of {need(1, rows)} bytes, rank_max_bytes is {budget}")
+            per = B
+            while need(per, rows) > budget:
+                per = max(1, min(per - 1, per * budget // need(per, rows)))
+            return per
+
+        def plan_users(cand_c, nb, nbytes):
+            ws = self._lane_workspace(lane, nbytes, "cand")
+            self._be.check(lib.p5_cand_plan(engine, _ptr(cand_c), nb, C, _ptr(item_rows), n_items, path_len, _ptr(ws), ws.numel(), sp), "p5_cand_plan")
+            return ws
+
+        # PLAN on the device; the one integer the host reads is the largest row count (it sizes the pass)
+        per0, rows, ws = fit(0), 0, None
+        for a in range(0, B, per0):
+            nb = min(B, a + per0) - a
+            ws = plan_users(cand_t[a:a + nb].contiguous(), nb, need(nb, 0))
+            rows = max(rows, int(ws[:4].view(torch.int32).item()))
+        rows = max(rows, 1)
+        per = fit(rows)
+        scores = torch.empty(B, C, dtype=torch.float32, device=dev)
+        order = torch.empty(B, N, dtype=torch.int32, device=dev)
+        index = torch.empty(B, N, dtype=torch.int32, device=dev)
+        score = torch.empty(B, N, dtype=torch.float32, device=dev)
+
+        def run(users, exact, planned=None):
+            nb = int(users.numel())
+            whole = nb == B and bool((users == torch.arange(B, device=users.device)).all())
+            cut = lambda t: t if whole else t[users].contiguous()      # noqa: E731
+            ids_c, ww_c, mask_c, cand_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(cand_t)
+            o_all = torch.empty(nb, C, dtype=torch.float32, device=dev)
+            o_ord = torch.empty(nb, N, dtype=torch.int32, device=dev)
+            o_idx = torch.empty(nb, N, dtype=torch.int32, device=dev)
+            o_sc = torch.empty(nb, N, dtype=torch.float32, device=dev)
+            flagged = torch.zeros(nb, dtype=torch.int32, device=dev)
+            if planned is None:
+                ws = plan_users(cand_c, nb, need(nb, rows))
+            else:               # the plan made above leads the workspace: kept, or carried to the head of the larger one
+                ws = self._lane_workspace(lane, need(nb, rows), "cand")
+                if ws.data_ptr() != planned.data_ptr():
+                    head = need(nb, 0)
+                    ws[:head].copy_(planned[:head])
+            self._be.check(lib.p5_cand_score(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, _ptr(row_tok), _ptr(row_depth), _ptr(row_anc),
+                                             int(row_anc.shape[1]), _ptr(cand_c), C, _ptr(item_rows), _ptr(item_tokens), n_items, path_len, ldt, rows, N,
+                                             1 if exact else 0, _ptr(o_all), _ptr(o_ord), _ptr(o_idx), _ptr(o_sc), _ptr(flagged), _ptr(ws), ws.numel(), sp),
+                           "p5_cand_score")
+            return o_all, o_ord, o_idx, o_sc, flagged
+
+        rescored = 0
+        for a in range(0, B, per):
+            users = torch.arange(a, min(B, a + per), device=dev)
+            o_all, o_ord, o_idx, o_sc, flagged = run(users, False, ws if (per == B and per0 >= B) else None)
+            scores[users], order[users], index[users], score[users] = o_all, o_ord, o_idx, o_sc
+            bad = users[flagged.nonzero().flatten()]
+            if bad.numel():
+                # a value of the split-product pass left the range of the two-term fp16 split: these users again, with exact fp32 products
+                rescored += int(bad.numel())
+                o_all, o_ord, o_idx, o_sc, flagged = run(bad, True)
+                scores[bad], order[bad], index[bad], score[bad] = o_all, o_ord, o_idx, o_sc
+        with self._stats_lock:
+            st = self.cand_stats
+            st["calls"] += 1; st["users"] += B; st["rescored_users"] += rescored; st["users_per_pass"] = per; st["rows_per_user"] = rows
+        self.last_generate_path = path
+        item_index = index.to(torch.int64)
+        sequences = item_tokens[item_index.clamp(min=0)] * (item_index >= 0).unsqueeze(-1)       # (no candidate at this rank: the all-pad sequence)
+        return {"scores": scores, "order": order.to(torch.int64), "item_index": item_index, "sequences": sequences.reshape(B * N, -1),
+                "sequences_scores": score.reshape(B * N)}
 
     def _in_user_chunks(self, fn, args):
         """fn(*args) for a search wider than the narrow step, over consecutive chunks of users of at most `wide_max_rows` decode rows each,

@@ -53,6 +53,11 @@ def parse_runner_args(parser):
                         "(P5T5Native.rank_items: one pass scores every item of the trie, then an exact top generate_num; with --test_filtered "
                         "the user's history is left out of the ranking, whichever --test_filtered_batch is set): the limit the widened-beam "
                         "protocol approaches, at any catalogue size and history length.  0 = the beam-search protocols, untouched.")
+    parser.add_argument("--test_candidates", type=int, default=0, help="N > 0 = the sampled-candidates protocol: every test user is ranked on the gold "
+                        "item + N negatives drawn uniformly, without replacement, from the items outside the user's history (all of them if fewer "
+                        "exist) by a generator seeded from (--seed, dataset, user) alone, scored exactly in one pass (P5T5Native.score_candidates), "
+                        "metrics over the top min(generate_num, N + 1).  Takes precedence over --test_filtered; not with --test_exhaustive 1.  "
+                        "0 = off, nothing changes.")
     parser.add_argument("--gen_lanes", type=int, default=3, help="evaluation batches in flight (P5T5Native.map_lanes): each lane has its own search / "
                         "verification engines, workspaces and HIP stream over the one set of weights, so one batch's latency-bound beam search overlaps "
                         "the next one's; 1 = one batch at a time")
@@ -182,6 +187,12 @@ class DistributedRunner:
         self.test_before_train = args.test_before_train
         self.test_filtered, self.test_filtered_batch = args.test_filtered, args.test_filtered_batch
         self.test_exhaustive = int(getattr(args, "test_exhaustive", 0))
+        self.test_candidates = int(getattr(args, "test_candidates", 0))
+        if self.test_candidates < 0:
+            raise ValueError(f"--test_candidates {self.test_candidates}: the number of sampled negatives per user (0 = off)")
+        if self.test_candidates > 0 and self.test_exhaustive:
+            raise ValueError("--test_candidates N ranks the gold item among N sampled negatives, --test_exhaustive 1 ranks the whole catalogue: "
+                             "choose one of the two protocols")
         self.id_metrics = int(getattr(args, "id_metrics", 1))
         self.gen_lanes = int(getattr(args, "gen_lanes", 3))
         self.metrics = args.metrics.split(",")
@@ -209,7 +220,7 @@ class DistributedRunner:
     def get_testloader(self):
         self.testloaders = []
         collator = (TestCollator(self.tokenizer, solo_rows=(self.test_filtered_batch == 0)) if self.test_filtered > 0
-                    else Collator(self.tokenizer))
+                    else TestCollator(self.tokenizer) if self.test_candidates > 0 else Collator(self.tokenizer))
         for dataset in self.args.datasets.split(","):
             for task in self.args.tasks.split(","):
                 testdata = TestDataset(self.args, dataset, task)
@@ -403,8 +414,14 @@ class DistributedRunner:
         if path:
             self.model.load_state_dict(torch.load(path, map_location="cpu"), strict=False)
         results = []
+        if self.test_candidates > 0 and self.test_filtered > 0 and self.rank == 0 and not self.__dict__.get("_cand_said"):
+            self._cand_said = True
+            logging.info(f"--test_candidates {self.test_candidates} takes precedence over --test_filtered {self.test_filtered}: "
+                         "the sampled negatives never contain the user's history")
         for loader in self.testloaders:
-            if self.test_filtered > 0:
+            if self.test_candidates > 0:
+                results.append(self.test_dataset_task_candidates(loader))
+            elif self.test_filtered > 0:
                 if self.test_filtered_batch > 0:
                     results.append(self.test_dataset_task_filtered_batch(loader))
                 else:
@@ -511,6 +528,49 @@ class DistributedRunner:
             return evaluate.get_metrics_results(rel, self.metrics), len(rel)
 
         # (collation overlaps the previous generate(); up to --gen_lanes batches are in flight on the device, results come back in order)
+        for m, n in self._lanes_map(one, Prefetcher(testloader, pin=self.device.type == "cuda")):
+            if torch.is_tensor(m) and m.is_cuda:
+                m.record_stream(torch.cuda.current_stream())      # (allocated on the lane's stream, read here)
+            metrics_res = metrics_res + (m.to(self.device) if torch.is_tensor(m) else m)
+            test_total += n
+        return self._finish(metrics_res, test_total, testloader, t0)
+
+    def candidate_lists(self, ds, user_idx):
+        """--test_candidates N: per user of the batch the item ids [gold, N sampled negatives] (evaluate.sample_candidates: the same
+        list on every rank, every run and at every batch size)."""
+        out = []
+        for u in user_idx:
+            user = ds.id2user[int(u)]
+            out.append(evaluate.sample_candidates(ds.all_items, ds.positive[user], ds.reindex_user_seq_dict[user][-1], self.test_candidates,
+                                                  self.args.seed, ds.dataset, user))
+        return out
+
+    @torch.no_grad()
+    def test_dataset_task_candidates(self, testloader):
+        """The sampled-candidates protocol ("1 + N"): the gold item among N negatives from outside the user's history, every list scored
+        exactly in one pass over its own prefixes (P5T5Native.score_candidates), metrics over the top min(generate_num, N + 1)."""
+        ds = testloader.dataset
+        _, ct, index = self._dataset_trie(ds)
+        width = self.test_candidates + 1
+        top_n = min(self.generate_num, width)
+        metrics_res, test_total, t0 = 0, 0, time.perf_counter()
+
+        def one(batch):
+            batch = self._to_dev(batch)
+            lists = self.candidate_lists(ds, batch[5].detach().cpu().tolist())
+            cand = torch.full((len(lists), width), -1, dtype=torch.int64)
+            for b, items in enumerate(lists):
+                cand[b, :len(items)] = torch.tensor([index[i] for i in items], dtype=torch.int64)
+            pred = self.model.score_candidates(input_ids=batch[0], attention_mask=batch[1], whole_word_ids=batch[2], trie=ct, candidates=cand,
+                                               top_n=top_n)
+            if self.id_metrics:
+                rel = evaluate.rel_results_ids(pred["sequences"], pred["sequences_scores"], batch[3].to(pred["sequences"].device), top_n)
+                return evaluate.get_metrics_results_ids(rel, self.metrics), len(rel)
+            gold = self.tokenizer.batch_decode(batch[3], skip_special_tokens=True)
+            gen = self.tokenizer.batch_decode(pred["sequences"], skip_special_tokens=True)
+            rel = evaluate.rel_results(gen, gold, pred["sequences_scores"].detach().cpu().tolist(), top_n)
+            return evaluate.get_metrics_results(rel, self.metrics), len(rel)
+
         for m, n in self._lanes_map(one, Prefetcher(testloader, pin=self.device.type == "cuda")):
             if torch.is_tensor(m) and m.is_cuda:
                 m.record_stream(torch.cuda.current_stream())      # (allocated on the lane's stream, read here)

@@ -236,6 +236,7 @@ class CompiledTrie:
         self.item_edges = edges          # the edge taken at each position (index into child_tok / child_node): what `rank_items` sums over
         self.item_tokens = tokens        # the sequences themselves, pad-filled (token 0)
         self._dev_items = {}
+        self.__dict__.pop("_item_rows", None)        # (item_rows() is per item list)
         cnt = np.zeros(self.n_nodes, dtype=np.int64)
         np.add.at(cnt, paths[paths >= 0], 1)
         self.items_under = cnt
@@ -331,6 +332,28 @@ class CompiledTrie:
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
             self._dev_items[key] = (t(plan["row_tok"]), t(plan["row_depth"]), t(plan["row_node"]), t(plan["row_anc"]),
                                     t(self.item_edges[:, 1:]), t(self.item_tokens))
+        return self._dev_items[key]
+
+    def item_rows(self, start_id: int) -> np.ndarray:
+        """int32 [n_items, depth - 1]: the row of `rank_plan(start_id)` that holds the item's prefix at each depth (depth 0 = the start
+        token alone), -1 beyond the item's last non-leaf prefix.  What `score_candidates` (csrc/p5_cand.h) builds a user's rows from: the
+        union of the candidates' entries.  Cached per start token."""
+        cache = self.__dict__.setdefault("_item_rows", {})
+        key = int(start_id)
+        if key not in cache:
+            plan = self.rank_plan(start_id)
+            node_row = np.full(self.n_nodes + 1, -1, dtype=np.int32)          # (the last entry answers the -1 of a path's filler)
+            node_row[plan["row_node"]] = np.arange(plan["rows"], dtype=np.int32)
+            cache[key] = np.ascontiguousarray(node_row[self.item_paths[:, :-1]])
+        return cache[key]
+
+    def cand_device_arrays(self, device, start_id: int):
+        """(row_tok, row_depth, row_anc of the plan; item_rows; item_tokens int64) on `device`, cached per (device, start token)."""
+        import torch
+        key = (str(device), int(start_id), "cand")
+        if key not in self._dev_items:
+            row_tok, row_depth, _, row_anc, _, item_tokens = self.rank_device_arrays(device, start_id)
+            self._dev_items[key] = (row_tok, row_depth, row_anc, torch.from_numpy(self.item_rows(start_id)).to(device), item_tokens)
         return self._dev_items[key]
 
     def children(self, node: int):
