@@ -43,7 +43,7 @@ typedef struct P5Engine P5Engine;
 
 const char* p5_last_error(void);
 /* process-wide tuning knobs (tests / benchmarks): "gemm_tile" = 0|64|128|256, "gemm_v2" = 0|2|3|4 (hand-pipelined loop for forced
- * 128x128 tiles), "gemm_ring", "gemm_small_ring", "gemm_ksdma", "gemm_xcd_rect", "decode_fused" = 0|1 */
+ * 128x128 tiles), "gemm_ring", "gemm_small_ring", "gemm_ksdma", "gemm_xcd_rect" = 0|1 */
 int p5_set_option(const char* name, int value);
 int p5_abi_version(void);
 /* In-run kernel profiler (measurement aid, bench.py): between p5_profile_begin() and p5_profile_end() every kernel launch of the library is
@@ -153,13 +153,6 @@ int p5_engine_adamw_step(P5Engine* e, float* m, float* v, const float* sumsq, do
                          double beta2, double eps, double weight_decay, int step_t, int* copies_fresh, void* stream);
 
 /* ---- generation ---- */
-/* Optional: a caller-owned buffer of p5_decode_fold_count(e) elements of the compute dtype.  When bound, p5_generate folds every
- * decoder RMSNorm but the first into the GEMMs around it (norm weight multiplied into the consuming projection, row statistic
- * carried between GEMM epilogues): 18 of 73 launches per decode step fewer for T5-small.  Call p5_refresh_decode_fold after
- * the parameters change (and after p5_refresh_shadow / an optimizer step). */
-int64_t p5_decode_fold_count(const P5Engine* e);
-int p5_engine_bind_decode_fold(P5Engine* e, void* buf);
-int p5_refresh_decode_fold(P5Engine* e, void* stream);
 /* Exact workspace of p5_generate / p5_decode_begin (R = B*K rows, C = min(max_children, 2K), every block rounded up to 256 bytes):
  * the encoder / forced-prefix buffers, cross-attention K/V, the step KV cache (n_dec_layers x max_len x R x 2 x inner x sizeof(T)),
  * the decode-step activations, per-row head partials and candidate scratch (R x max_children fp32), the beam state, and

@@ -59,9 +59,6 @@ PROTOTYPES = {
     "p5_grad_sumsq": (i32, [vp, i64, vp, vp]),
     "p5_adamw_step": (i32, [vp, vp, vp, vp, vp, i64, vp, f64, f64, f64, f64, f64, f64, f64, i32, vp]),
     "p5_engine_adamw_step": (i32, [vp, vp, vp, vp, f64, f64, f64, f64, f64, f64, f64, i32, C.POINTER(i32), vp]),
-    "p5_decode_fold_count": (i64, [vp]),
-    "p5_engine_bind_decode_fold": (i32, [vp, vp]),
-    "p5_refresh_decode_fold": (i32, [vp, vp]),
     "p5_engine_grads_zeroed": (i32, [vp]),
     "p5_engine_clear_grads": (i32, [vp, vp]),
     "p5_engine_discard_grads": (i32, [vp]),

@@ -15,125 +15,6 @@
 #pragma once
 #include "p5_device.h"
 
-// ---- single-token self-attention over the ancestry-indexed cache: one wave per (row, head) ----
-template <class T>
-__global__ __launch_bounds__(256) void p5_dec_self_attn_kernel(T* __restrict__ out, const T* __restrict__ qkv, T* __restrict__ cache,
-                                                              const int* __restrict__ anc_odd, const int* __restrict__ anc_even,
-                                                              const float* __restrict__ rel_table, const int* __restrict__ lut,
-                                                              int lut_half, int R, int H, const int* __restrict__ step, int max_len) {
-  // the step counter lives in device memory (cur_len = tokens so far, incl. the start token) so that ONE captured
-  // hipGraph of the decode step can be replayed for every step; double-buffered state is selected by its parity
-  const int cur_len = *step;
-  const int pos = cur_len - 1;
-  const int* __restrict__ anc = (cur_len & 1) ? anc_odd : anc_even;
-  const int lane = threadIdx.x & 63;
-  const int rh = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (rh >= R * H) return;
-  const int r = rh / H, h = rh % H;
-  const int inner = H * 64;
-  const float q = to_f<T>(qkv[(size_t)r * 3 * inner + h * 64 + lane]);
-  const T kcur = qkv[(size_t)r * 3 * inner + inner + h * 64 + lane];
-  const T vcur = qkv[(size_t)r * 3 * inner + 2 * inner + h * 64 + lane];
-  // cache layout: [max_len][R][2*inner]  (K then V)
-  cache[((size_t)pos * R + r) * 2 * inner + h * 64 + lane] = kcur;
-  cache[((size_t)pos * R + r) * 2 * inner + inner + h * 64 + lane] = vcur;
-  float mys = P5_NEG_INF;
-  for (int t = 0; t <= pos; ++t) {
-    float kv;
-    if (t == pos) kv = to_f<T>(kcur);
-    else kv = to_f<T>(cache[((size_t)t * R + anc[(size_t)t * R + r]) * 2 * inner + h * 64 + lane]);
-    float s = wave_sum(q * kv);
-    s += rel_table[lut[(t - pos) + lut_half] * H + h];
-    if (lane == t) mys = s;
-  }
-  const float m = wave_max(mys);
-  const float p = (lane <= pos) ? expf(mys - m) : 0.f;
-  const float l = wave_sum(p);
-  float o = 0.f;
-  for (int t = 0; t <= pos; ++t) {
-    const float pt = __shfl(p, t);
-    float vv;
-    if (t == pos) vv = to_f<T>(vcur);
-    else vv = to_f<T>(cache[((size_t)t * R + anc[(size_t)t * R + r]) * 2 * inner + inner + h * 64 + lane]);
-    o += pt * vv;
-  }
-  out[(size_t)r * inner + h * 64 + lane] = from_f<T>(o / l);
-}
-
-// ---- single-token cross-attention; K/V of batch item r / Kb are shared by its beams ----
-template <class T>
-__global__ __launch_bounds__(256) void p5_dec_cross_attn_kernel(T* __restrict__ out, const T* __restrict__ q, const T* __restrict__ kv,
-                                                               const int64_t* __restrict__ mask, int R, int H, int Kb, int L) {
-  __shared__ float sq[4][64];
-  __shared__ float sp[4][512];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rh = blockIdx.x * 4 + wave;
-  const bool active = rh < R * H;
-  const int r = active ? rh / H : 0, h = active ? rh % H : 0;
-  const int b = r / Kb;
-  const int inner = H * 64;
-  if (active) sq[wave][lane] = to_f<T>(q[(size_t)r * inner + h * 64 + lane]);
-  __syncthreads();
-  float s[8];
-  float m = P5_NEG_INF;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int j = lane + i * 64;
-    s[i] = P5_NEG_INF;
-    if (active && j < L && mask[(size_t)b * L + j] != 0) {
-      const T* kr = kv + ((size_t)b * L + j) * 2 * inner + h * 64;
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 64 / TT<T>::EPF; ++c) {
-        float x[8];
-        unpack16<T>(ld16(kr + c * TT<T>::EPF), x);
-#pragma unroll
-        for (int e = 0; e < TT<T>::EPF; ++e) acc += x[e] * sq[wave][c * TT<T>::EPF + e];
-      }
-      s[i] = acc;
-    }
-    m = fmaxf(m, s[i]);
-  }
-  m = wave_max(m);
-  if (m == P5_NEG_INF) m = 0.f;
-  float l = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int j = lane + i * 64;
-    const float p = expf(s[i] - m);
-    if (j < 512) sp[wave][j] = p;
-    l += p;
-  }
-  l = wave_sum(l);
-  __syncthreads();
-  if (!active) return;
-  // P V: lane = (key group kg = lane / NDG, dim group dg = lane % NDG); each lane accumulates EPF dims over the keys
-  // j == kg (mod NKG) with one 16-byte load per key, then the key groups are summed with shuffles
-  constexpr int EPF = TT<T>::EPF, NDG = 64 / EPF, NKG = 64 / NDG;
-  const int kg = lane / NDG, dg = lane % NDG;
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int j = kg; j < L; j += NKG) {
-    float x[8];
-    unpack16<T>(ld16(kv + ((size_t)b * L + j) * 2 * inner + inner + h * 64 + dg * EPF), x);
-    const float pj = sp[wave][j];
-#pragma unroll
-    for (int e = 0; e < EPF; ++e) o[e] += pj * x[e];
-  }
-#pragma unroll
-  for (int e = 0; e < EPF; ++e) {
-#pragma unroll
-    for (int msk = NDG; msk < 64; msk <<= 1) o[e] += __shfl_xor(o[e], msk);
-  }
-  if (kg == 0) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-#pragma unroll
-    for (int e = 0; e < EPF; ++e) o[e] *= inv;
-    st16(out + (size_t)r * inner + h * 64 + dg * EPF, pack16<T>(o));
-  }
-}
-
 // block-wide arg-max with deterministic tie-break (lowest index); every thread gets the winner
 __device__ static __forceinline__ void block_argmax(float& bv, int& bi, float* s_val, int* s_idx) {
 #pragma unroll

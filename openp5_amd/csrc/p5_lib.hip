@@ -33,8 +33,6 @@ thread_local std::string g_p5_err;
 // =====================================================================================================
 // tuning knobs (p5_set_option / environment) of the engine and the decode step; the GEMM / attention families keep theirs in their own units
 static int g_opt_wgrad_group = getenv("P5_WGRAD_GROUP") ? atoi(getenv("P5_WGRAD_GROUP")) : 1;   // layer-grouped deferred weight gradients (bf16)
-static int g_opt_decode_fused = getenv("P5_DECODE_FUSED") ? atoi(getenv("P5_DECODE_FUSED")) : 1;   // RMSNorm folded into the decode-step GEMMs
-static int g_opt_decode_v2 = getenv("P5_DECODE_V2") ? atoi(getenv("P5_DECODE_V2")) : 1;   // latency-shaped decode step (p5_decode2.h)
 static int g_opt_dec_nb = getenv("P5_DEC_NB") ? atoi(getenv("P5_DEC_NB")) : 0;           // skinny GEMM: forced column-tile width (0 = auto)
 static int g_opt_dec_kw = getenv("P5_DEC_KW") ? atoi(getenv("P5_DEC_KW")) : 0;           // skinny GEMM: forced K range per workgroup (0 = auto)
 static int g_opt_dec_fuseq = getenv("P5_DEC_FUSEQ") ? atoi(getenv("P5_DEC_FUSEQ")) : 1;   // cross-attention computes its own q projection
@@ -96,18 +94,17 @@ struct Bump {
   }
 };
 
-struct GraphKey { int B, L, K, max_len, max_c, excl_words; const void *ws, *trie, *trie_tok, *trie_node, *roots, *P, *S, *fold, *hist; int sz, fused, wide; };
+struct GraphKey { int B, L, K, max_len, max_c, excl_words; const void *ws, *trie, *trie_tok, *trie_node, *roots, *P, *S, *hist; int sz, fused, wide; };
 
 struct GenWs {
-  void* kv_cross[64];   // per decoder layer: T [B*L, ldkv] -- column slices of ONE [B*L, n_dec*2*inner] block in the latency-shaped path
-  int ldkv;             // (all layers' K/V projections are a single GEMM, as in training), separate [B*L, 2*inner] blocks otherwise
+  void* kv_cross[64];   // per decoder layer: T [B*L, ldkv] -- column slices of ONE [B*L, n_dec*2*inner] block
+  int ldkv;             // (all layers' K/V projections are a single GEMM, as in training)
   void* cache[64];      // per decoder layer: T [max_len, R, 2*inner]
-  void *xa, *xb, *n, *qkv, *q, *o, *h, *hn;
-  float* x32;             // [R, d] fp32 residual stream of the decode step (v2: updated in place with atomics)
+  void *qkv, *q, *o, *h, *hn;
+  float* x32;             // [R, d] fp32 residual stream of the decode step (dec_atomic: updated in place with atomics)
   float *logits, *cand, *row_top_score; int *n_cand, *row_top_c;
   float *part_m, *part_s; int* cand_key;   // streaming head: per (row, vocabulary tile) max / sum exp; candidate keys of pools beyond the LDS budget
   int64_t* mask_copy;
-  float* ssq;             // [3 * n_dec_layers + 1][R] row sums of squares of the residual stream entering each norm (fused path)
   uint32_t* excluded;     // [B, excl_words] copy of the caller's per-item excluded-node bitmap (stable address for the graph)
   int64_t* ff_labels; float* ff_nll;     // forced-prefix pass: its labels [B, F] and per-token NLL
   P5BeamState st;
@@ -175,11 +172,6 @@ struct P5Engine {
   bool grads_zeroed = false;      // the gradient arena holds zeros (p5_engine_clear_grads): the next backward need not clear it
   bool grads_keep = false;        // p5_engine_grads_zeroed(): the next backward ADDS to the arena (2nd.. micro-batch of an accumulation group)
   int wg_epi = P5_EPI_ACCUM;      // how this backward's grouped weight-gradient GEMMs write: P5_EPI_STORE on a first micro-batch
-  // decode-step weights with the following RMSNorm weight folded in (W[out,in] * ln[in]): per decoder layer qkv / cross-q / wi,
-  // and the tied head E * final_ln; caller-owned buffer in the compute dtype (p5_engine_bind_decode_fold)
-  void* fold = nullptr;
-  std::vector<int64_t> fold_qkv, fold_q, fold_wi;
-  int64_t fold_E = 0, fold_count = 0;
   GenCtx gen;
   int* gen_hist_next = nullptr;    // p5_generate_draft: history buffer of the NEXT search (one-shot)
   const float* enc_ext_next = nullptr;   // p5_generate_set_encoder_output: fp32 encoder output the NEXT search starts from (one-shot)
@@ -365,20 +357,6 @@ static void build_layout(P5Engine* e) {
     }
     e->tr_tiles = tiles;
   }
-  // folded decode-step weights (element offsets into the fold buffer, 64-element aligned)
-  {
-    const int in = c.n_heads * c.d_kv;
-    int64_t off = 0;
-    auto take = [&](int64_t n) { const int64_t o = off; off += (n + 63) & ~(int64_t)63; return o; };
-    e->fold_qkv.clear(); e->fold_q.clear(); e->fold_wi.clear();
-    for (int i = 0; i < c.n_dec_layers; ++i) {
-      e->fold_qkv.push_back(take((int64_t)3 * in * d));
-      e->fold_q.push_back(take((int64_t)in * d));
-      e->fold_wi.push_back(take((int64_t)(c.gated_gelu ? 2 : 1) * F * d));
-    }
-    e->fold_E = take((int64_t)c.vocab_size * d);
-    e->fold_count = off;
-  }
 }
 
 template <class T> static const T* Wc(const P5Engine* e, int64_t off) {
@@ -407,14 +385,12 @@ struct SplitScope { int prev; explicit SplitScope(int on) : prev(g_f32_split) { 
 
 template <class T>
 static int gemm(hipStream_t s, const void* A, int lda, int aks, const void* Bm, int ldb, int bks, void* C, int ldc, int M, int N,
-                int K, int epi, const void* aux, int ldaux, float alpha, int c_f32, P5Drop drop, const float* rowss = nullptr,
-                float rowss_eps = 0.f, float* ssq_out = nullptr) {
+                int K, int epi, const void* aux, int ldaux, float alpha, int c_f32, P5Drop drop) {
   P5GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = A; g.B = Bm; g.C = C; g.aux = aux; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux;
   g.a_ks = aks; g.b_ks = bks; g.epi = epi; g.c_f32 = c_f32; g.splitk = 0; g.ring = 0; g.alpha = alpha; g.drop = drop;
-  g.rowss = rowss; g.rowss_invd = 1.0f / (float)K; g.rowss_eps = rowss_eps; g.ssq_out = ssq_out;
-  g.rowss_nt = 0; g.ssq_nt = 0; g.g4_tiles_n = 0; g.g4_nk = 0; g.xcd_bm = g.xcd_bn = 0; g.c_split_stride = 0;
+  g.g4_tiles_n = 0; g.g4_nk = 0; g.xcd_bm = g.xcd_bn = 0; g.c_split_stride = 0;
   g.mm_split = (sizeof(T) == 4 && !aks && !bks && epi != P5_EPI_ATOMIC && epi != P5_EPI_ACCUM) ? g_f32_split : 0;
   return launch_gemm<T>(g, s);
 }
@@ -431,13 +407,6 @@ static int gemm_nf(hipStream_t s, const void* A, int lda, const void* Bm, int ld
   g.rowss = rowss; g.rowss_invd = 1.0f / (float)K; g.rowss_eps = eps; g.rowss_nt = rowss ? d_model / 64 : 0;
   g.ssq_out = ssq_out; g.ssq_nt = ssq_out ? d_model / 64 : 0;
   return launch_gemm<T>(g, s);
-}
-// decode step: y = rmsnorm(x) W^T with the norm weight folded into Wf and the row statistic taken from `rowss` (sum of squares
-// of the rows of x, K = d_model); optional ssq_out collects the sum of squares of the rows of y for the NEXT norm
-template <class T>
-static int linear_fwd_fused(hipStream_t s, const void* x, int ldx, const T* Wf, void* y, int ldy, int M, int N, int K, int epi,
-                            const void* aux, int ldaux, float alpha, int c_f32, const float* rowss, float eps, float* ssq_out) {
-  return gemm<T>(s, x, ldx, 0, Wf, K, 0, y, ldy, M, N, K, epi, aux, ldaux, alpha, c_f32, no_drop(), rowss, eps, ssq_out);
 }
 // y = x W^T
 template <class T>
@@ -1322,7 +1291,7 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
   const size_t R = (size_t)B * K;
   const int Vp = (c.vocab_size + 63) / 64 * 64;
   // (the encoder's buffers, and the training-layout decoder buffers of the forced-prefix pass: at most P5_FF_MAX positions per user)
-  const int ffcap = g_opt_gen_ff && g_opt_decode_v2 ? (max_len - 2 < P5_FF_MAX ? (max_len - 2 > 0 ? max_len - 2 : 0) : P5_FF_MAX) : 0;
+  const int ffcap = g_opt_gen_ff ? (max_len - 2 < P5_FF_MAX ? (max_len - 2 > 0 ? max_len - 2 : 0) : P5_FF_MAX) : 0;
   const int64_t enc_bytes = layout_ws(e, base, B, L, ffcap, false);
   Bump b{base, (size_t)enc_bytes};
   GenWs tmp;
@@ -1330,21 +1299,19 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
   w.ff_labels = (int64_t*)b.take((size_t)B * (ffcap > 0 ? ffcap : 1) * 8);
   w.ff_nll = (float*)b.take((size_t)B * (ffcap > 0 ? ffcap : 1) * 4);
   {
-    char* kv_all = g_opt_decode_v2 ? (char*)b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz) : nullptr;
-    w.ldkv = g_opt_decode_v2 ? c.n_dec_layers * 2 * in : 2 * in;
+    char* kv_all = (char*)b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz);
+    w.ldkv = c.n_dec_layers * 2 * in;
     for (int i = 0; i < c.n_dec_layers; ++i) {
-      w.kv_cross[i] = g_opt_decode_v2 ? (base ? (void*)(kv_all + (size_t)i * 2 * in * sz) : nullptr) : b.take((size_t)B * L * 2 * in * sz);
+      w.kv_cross[i] = base ? (void*)(kv_all + (size_t)i * 2 * in * sz) : nullptr;
       w.cache[i] = b.take((size_t)max_len * R * 2 * in * sz);
     }
   }
-  w.xa = b.take(R * d * sz); w.xb = b.take(R * d * sz); w.n = b.take(R * d * sz);
   w.qkv = b.take(R * 3 * in * sz); w.q = b.take(R * in * sz); w.o = b.take(R * in * sz);
   w.h = b.take(R * (c.gated_gelu ? 3 : 1) * F * sz); w.hn = b.take(R * d * sz);
   w.x32 = (float*)b.take(R * d * 4);
   // (beyond 64 beams only the wide step runs: no narrow candidate lists, and no [R, V] logits when the head streams)
   const bool narrow = K <= P5_MAX_K;
   w.logits = (float*)b.take(narrow || head_nv(e) == 0 ? R * Vp * 4 : 0);
-  w.ssq = (float*)b.take((size_t)(3 * c.n_dec_layers + 1) * R * 4);
   w.cand = (float*)b.take(R * (size_t)max_c * 4);
   w.cand_key = (int*)b.take(R * (size_t)max_c * 4);
   w.part_m = (float*)b.take(R * (size_t)((c.vocab_size + 15) / 16) * 4);
@@ -1364,7 +1331,7 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
   st.last_tok = (int64_t*)b.take(R * 8);
   st.flags = (int*)b.take(64);
   // latency-shaped decode step: the beam step itself writes the next step's input embeddings into the fp32 residual stream
-  st.x32 = g_opt_decode_v2 ? w.x32 : nullptr;
+  st.x32 = w.x32;
   st.E32 = e->P ? e->P + e->off_E : nullptr;
   st.d = d;
   st.hist = nullptr;
@@ -1384,85 +1351,6 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
     w.wide.fin_src = (int*)b.take(R * 4);
   }
   return (int64_t)((b.off + 255) & ~(size_t)255);
-}
-
-template <class T>
-static const T* Wf(const P5Engine* e, int64_t off) { return (const T*)e->fold + off; }
-
-// One decoder step over R = B*K rows.  With a fold buffer bound (p5_engine_bind_decode_fold) every RMSNorm except the
-// first disappears as a kernel: its weight is folded into the consuming projection (W * ln), its row statistic
-// sum(x^2) is accumulated by the residual epilogue that PRODUCES x (one atomic per 64-column tile row) and applied as a
-// row scale in the epilogue of the consuming GEMM -- 18 of 73 launches fewer for T5-small.
-template <class T>
-static int decode_step(P5Engine* e, GenWs& w, int B, int L, int K, int max_len, hipStream_t s) {
-  const P5Config& c = e->c;
-  const int d = c.d_model, in = e->inner, H = c.n_heads, F = c.d_ff, R = B * K;
-  const bool fused = e->fold != nullptr && g_opt_decode_fused;
-  P5_LAUNCH((p5_embed_fwd_kernel<T>), dim3((R + 3) / 4), dim3(256), 0, s, (T*)w.xa, Wc<T>(e, e->off_E), (const T*)nullptr,
-            (const int64_t*)w.st.last_tok, (const int64_t*)nullptr, R, d, no_drop());
-  P5_TRY(P5_KCHECK());
-  void* x = w.xa; void* y = w.xb;
-  const int Vp = (c.vocab_size + 63) / 64 * 64;
-  int site = 0;                                   // index of the ssq row that holds sum(x^2) of the current x
-  auto ssq_row = [&](int k) { return w.ssq + (size_t)k * R; };
-  if (fused) hipMemsetAsync(w.ssq, 0, (size_t)(3 * c.n_dec_layers + 1) * R * 4, s);
-  for (int i = 0; i < c.n_dec_layers; ++i) {
-    const LayerOff& lo = e->dec[i];
-    // ---- self-attention ----
-    if (fused && i > 0) {
-      P5_TRY(linear_fwd_fused<T>(s, x, d, Wf<T>(e, e->fold_qkv[i]), w.qkv, 3 * in, R, 3 * in, d, P5_EPI_STORE, nullptr, 0, 1.f, 0,
-                                 ssq_row(site), c.eps, nullptr));
-    } else {
-      P5_TRY(rmsnorm_fwd<T>(s, w.n, nullptr, x, e->P + lo.sa.ln, R, d, c.eps, no_drop()));
-      P5_TRY(linear_fwd<T>(s, w.n, d, Wc<T>(e, lo.sa.q), w.qkv, 3 * in, R, 3 * in, d));
-    }
-    P5_LAUNCH((p5_dec_self_attn_kernel<T>), dim3((R * H + 3) / 4), dim3(256), 0, s, (T*)w.o, (const T*)w.qkv, (T*)w.cache[i],
-              (const int*)w.st.anc, (const int*)w.st.anc_next, (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, R, H,
-              (const int*)(w.st.flags + 2), max_len);
-    P5_TRY(P5_KCHECK());
-    ++site;
-    P5_TRY(gemm<T>(s, w.o, in, 0, Wc<T>(e, lo.sa.o), in, 0, y, d, R, d, in, P5_EPI_RESID_DROP, x, d, 1.f, 0, no_drop(), nullptr, 0.f,
-                   fused ? ssq_row(site) : nullptr));
-    std::swap(x, y);
-    // ---- cross-attention ----
-    if (fused) {
-      P5_TRY(linear_fwd_fused<T>(s, x, d, Wf<T>(e, e->fold_q[i]), w.q, in, R, in, d, P5_EPI_STORE, nullptr, 0, 1.f, 0, ssq_row(site), c.eps,
-                                 nullptr));
-    } else {
-      P5_TRY(rmsnorm_fwd<T>(s, w.n, nullptr, x, e->P + lo.ca.ln, R, d, c.eps, no_drop()));
-      P5_TRY(linear_fwd<T>(s, w.n, d, Wc<T>(e, lo.ca.q), w.q, in, R, in, d));
-    }
-    P5_LAUNCH((p5_dec_cross_attn_kernel<T>), dim3((R * H + 3) / 4), dim3(256), 0, s, (T*)w.o, (const T*)w.q, (const T*)w.kv_cross[i],
-              (const int64_t*)w.mask_copy, R, H, K, L);
-    P5_TRY(P5_KCHECK());
-    ++site;
-    P5_TRY(gemm<T>(s, w.o, in, 0, Wc<T>(e, lo.ca.o), in, 0, y, d, R, d, in, P5_EPI_RESID_DROP, x, d, 1.f, 0, no_drop(), nullptr, 0.f,
-                   fused ? ssq_row(site) : nullptr));
-    std::swap(x, y);
-    // ---- feed-forward ----
-    if (!fused) P5_TRY(rmsnorm_fwd<T>(s, w.n, nullptr, x, e->P + lo.ff_ln, R, d, c.eps, no_drop()));
-    const void* ffn_in = fused ? x : w.n;
-    const T* Wi = fused ? Wf<T>(e, e->fold_wi[i]) : Wc<T>(e, lo.wi);
-    const float* rs = fused ? ssq_row(site) : nullptr;
-    if (c.gated_gelu) {
-      T* u = (T*)w.h + (size_t)R * F;
-      P5_TRY(linear_fwd_fused<T>(s, ffn_in, d, Wi, u, 2 * F, R, 2 * F, d, P5_EPI_STORE, nullptr, 0, 1.f, 0, rs, c.eps, nullptr));
-      const size_t n = (size_t)R * F;
-      P5_LAUNCH((p5_gated_gelu_fwd_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (T*)w.h, (const T*)u, R, F, no_drop());
-      P5_TRY(P5_KCHECK());
-    } else {
-      P5_TRY(linear_fwd_fused<T>(s, ffn_in, d, Wi, w.h, F, R, F, d, P5_EPI_RELU_DROP, nullptr, 0, 1.f, 0, rs, c.eps, nullptr));
-    }
-    ++site;
-    P5_TRY(gemm<T>(s, w.h, F, 0, Wc<T>(e, lo.wo), F, 0, y, d, R, d, F, P5_EPI_RESID_DROP, x, d, 1.f, 0, no_drop(), nullptr, 0.f,
-                   fused ? ssq_row(site) : nullptr));
-    std::swap(x, y);
-  }
-  if (fused)      // logits = (norm(x) * d^-0.5) E^T  with  E * final_ln folded
-    return linear_fwd_fused<T>(s, x, d, Wf<T>(e, e->fold_E), w.logits, Vp, R, c.vocab_size, d, P5_EPI_STORE, nullptr, 0,
-                               1.0f / sqrtf((float)d), 1, ssq_row(site), c.eps, nullptr);
-  P5_TRY(rmsnorm_fwd<T>(s, w.hn, nullptr, x, e->P + e->off_dec_fln, R, d, c.eps, no_drop()));
-  return linear_fwd<T>(s, w.hn, d, Wc<T>(e, e->off_E), w.logits, Vp, R, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, 1.0f / sqrtf((float)d), 1);
 }
 
 // ---- latency-shaped decode step (p5_decode2.h) ------------------------------------------------------------
@@ -1526,7 +1414,7 @@ static int skinny(hipStream_t s, int amode, const void* A, int lda, const float*
 // streaming head: rows of E kept in LDS per workgroup (0 = materialised-logits path): the largest of 128/64/32/16 whose tile
 // fits 128 KiB (bf16 d_model 512 -> 128, 768/1024 -> 64; fp32 512 -> 64, 768/1024 -> 32)
 static int head_nv(const P5Engine* e) {
-  if (!g_opt_dec_head || !g_opt_decode_v2) return 0;
+  if (!g_opt_dec_head) return 0;
   // the kernel walks K in units of eight 64-byte chunks (p5_decode2.h): d_model % 256 (bf16) / % 128 (fp32) -- every T5 size;
   // other widths (toy models) take the materialised-logits head
   if (e->c.d_model % (e->c.dtype == 1 ? 256 : 128) != 0) return 0;
@@ -1648,7 +1536,7 @@ static int decode_begin_impl(P5Engine* e, int B, int L, int K, int max_len, cons
   // forced-prefix fast-forward (p5_decode.h): the first F steps as one teacher-forced pass of the training-layout decoder over B x F rows
   P5Forced ff = e->ff_next;
   e->ff_next.n = 0;
-  const int ffcap = g_opt_gen_ff && g_opt_decode_v2 ? (max_len - 2 < P5_FF_MAX ? max_len - 2 : P5_FF_MAX) : 0;
+  const int ffcap = g_opt_gen_ff ? (max_len - 2 < P5_FF_MAX ? max_len - 2 : P5_FF_MAX) : 0;
   if (ff.n > ffcap) ff.n = ffcap > 0 ? ffcap : 0;
   if (ff.n < 2 || roots != nullptr) ff.n = 0;          // (one forced step is what a decode step costs; per-user roots: not a shared prefix)
   const int F = ff.n;
@@ -1665,11 +1553,8 @@ static int decode_begin_impl(P5Engine* e, int B, int L, int K, int max_len, cons
       P5_TRY(P5_KCHECK());
     }
     e->T = 0; e->Md = 0; e->labels = nullptr;
-  } else if (g_opt_decode_v2) {     // K/V projections of every decoder layer in ONE GEMM over the contiguous weight block (build_layout)
+  } else {     // K/V projections of every decoder layer in ONE GEMM over the contiguous weight block (build_layout)
     P5_TRY(linear_fwd<T>(s, e->enc_out, d, Wc<T>(e, e->dec[0].ca.k), w.kv_cross[0], w.ldkv, B * L, c.n_dec_layers * 2 * in, d));
-  } else {
-    for (int i = 0; i < c.n_dec_layers; ++i)
-      P5_TRY(linear_fwd<T>(s, e->enc_out, d, Wc<T>(e, e->dec[i].ca.k), w.kv_cross[i], 2 * in, B * L, 2 * in, d));
   }
   P5_LAUNCH(p5_beam_init_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, w.st, child_off, child_tok, child_node, roots, B, K, max_len,
             c.pad_id);
@@ -1697,8 +1582,7 @@ static int decode_step_body(P5Engine* e, hipStream_t s) {
   const int Vp = (c.vocab_size + 63) / 64 * 64;
   const uint32_t* excl = excl_words > 0 ? w.excluded : nullptr;
   const int* done = w.st.flags + 4;
-  if (g_opt_decode_v2) P5_TRY(decode_step2<T>(e, w, B, L, K, max_len, s));
-  else P5_TRY(decode_step<T>(e, w, B, L, K, max_len, s));
+  P5_TRY(decode_step2<T>(e, w, B, L, K, max_len, s));
   if (head_nv(e) > 0) {
     const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
     P5_LAUNCH((p5_dec_score2_kernel<T>), dim3(R), dim3(256), 0, s, w.row_top_score, w.row_top_c, w.n_cand, w.cand, (const float*)w.part_m,
@@ -1725,8 +1609,7 @@ static int decode_step_wide(P5Engine* e, hipStream_t s) {
   const int Vp = (c.vocab_size + 63) / 64 * 64;
   const uint32_t* excl = excl_words > 0 ? w.excluded : nullptr;
   const int* done = w.st.flags + 4;
-  if (g_opt_decode_v2) P5_TRY(decode_step2<T>(e, w, B, L, K, max_len, s));
-  else P5_TRY(decode_step<T>(e, w, B, L, K, max_len, s));
+  P5_TRY(decode_step2<T>(e, w, B, L, K, max_len, s));
   if (head_nv(e) > 0) {
     const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
     P5_LAUNCH((p5_wide_score2_kernel<T>), dim3(R), dim3(256), 0, s, w.wide.row_key, w.wide.row_n, w.cand, (const float*)w.part_m,
@@ -1760,8 +1643,8 @@ static int decode_step_impl(P5Engine* e, hipStream_t s) {
   memset(&key, 0, sizeof(key));
   key.B = g.B; key.L = g.L; key.K = g.K; key.max_len = g.max_len; key.max_c = g.max_c; key.excl_words = g.excl_words; key.ws = g.ws;
   key.trie = g.child_off; key.trie_tok = g.child_tok; key.trie_node = g.child_node; key.roots = g.roots;
-  key.P = e->P; key.S = e->S; key.sz = (int)sizeof(T); key.fold = e->fold; key.hist = g.w.st.hist; key.wide = g.wide ? 1 : 0;
-  key.fused = g_opt_decode_fused + 2 * g_opt_decode_v2 + 4 * g_opt_dec_fuseq + 8 * g_opt_dec_nb + 4096 * g_opt_dec_kw + (g_opt_dec_cross << 20) +
+  key.P = e->P; key.S = e->S; key.sz = (int)sizeof(T); key.hist = g.w.st.hist; key.wide = g.wide ? 1 : 0;
+  key.fused = 4 * g_opt_dec_fuseq + 8 * g_opt_dec_nb + 4096 * g_opt_dec_kw + (g_opt_dec_cross << 20) +
               (g_opt_dec_head << 23) + (g_opt_dec_head_nv << 24) + ((g.steps0 > 0 ? 1 : 0) << 30) + (g_opt_dec_atomic << 29);     // (forced-prefix pass: the cross K/V live elsewhere)
   bool have_graph = use_graph && e->gen_graph_exec && memcmp(&key, &e->gen_graph_key, sizeof(key)) == 0;
   if (use_graph && !have_graph && g.steps > g.steps0 && !e->gen_graph_failed) {
@@ -2312,31 +2195,6 @@ static int cand_score_impl(P5Engine* e, CandArgs& r, hipStream_t s) {
 // =====================================================================================================
 // C ABI
 // =====================================================================================================
-// out[r, c] = W[r, c] * ln[c]  (fp32 product of the master weights, rounded once to the compute dtype)
-template <class T>
-__global__ __launch_bounds__(256) void p5_fold_norm_kernel(T* __restrict__ out, const float* __restrict__ W, const float* __restrict__ ln,
-                                                          size_t n, int cols) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = from_f<T>(W[i] * ln[i % cols]);
-}
-template <class T>
-static int refresh_fold(P5Engine* e, hipStream_t s) {
-  const P5Config& c = e->c;
-  const int d = c.d_model, in = e->inner;
-  auto fold = [&](int64_t dst, int64_t w_off, int64_t ln_off, int64_t rows) -> int {
-    const size_t n = (size_t)rows * d;
-    P5_LAUNCH((p5_fold_norm_kernel<T>), dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, s, (T*)e->fold + dst,
-              (const float*)(e->P + w_off), (const float*)(e->P + ln_off), n, d);
-    return P5_KCHECK();
-  };
-  for (int i = 0; i < c.n_dec_layers; ++i) {
-    const LayerOff& lo = e->dec[i];
-    P5_TRY(fold(e->fold_qkv[i], lo.sa.q, lo.sa.ln, 3 * in));       // q, k, v are contiguous in the arena
-    P5_TRY(fold(e->fold_q[i], lo.ca.q, lo.ca.ln, in));
-    P5_TRY(fold(e->fold_wi[i], lo.wi, lo.ff_ln, (int64_t)(c.gated_gelu ? 2 : 1) * c.d_ff));
-  }
-  return fold(e->fold_E, e->off_E, e->off_dec_fln, c.vocab_size);
-}
-
 // out[w_off + r*d + c] = bf16(P[w_off + r*d + c] * P[ln_off + c]) for every listed weight: 8 rows per workgroup, one launch for the model
 struct P5FoldTab {
   int n, d;
@@ -2543,7 +2401,6 @@ int p5_set_option(const char* name, int value) {
   else if (!strcmp(name, "gemm_tile")) g_opt_gemm_tile = value;
   else if (!strcmp(name, "gemm_ksdma")) g_opt_gemm_ksdma = value;
   else if (!strcmp(name, "gemm_ring")) g_opt_gemm_ring = value;
-  else if (!strcmp(name, "decode_fused")) g_opt_decode_fused = value;
   else if (!strcmp(name, "gemm_small_ring")) g_opt_gemm_small_ring = value;
   else if (!strcmp(name, "gemm_small_ring_tiles")) g_opt_gemm_small_ring_tiles = value;
   else if (!strcmp(name, "attn_fused")) g_opt_attn_fused = value;
@@ -2555,7 +2412,6 @@ int p5_set_option(const char* name, int value) {
   else if (!strcmp(name, "attn_small")) g_opt_attn_small = value;
   else if (!strcmp(name, "gemm_ring32")) g_opt_gemm_ring32 = value;
   else if (!strcmp(name, "gemm_xcd_rect")) g_opt_gemm_xcd_rect = value;
-  else if (!strcmp(name, "decode_v2")) g_opt_decode_v2 = value;
   else if (!strcmp(name, "dec_nb")) g_opt_dec_nb = value;
   else if (!strcmp(name, "dec_kw")) g_opt_dec_kw = value;
   else if (!strcmp(name, "dec_fuseq")) g_opt_dec_fuseq = value;
@@ -2595,7 +2451,7 @@ int p5_set_option(const char* name, int value) {
   else return fail("p5_set_option: unknown option");
   return 0;
 }
-int p5_abi_version(void) { return 5; }    // 2: p5_op_attn_bwd gained d_rel_scratch / rel_buckets (round 4); 3: p5_generate_verified, p5_backward_staged (round 5); 4: p5_allreduce_range / _sum, p5_verify_row_capacity, range flag in p5_verify_run (round 6); 5: P5GemmProblem gained the T5LayerNorm-backward epilogue fields, p5_op_attn_bwd gained dot_out (round 6)
+int p5_abi_version(void) { return 6; }    // 2: p5_op_attn_bwd gained d_rel_scratch / rel_buckets (round 4); 3: p5_generate_verified, p5_backward_staged (round 5); 4: p5_allreduce_range / _sum, p5_verify_row_capacity, range flag in p5_verify_run (round 6); 5: P5GemmProblem gained the T5LayerNorm-backward epilogue fields, p5_op_attn_bwd gained dot_out (round 6); 6: the decode-fold entries (count / bind / refresh of the folded decoder-weight buffer of the round-1 decode step) were removed
 // ---- in-run kernel profiler (p5_device.h P5Prof) ----
 int p5_profile_begin(void) {
 #ifndef P5_EMU
@@ -2733,12 +2589,6 @@ int p5_engine_bind(P5Engine* e, float* params, float* grads, void* shadow, const
   P5_REQUIRE(lut_half >= 511, "bucket LUT must cover |rel| <= 511");
   e->P = params; e->G = grads; e->S = shadow; e->lut_enc = lut_enc; e->lut_dec = lut_dec; e->lut_half = lut_half; e->rng = rng_state;
   return 0;
-}
-int64_t p5_decode_fold_count(const P5Engine* e) { return e->fold_count; }
-int p5_engine_bind_decode_fold(P5Engine* e, void* buf) { e->fold = buf; return 0; }
-int p5_refresh_decode_fold(P5Engine* e, void* stream) {
-  P5_REQUIRE(e->P && e->fold, "engine / fold buffer not bound");
-  return e->c.dtype == 1 ? refresh_fold<bf16>(e, (hipStream_t)stream) : refresh_fold<float>(e, (hipStream_t)stream);
 }
 
 // buffer layout: [W^T copy: n_params bf16][256-byte aligned descriptor table][256-byte aligned folded copy W diag(ln): n_params bf16]
@@ -3123,7 +2973,6 @@ int p5_decode_begin(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
   P5_REQUIRE(e->P, "engine not bound");
   P5_REQUIRE(K >= 1 && K <= P5_WIDE_MAX_K, "1 <= num_beams <= 4096");
   P5_REQUIRE(max_len >= 2 && max_len <= P5_MAX_LEN, "2 <= max_length <= 128 (P5_MAX_LEN)");
-  P5_REQUIRE(max_len <= 64 || g_opt_decode_v2, "max_length > 64 needs the decode_v2 step (the first-generation self-attention kernel keeps one score per lane)");
   P5_REQUIRE(L >= 1 && L <= 512, "1 <= L <= 512");
   P5_REQUIRE(max_children >= 1, "max_children");
   P5_REQUIRE(e->lut_half >= max_len, "bucket LUT too short");

@@ -123,11 +123,11 @@ class _GenLane:
     """What ONE in-flight generate() call owns: its engines (the bf16 / fp32 search engine and, for verified generation, the fp32 verification
     engine -- all bound to the model's ONE set of parameter arenas), its workspaces, its pinned read-back buffer, its HIP stream.  Lane 0 is
     the model's own engine on the caller's stream; further lanes let several batches be in flight at once (`P5T5Native.map_lanes`)."""
-    __slots__ = ("idx", "engine", "engine_v", "fold_v", "fold_v_dirty", "ws", "ver_hdr", "forced", "stream")
+    __slots__ = ("idx", "engine", "engine_v", "ws", "ver_hdr", "forced", "stream")
 
     def __init__(self, idx, engine, stream=None):
         self.idx, self.engine, self.stream = idx, engine, stream
-        self.engine_v, self.fold_v, self.fold_v_dirty, self.ver_hdr = None, None, True, None
+        self.engine_v, self.ver_hdr = None, None
         self.ws, self.forced = {}, ([], [])
 
 
@@ -139,7 +139,6 @@ class P5T5Native(nn.Module):
     # Data-parallel gradient exchange uses its own communication stream either way (`_engine_backward`).
     use_side_stream = False
     use_transposed_weights = True     # bf16: keep W^T of the layer weights for the data gradients (p5_engine_bind_transposed)
-    fuse_decode_norms = True      # generate(): fold the decoder RMSNorms into the GEMMs around them
     # generate() of a bf16 model: "verified" = the bf16 search (with `verify_extra_beams` more beams) proposes, one fp32 pass decides -- the
     # returned lists and scores are the fp32 search's (include/p5hip.h, csrc/p5_verify.h); "draft" = the plain bf16 search.  An fp32 model
     # always runs the plain (fp32) search.
@@ -188,8 +187,6 @@ class P5T5Native(nn.Module):
         self._staged_ranges, self._bucket16 = None, None
         self._side = None
         self._comm = None
-        self._fold = None
-        self._fold_dirty = True; self._mark_lanes_dirty()
         self._lanes = []            # generation lanes (lane 0 = this model's engine on the caller's stream)
         self._tls = threading.local()
         self._stats_lock = threading.Lock()
@@ -221,7 +218,6 @@ class P5T5Native(nn.Module):
         if self._engine:
             self._lib.p5_engine_destroy(self._engine)
         self._engine = ctypes.c_void_p()
-        self._fold, self._fold_dirty = None, True       # sized by (and bound to) the engine
         self._drop_lanes()          # lane engines (verification engines, extra search engines) are bound to the old arena: rebuilt on demand
         cfg = self._cfg_struct()
         self._be.check(self._lib.p5_engine_create(ctypes.byref(cfg), ctypes.byref(self._engine)), "p5_engine_create")
@@ -261,7 +257,6 @@ class P5T5Native(nn.Module):
             self._copy_in(old_state, strict=False)
         self._bind()
         self._shadow_dirty = True
-        self._fold_dirty = True; self._mark_lanes_dirty()
 
     def _register_dotted(self, name, p):
         parts = name.split(".")
@@ -317,25 +312,10 @@ class P5T5Native(nn.Module):
             self._be.check(self._lib.p5_refresh_shadow(self._engine, self._be.stream_ptr()), "p5_refresh_shadow")
         self._shadow_dirty = False
 
-    def _sync_decode_fold(self):
-        """Decode-step weights with the RMSNorm weights folded in (include/p5hip.h: p5_refresh_decode_fold); rebuilt lazily
-        from the fp32 master parameters whenever they have changed since the last generate()."""
-        if not self.fuse_decode_norms:
-            return
-        if self._fold is None:
-            n = int(self._lib.p5_decode_fold_count(self._engine))
-            self._fold = torch.empty(n, dtype=torch.bfloat16 if self.compute_dtype == 1 else torch.float32, device=self._flat.device)
-            self._be.check(self._lib.p5_engine_bind_decode_fold(self._engine, _ptr(self._fold)), "p5_engine_bind_decode_fold")
-            self._fold_dirty = True; self._mark_lanes_dirty()
-        if self._fold_dirty:
-            self._be.check(self._lib.p5_refresh_decode_fold(self._engine, self._be.stream_ptr()), "p5_refresh_decode_fold")
-            self._fold_dirty = False
-
     def mark_params_updated(self, shadow_fresh: bool = False, copies_fresh: bool = False):
         """Call after writing parameters outside the fused optimizer (which refreshes the bf16 shadow -- and, `copies_fresh`, the transposed
         and norm-folded copies -- itself)."""
         self._shadow_dirty = not shadow_fresh
-        self._fold_dirty = True; self._mark_lanes_dirty()
         self._tr_dirty = not (copies_fresh and shadow_fresh)
 
     def _sync_transposed(self):
@@ -393,7 +373,6 @@ class P5T5Native(nn.Module):
         if strict and (missing or unexpected):
             raise RuntimeError(f"load_state_dict: missing={missing} unexpected={unexpected}")
         self._shadow_dirty = True
-        self._fold_dirty = True; self._mark_lanes_dirty()
         self._tr_dirty = True
         return missing, unexpected
 
@@ -444,7 +423,6 @@ class P5T5Native(nn.Module):
         n = min(old, new_num_tokens)
         self.shared.weight[:n].copy_(old_E[:n])
         self._shadow_dirty = True
-        self._fold_dirty = True; self._mark_lanes_dirty()
         return self.shared
 
     def get_input_embeddings(self):
@@ -656,13 +634,9 @@ class P5T5Native(nn.Module):
                 self._lib.p5_engine_destroy(ln.engine)
         self._lanes = []
 
-    def _mark_lanes_dirty(self):
-        for ln in getattr(self, "_lanes", []):
-            ln.fold_v_dirty = True
-
     def _lane(self, i):
         """lane i, created on demand: lane 0 = the model's own engine; lane i > 0 = a second search engine over the SAME parameter arenas,
-        bf16 shadow, folded decode weights and transposed / norm-folded copies (read-only during generation) with its own HIP stream."""
+        bf16 shadow and transposed / norm-folded copies (read-only during generation) with its own HIP stream."""
         while len(self._lanes) <= i:
             k = len(self._lanes)
             if k == 0:
@@ -673,8 +647,6 @@ class P5T5Native(nn.Module):
             self._be.check(self._lib.p5_engine_create(ctypes.byref(cfg), ctypes.byref(eng)), "p5_engine_create (lane)")
             self._be.check(self._lib.p5_engine_bind(eng, _ptr(self._flat), _ptr(self._grads), _ptr(self._shadow), _ptr(self._lut_enc), _ptr(self._lut_dec),
                                                      self.LUT_HALF, _ptr(self._rng)), "p5_engine_bind (lane)")
-            if self._fold is not None:
-                self._be.check(self._lib.p5_engine_bind_decode_fold(eng, _ptr(self._fold)), "p5_engine_bind_decode_fold (lane)")
             if self._shadow_t is not None:
                 self._be.check(self._lib.p5_engine_bind_transposed(eng, _ptr(self._shadow_t), self._be.stream_ptr()), "p5_engine_bind_transposed (lane)")
             self._lanes.append(_GenLane(k, eng, torch.cuda.Stream(device=self._be.device) if self._flat.is_cuda else None))
@@ -707,7 +679,6 @@ class P5T5Native(nn.Module):
         # parameter copies the searches read are refreshed HERE, once, on the caller's stream: no lane does it under another lane's feet
         self._sync_shadow()
         self._sync_transposed()
-        self._sync_decode_fold()
         pool = [self._lane(i + 1) for i in range(lanes)]          # lanes 1 .. n; lane 0 stays with the calling thread's own generate() calls
         main = torch.cuda.current_stream()
         for ln in pool:
@@ -773,7 +744,6 @@ class P5T5Native(nn.Module):
             roots_t = torch.as_tensor(roots, dtype=torch.int32, device=dev).contiguous()
         self._sync_shadow()
         self._sync_transposed()     # (also refreshes the folded copy W diag(ln) the encoder pass multiplies the raw residual stream with)
-        self._sync_decode_fold()
         maxc = max(1, trie.max_children)
         excl_t, excl_words = None, 0
         if excluded is not None:
@@ -1243,19 +1213,7 @@ class P5T5Native(nn.Module):
     def _search_fp32(self, *args):
         """The plain fp32 beam search on this lane's verification engine (exact fp32 MFMAs over the master arena): the last resort of the
         verified mode and what a verified call wider than VERIFY_MAX_K beams runs."""
-        lib, dev, sp = self._lib, self._be.device, self._be.stream_ptr()
-        lane = self._cur_lane()
-        ev = self._verify_engine(lane)
-        ftok, fnode = lane.forced
-        if self.fuse_decode_norms:
-            if lane.fold_v is None:
-                n = int(lib.p5_decode_fold_count(ev))
-                lane.fold_v = torch.empty(n, dtype=torch.float32, device=dev)
-                self._be.check(lib.p5_engine_bind_decode_fold(ev, _ptr(lane.fold_v)), "p5_engine_bind_decode_fold (verify)")
-                lane.fold_v_dirty = True
-            if lane.fold_v_dirty:
-                self._be.check(lib.p5_refresh_decode_fold(ev, sp), "p5_refresh_decode_fold (verify)")
-                lane.fold_v_dirty = False
+        ev = self._verify_engine(self._cur_lane())
         return self._search(ev, "gen_v", *args)
 
     def time_generate(self, enable: bool = True):

@@ -2265,7 +2265,7 @@ def stepwise_decode_case(be, ocfg, B, L, K, max_len, n_items, dtype="fp32", seed
     i64 = lambda t: t.to(device=dev_, dtype=torch.int64).contiguous()      # noqa: E731
     ids_d, ww_d, mask_d = i64(ids), i64(ww), i64(mask)
     lib, eng = m._lib, m._engine
-    m._sync_shadow(); m._sync_decode_fold()
+    m._sync_shadow()
     nb = lib.p5_generate_workspace_bytes(eng, B, L, K, ml, max(1, ct.max_children), 0)
     ws = m._workspace(nb, "_gen_ws")
     be.check(lib.p5_decode_begin(eng, P(ids_d), P(ww_d), P(mask_d), B, L, K, ml, P(off), P(tok), P(nxt), None, None, 0, max(1, ct.max_children),

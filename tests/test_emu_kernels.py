@@ -284,15 +284,6 @@ def test_generate_ids_longer_than_64_tokens(emu):
     cases.generate_case(emu, O.T5Cfg.named("tiny"), 2, 12, 3, 100, 12, id_len=(66, 80), seed=3)
 
 
-def test_generate_unfused_decode_norms(emu):
-    """the decode step with separate RMSNorm kernels (p5_set_option decode_fused 0) -- the default folds them into the GEMMs."""
-    try:
-        emu.check(emu.lib.p5_set_option(b"decode_fused", 0), "set_option")
-        cases.generate_case(emu, O.T5Cfg.named("tiny"), 3, 20, 5, 12, 40)
-    finally:
-        emu.lib.p5_set_option(b"decode_fused", 1)
-
-
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_generate_forced_prefix_fast_forward(emu, dtype):
     """Item ids that share their first four tokens ("<dataset> item _ ..."): the four forced steps run as ONE teacher-forced decoder pass

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 def test_native_library_loaded(hip):
     assert hip.lib.p5_is_emulator() == 0
-    assert hip.lib.p5_abi_version() == 5
+    assert hip.lib.p5_abi_version() == 6
 
 
 def test_tr_probe(hip):

@@ -17,7 +17,7 @@ ALLOWED = {
     "p5_gemm4.h": ["atomicAdd(cp + r, v[r])", "atomicAdd((float*)g.C + ci + r, v[r])", "atomicAdd(cp + e, v[e])", "atomicAdd(g.ssq_out + row, ss)"],
     "p5_gemm5.h": ["atomicAdd(cp + r, v[r])", "atomicAdd((float*)g.C + ci + r, v[r])", "atomicAdd(cp + e, v[e])", "atomicAdd(g.ssq_out + row, ss)"],
     # (GEMM epilogues: P5_EPI_ATOMIC is issued by the engine with ONE split only -- each element receives a single add per backward --
-    #  or with c_split_stride > 0, which stores; the scalar ssq form is the first-generation decode step's, generation only)
+    #  or with c_split_stride > 0, which stores; the scalar ssq form is reachable through p5_op_gemm only)
     "p5_decode2.h": ["atomicAdd((float*)g.C + ci, v)"],        # decode step of rounds 2-4 (K-split workgroups adding into the residual stream): only with p5_set_option("dec_atomic", 1)
 }
 

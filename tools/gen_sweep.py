@@ -15,7 +15,7 @@ n = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 ids, ww, mask, _, _ = bench.synth_batch(gB, 128, 8, be.device, 500)
 kw = dict(input_ids=ids, attention_mask=mask, whole_word_ids=ww, max_length=30, prefix_allowed_tokens_fn=fn, num_beams=10, num_return_sequences=10,
           output_scores=True, return_dict_in_generate=True)
-DEFAULT = dict(decode_v2=1, dec_cross=3, dec_head=1, dec_nb=0, dec_head_nv=0, dec_fuseq=1, dec_kw=0)
+DEFAULT = dict(dec_cross=3, dec_head=1, dec_nb=0, dec_head_nv=0, dec_fuseq=1, dec_kw=0)
 def run(**opts):
     cfgd = dict(DEFAULT); cfgd.update(opts)
     for k, v in cfgd.items():
@@ -45,7 +45,6 @@ agree(run(dec_cross=2), "scalar cross-attention, streaming head")
 agree(run(dec_head=0), "MFMA cross-attention, materialised logits")
 run(dec_head_nv=64)
 run(dec_fuseq=0)
-run(decode_v2=0, dec_head=0)
 run()
 kw32 = dict(kw)
 torch.cuda.synchronize(); t0 = time.perf_counter()
