@@ -275,6 +275,31 @@ int p5_cand_score(P5Engine* e, const int64_t* input_ids, const int64_t* whole_wo
                   const int* row_tok, const int* row_depth, const int* row_anc, int max_depth, const int* candidates, int C, const int* item_rows,
                   const int64_t* item_tokens, int n_items, int path_len, int token_stride, int rows_per_user, int top_n, int exact_products,
                   float* out_scores, int* out_order, int* out_index, float* out_score, int* out_flagged, void* ws, int64_t ws_bytes, void* stream);
+/* ---- certified pruned ranking: the bf16 pass proposes, an fp32 pass over the proposed prefixes decides (openp5_amd/csrc/p5_prune.h) ----
+ * For a bf16 model: the top_n of p5_rank_items on the fp32 engine, at a cost that follows the prefixes within reach of the top_n-th item.
+ * Besides p5_rank_items' trie / plan / path arrays (rows_total = its rows_per_user): row_edge int32 [rows_total] the edge leading into a
+ * row (-1 for row 0), row_lmax int32 [rows_total] the largest token count of an item below the row, edge_row int32 [n_edges] the row of
+ * an edge's child (-1 for a leaf) -- CompiledTrie.prune_plan.
+ *   p5_prune_propose (the bf16 engine): p5_rank_items in `rank_ws` (out_index / out_score / out_flagged: its results), then per user the
+ *     rows r with P(a) / row_lmax[a] >= out_score[top_n - 1] - slack for r and every ancestor a, ascending, into the head of `prune_ws`:
+ *     int32 hdr[0] = the largest row count at byte 0 (the ONE integer the host reads), int32 n_rows[B] at byte 256, int32
+ *     sel[B][rows_total] at byte 256 + (4 B rounded up to 256).  p5_prune_workspace_bytes(.., rows_per_user = 0, ..) = the head alone.
+ *   p5_prune_decide (the fp32 engine; `prune_ws` sized for rows_per_user >= hdr[0], the head where propose left it): the decoder over
+ *     sel, the log-probability of every child edge of every sel row, the top_n of the items scored in full (excluded_items applied), and
+ *     the certificate: out_flagged[b] = 0 only when every item that was not scored is proven to score below out_score[b][top_n - 1] by
+ *     more than `margin`.  A flagged user's outputs must not be used: rank that user with p5_rank_items.
+ * Limits as p5_rank_items.  Both calls enqueue on `stream` only. */
+int64_t p5_prune_workspace_bytes(const P5Engine* e, int B, int L, int rows_total, int rows_per_user, int64_t n_edges, int n_items, int top_n);
+int p5_prune_propose(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                     const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                     const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* item_edges, int n_items,
+                     int path_len, const uint32_t* excluded_items, int top_n, float slack, int* out_index, float* out_score, int* out_flagged,
+                     void* rank_ws, int64_t rank_ws_bytes, void* prune_ws, int64_t prune_ws_bytes, void* stream);
+int p5_prune_decide(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                    const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                    const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* edge_row,
+                    const int* item_edges, int n_items, int path_len, const uint32_t* excluded_items, int top_n, int rows_per_user, float margin,
+                    int* out_index, float* out_score, int* out_flagged, void* prune_ws, int64_t prune_ws_bytes, void* stream);
 /* Device-time brackets of p5_generate for benchmarks: p5_generate_timing(e, 1, NULL, NULL) arms it; after a p5_generate call,
  * p5_generate_timing(e, enable, &encode_ms, &decode_ms) WAITS for that call to finish and returns the time between its start and
  * its first decode step (encoder pass + cross-attention K/V projection + beam state) and the time of the decode loop itself. */

@@ -24,6 +24,7 @@
 #include "p5_verify.h"
 #include "p5_rank.h"
 #include "p5_cand.h"
+#include "p5_prune.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -1933,6 +1934,12 @@ struct RankWs {
   int G, S;              // first selection stage: G workgroups per user over slices of S items
 };
 #define P5_RANK_LOGITS_BYTES ((size_t)256 << 20)      // the [rows, V] logits of one head chunk never exceed this
+static void rank_select_grid(int n_items, int top_n, int& G, int& S) {      // first selection stage: G workgroups per user over slices of S items
+  const int slice = top_n * 4 > 1024 ? top_n * 4 : 1024;
+  G = (n_items + slice - 1) / slice;
+  G = G < 1 ? 1 : (G > 64 ? 64 : G);
+  S = (n_items + G - 1) / G;
+}
 static int64_t layout_rank(P5Engine* e, char* base, int B, int L, int rows, int64_t n_edges, int n_items, int top_n, RankWs* out) {
   const P5Config& c = e->c;
   const size_t sz = c.dtype == 1 ? 2 : 4;
@@ -1963,12 +1970,50 @@ static int64_t layout_rank(P5Engine* e, char* base, int B, int L, int rows, int6
   w.head = (float*)b.take(head_bytes_l > head_bytes_s ? head_bytes_l : head_bytes_s);
   w.edge_lp = (float*)b.take((size_t)B * n_edges * 4);
   w.scores = (float*)b.take((size_t)B * n_items * 4);
-  const int slice = top_n * 4 > 1024 ? top_n * 4 : 1024;
-  w.G = (n_items + slice - 1) / slice;
-  w.G = w.G < 1 ? 1 : (w.G > 64 ? 64 : w.G);
-  w.S = (n_items + w.G - 1) / w.G;
+  rank_select_grid(n_items, top_n, w.G, w.S);
   w.part = (unsigned long long*)b.take((size_t)B * w.G * top_n * 8);
   return (int64_t)((b.off + 255) & ~(size_t)255);
+}
+
+// tied head + the log-probability of every child edge of every row of a pass, in row chunks (the buffers of this phase do not grow with
+// the catalogue).  rs.sel == nullptr: the pass holds every plan row (rank_items_impl); else row i of user b is plan row sel[b][i]
+// (prune_decide_impl).  head: the partials of the streaming head or the logits of one chunk.
+template <class T>
+static int rank_edges(P5Engine* e, float* edge_lp, int64_t n_edges, const void* hn_all, float* head, int HC_stream, int HC_logits, int R, const P5RankPlan& pl,
+                      P5RankSel rs, const int* child_off, const int* child_tok, int split_on, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int d = c.d_model;
+  const int Vp = (c.vocab_size + 63) / 64 * 64;
+  const float alpha = 1.0f / sqrtf((float)d);
+  const bool streaming = head_nv(e) > 0 && !split_on;     // (with split products the head is a throughput GEMM into logits, as in verify_run_impl)
+  const int HC = streaming ? HC_stream : HC_logits;
+  for (int g0 = 0; g0 < R; g0 += HC) {
+    const int nr = R - g0 < HC ? R - g0 : HC;
+    const T* hn = (const T*)hn_all + (size_t)g0 * d;
+    if (streaming) {
+      const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
+      float* part_m = head; float* part_s = head + (size_t)HC_stream * nt;
+      P5_TRY(launch_head_lse<T>(e, part_m, part_s, hn, nr, nullptr, s));
+      P5_LAUNCH((p5_rank_score_kernel<T>), dim3(nr), dim3(256), 0, s, edge_lp, (long long)n_edges, (const float*)part_m, (const float*)part_s, nt,
+                (const T*)hn_all, Wc<T>(e, e->off_E), d, alpha, pl, g0, child_off, child_tok, rs);
+    } else {
+      P5_TRY(linear_fwd<T>(s, hn, d, Wc<T>(e, e->off_E), head, Vp, nr, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
+      P5_LAUNCH(p5_rank_score_logits_kernel, dim3(nr), dim3(256), 0, s, edge_lp, (long long)n_edges, (const float*)head, Vp, c.vocab_size, pl, g0,
+                child_off, child_tok, rs);
+    }
+    P5_TRY(P5_KCHECK());
+  }
+  return 0;
+}
+// item scores and the per-user top N
+static int rank_select(float* scores, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len, const uint32_t* excluded,
+                       unsigned long long* part, int G, int S, int B, int top_n, int* out_index, float* out_score, hipStream_t s) {
+  P5_LAUNCH(p5_rank_items_kernel, dim3((n_items + 255) / 256, B), dim3(256), 0, s, scores, edge_lp, (long long)n_edges, item_edges, n_items, path_len);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_rank_select_part_kernel, dim3(G, B), dim3(256), 0, s, part, (const float*)scores, excluded, (n_items + 31) / 32, n_items, S, top_n);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_rank_select_kernel, dim3(B), dim3(256), 0, s, out_index, out_score, (const unsigned long long*)part, G, top_n);
+  return P5_KCHECK();
 }
 
 struct RankArgs {
@@ -1995,7 +2040,6 @@ static int rank_items_impl(P5Engine* e, RankArgs& r, hipStream_t s) {
   P5RankPlan pl = r.pl;
   pl.B = B; pl.CQ = w.CQ; pl.nchunk = w.nchunk;
   const int R = B * w.CQ * w.nchunk;
-  const int Vp = (c.vocab_size + 63) / 64 * 64;
   // encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl)
   layout_ws(e, r.ws, B, r.L, 0, false);
   e->B = B; e->L = r.L; e->T = 0; e->M = B * r.L; e->Md = 0; e->training = 0;
@@ -2018,36 +2062,12 @@ static int rank_items_impl(P5Engine* e, RankArgs& r, hipStream_t s) {
     P5_LAUNCH((p5_rank_range_kernel<T>), dim3(B, w.nchunk), dim3(256), 0, s, r.out_flagged, (const T*)w.hn, B, w.CQ, d);
     P5_TRY(P5_KCHECK());
   }
-  // tied head + the log-probability of every edge, in row chunks (the buffers of this phase do not grow with the catalogue)
+  // tied head + the log-probability of every edge
   hipMemsetAsync(w.edge_lp, 0, (size_t)B * r.n_edges * 4, s);
-  const float alpha = 1.0f / sqrtf((float)d);
-  const bool streaming = head_nv(e) > 0 && !split_on;     // (with split products the head is a throughput GEMM into logits, as in verify_run_impl)
-  const int HC = streaming ? w.HC_stream : w.HC_logits;
-  for (int g0 = 0; g0 < R; g0 += HC) {
-    const int nr = R - g0 < HC ? R - g0 : HC;
-    const T* hn = (const T*)w.hn + (size_t)g0 * d;
-    if (streaming) {
-      const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
-      float* part_m = w.head; float* part_s = w.head + (size_t)w.HC_stream * nt;
-      P5_TRY(launch_head_lse<T>(e, part_m, part_s, hn, nr, nullptr, s));
-      P5_LAUNCH((p5_rank_score_kernel<T>), dim3(nr), dim3(256), 0, s, w.edge_lp, (long long)r.n_edges, (const float*)part_m, (const float*)part_s, nt,
-                (const T*)w.hn, Wc<T>(e, e->off_E), d, alpha, pl, g0, r.child_off, r.child_tok);
-    } else {
-      P5_TRY(linear_fwd<T>(s, hn, d, Wc<T>(e, e->off_E), w.head, Vp, nr, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
-      P5_LAUNCH(p5_rank_score_logits_kernel, dim3(nr), dim3(256), 0, s, w.edge_lp, (long long)r.n_edges, (const float*)w.head, Vp, c.vocab_size, pl, g0,
-                r.child_off, r.child_tok);
-    }
-    P5_TRY(P5_KCHECK());
-  }
+  P5_TRY((rank_edges<T>(e, w.edge_lp, r.n_edges, w.hn, w.head, w.HC_stream, w.HC_logits, R, pl, P5RankSel{nullptr, nullptr, 0}, r.child_off, r.child_tok,
+                        split_on, s)));
   // item scores and the per-user top N
-  P5_LAUNCH(p5_rank_items_kernel, dim3((r.n_items + 255) / 256, B), dim3(256), 0, s, w.scores, (const float*)w.edge_lp, (long long)r.n_edges, r.item_edges,
-            r.n_items, r.path_len);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_rank_select_part_kernel, dim3(w.G, B), dim3(256), 0, s, w.part, (const float*)w.scores, r.excluded, (r.n_items + 31) / 32, r.n_items, w.S,
-            r.top_n);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_rank_select_kernel, dim3(B), dim3(256), 0, s, r.out_index, r.out_score, (const unsigned long long*)w.part, w.G, r.top_n);
-  P5_TRY(P5_KCHECK());
+  P5_TRY(rank_select(w.scores, w.edge_lp, r.n_edges, r.item_edges, r.n_items, r.path_len, r.excluded, w.part, w.G, w.S, B, r.top_n, r.out_index, r.out_score, s));
   if (r.out_scores_all) hipMemcpyAsync(r.out_scores_all, w.scores, (size_t)B * r.n_items * 4, hipMemcpyDeviceToDevice, s);
   return 0;
 }
@@ -2066,10 +2086,8 @@ struct CandWs {
   float *lse, *head, *row_lse, *scores;
   int CQ, nchunk, HC_stream, HC_logits;
 };
+static Bump layout_sel_pass(P5Engine* e, char* pass, int B, int L, int rows, CandWs& w);
 static int64_t layout_cand(P5Engine* e, char* base, int B, int L, int C, int path_len, int rows, CandWs* out) {
-  const P5Config& c = e->c;
-  const size_t sz = c.dtype == 1 ? 2 : 4;
-  const int d = c.d_model, in = e->inner, F = c.d_ff, H = c.n_heads;
   CandWs tmp;
   CandWs& w = out ? *out : tmp;
   Bump p{base, 0};
@@ -2082,11 +2100,22 @@ static int64_t layout_cand(P5Engine* e, char* base, int B, int L, int C, int pat
   w.keys = (unsigned long long*)p.take((size_t)B * w.P * 8);
   w.plan_bytes = (p.off + 255) & ~(size_t)255;
   if (rows <= 0) return (int64_t)w.plan_bytes;
+  Bump b = layout_sel_pass(e, base ? base + w.plan_bytes : nullptr, B, L, rows, w);
+  const size_t R = (size_t)B * w.CQ * w.nchunk;
+  w.row_lse = (float*)b.take(R * 4);
+  w.scores = (float*)b.take((size_t)B * C * 4);
+  return (int64_t)(w.plan_bytes + ((b.off + 255) & ~(size_t)255));
+}
+// the buffers of a pass over per-user subsets of the plan's rows (encoder, K/V, decoder_rows_pass, head chunk) behind a plan of
+// w.plan_bytes: shared by layout_cand and layout_prune
+static Bump layout_sel_pass(P5Engine* e, char* pass, int B, int L, int rows, CandWs& w) {
+  const P5Config& c = e->c;
+  const size_t sz = c.dtype == 1 ? 2 : 4;
+  const int d = c.d_model, in = e->inner, F = c.d_ff, H = c.n_heads;
   w.nchunk = (rows + 511) / 512;
   w.CQ = ((rows + w.nchunk - 1) / w.nchunk + 15) / 16 * 16;
   const size_t R = (size_t)B * w.CQ * w.nchunk;
   const int Vp = (c.vocab_size + 63) / 64 * 64;
-  char* pass = base ? base + w.plan_bytes : nullptr;
   const int64_t enc_bytes = layout_ws(e, pass, B, L, 0, false);
   Bump b{pass, (size_t)enc_bytes};
   w.kv_all = b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz);
@@ -2103,9 +2132,7 @@ static int64_t layout_cand(P5Engine* e, char* base, int B, int L, int C, int pat
   w.HC_stream = (int)(R < 8192 ? R : 8192);
   const size_t head_bytes_l = (size_t)w.HC_logits * Vp * 4, head_bytes_s = 2 * (size_t)w.HC_stream * nt * 4;
   w.head = (float*)b.take(head_bytes_l > head_bytes_s ? head_bytes_l : head_bytes_s);
-  w.row_lse = (float*)b.take(R * 4);
-  w.scores = (float*)b.take((size_t)B * C * 4);
-  return (int64_t)(w.plan_bytes + ((b.off + 255) & ~(size_t)255));
+  return b;
 }
 
 static int cand_plan_impl(P5Engine* e, const int* cand, int B, int C, const int* item_rows, int n_items, int path_len, char* ws, hipStream_t s) {
@@ -2115,6 +2142,39 @@ static int cand_plan_impl(P5Engine* e, const int* cand, int B, int C, const int*
   P5_TRY(P5_KCHECK());
   P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, B);
   return P5_KCHECK();
+}
+
+// encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl; `pass`: where its buffers start, behind the plan's) + the
+// decoder over every user's own rows pl.sel + the range guard of the split-product pass into out_flagged (cleared first).  Shared by
+// cand_score_impl and prune_decide_impl.
+template <class T>
+static int sel_rows_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids,
+                         const int64_t* attention_mask, int L, int split_on, int* out_flagged, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int d = c.d_model, in = e->inner, H = c.n_heads, B = pl.g.B;
+  const int R = B * w.CQ * w.nchunk;
+  layout_ws(e, pass, B, L, 0, false);
+  e->B = B; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
+  e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
+  P5_TRY(encoder_fwd<T>(e, s));
+  P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * L, c.n_dec_layers * 2 * in, c.d_model));
+  // the decoder over every user's own prefixes
+  P5_LAUNCH(p5_cand_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, w.ids, pl, c.pad_id);
+  P5_TRY(P5_KCHECK());
+  RowsPassBufs pb;
+  pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
+  auto tree_attn = [&](T* o, const T* qkv) -> int {
+    P5_LAUNCH((p5_cand_tree_attn_kernel<T>), dim3((unsigned)(((long long)R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, (const float*)(e->P + e->off_dec_rel),
+              e->lut_dec, e->lut_half, H);
+    return P5_KCHECK();
+  };
+  P5_TRY((decoder_rows_pass<T>(e, pb, B, w.CQ, w.nchunk, L, tree_attn, s)));
+  hipMemsetAsync(out_flagged, 0, (size_t)B * 4, s);
+  if (split_on) {     // (ordered behind the clear on this stream)
+    P5_LAUNCH((p5_rank_range_kernel<T>), dim3(B, w.nchunk), dim3(256), 0, s, out_flagged, (const T*)w.hn, B, w.CQ, d);
+    P5_TRY(P5_KCHECK());
+  }
+  return 0;
 }
 
 struct CandArgs {
@@ -2135,35 +2195,14 @@ static int cand_score_impl(P5Engine* e, CandArgs& r, hipStream_t s) {
   SplitScope split(split_on);
   CandWs w;
   layout_cand(e, r.ws, r.B, r.L, r.C, r.path_len, r.rows, &w);
-  const int d = c.d_model, in = e->inner, H = c.n_heads, B = r.B;
+  const int d = c.d_model, B = r.B;
   P5CandPlan pl;
   pl.g.row_tok = r.row_tok; pl.g.row_depth = r.row_depth; pl.g.row_node = nullptr; pl.g.anc = r.row_anc;
   pl.g.rows = r.rows; pl.g.max_depth = r.max_depth; pl.g.B = B; pl.g.CQ = w.CQ; pl.g.nchunk = w.nchunk;
   pl.sel = w.sel; pl.n_rows = w.n_rows; pl.cap = w.cap;
   const int R = B * w.CQ * w.nchunk;
   const int Vp = (c.vocab_size + 63) / 64 * 64;
-  // encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl); its buffers follow the plan's
-  layout_ws(e, r.ws + w.plan_bytes, B, r.L, 0, false);
-  e->B = B; e->L = r.L; e->T = 0; e->M = B * r.L; e->Md = 0; e->training = 0;
-  e->ids = r.input_ids; e->ww = r.whole_word_ids; e->mask = r.attention_mask; e->labels = nullptr;
-  P5_TRY(encoder_fwd<T>(e, s));
-  P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * r.L, c.n_dec_layers * 2 * in, c.d_model));
-  // the decoder over every user's own prefixes
-  P5_LAUNCH(p5_cand_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, w.ids, pl, c.pad_id);
-  P5_TRY(P5_KCHECK());
-  RowsPassBufs pb;
-  pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
-  auto tree_attn = [&](T* o, const T* qkv) -> int {
-    P5_LAUNCH((p5_cand_tree_attn_kernel<T>), dim3((unsigned)(((long long)R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, (const float*)(e->P + e->off_dec_rel),
-              e->lut_dec, e->lut_half, H);
-    return P5_KCHECK();
-  };
-  P5_TRY((decoder_rows_pass<T>(e, pb, B, w.CQ, w.nchunk, r.L, tree_attn, s)));
-  hipMemsetAsync(r.out_flagged, 0, (size_t)B * 4, s);
-  if (split_on) {     // (ordered behind the clear on this stream)
-    P5_LAUNCH((p5_rank_range_kernel<T>), dim3(B, w.nchunk), dim3(256), 0, s, r.out_flagged, (const T*)w.hn, B, w.CQ, d);
-    P5_TRY(P5_KCHECK());
-  }
+  P5_TRY((sel_rows_pass<T>(e, w, pl, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.L, split_on, r.out_flagged, s)));
   // tied head: the log-sum-exp of every row, in row chunks (the two routes of rank_items_impl, chosen by the same condition)
   const float alpha = 1.0f / sqrtf((float)d);
   const bool streaming = head_nv(e) > 0 && !split_on;
@@ -2190,6 +2229,87 @@ static int cand_score_impl(P5Engine* e, CandArgs& r, hipStream_t s) {
   P5_TRY(P5_KCHECK());
   hipMemcpyAsync(r.out_scores, w.scores, (size_t)B * r.C * 4, hipMemcpyDeviceToDevice, s);
   return 0;
+}
+
+// ---- certified pruned ranking (p5_prune.h).  PROPOSE on the bf16 engine: the unchanged rank_items_impl pass in its own workspace, then
+// the rows worth fp32 numbers into the head of the prune workspace (hdr | n_rows [B] | sel [B][rows of the plan]: the plan protocol of
+// p5_cand_plan, the head depends on B and the plan's row count alone, so the engine that decides finds it where this one left it).
+// DECIDE on the fp32 engine: sel_rows_pass over sel -> rank_edges through sel -> mask -> rank_select -> certificate. ----
+struct PruneWs : CandWs {
+  float* edge_lp;
+  uint32_t* excl;
+  unsigned long long* part;
+  int G, S;
+};
+static int64_t layout_prune(P5Engine* e, char* base, int B, int L, int rows_total, int rows, int64_t n_edges, int n_items, int top_n, PruneWs* out) {
+  PruneWs tmp;
+  PruneWs& w = out ? *out : tmp;
+  Bump p{base, 0};
+  w.cap = rows_total;
+  w.P = 0; w.keys = nullptr; w.row_lse = nullptr;
+  w.hdr = (int*)p.take(64);
+  w.n_rows = (int*)p.take((size_t)B * 4);
+  w.sel = (int*)p.take((size_t)B * w.cap * 4);
+  w.plan_bytes = (p.off + 255) & ~(size_t)255;
+  if (rows <= 0) return (int64_t)w.plan_bytes;
+  Bump b = layout_sel_pass(e, base ? base + w.plan_bytes : nullptr, B, L, rows, w);
+  w.edge_lp = (float*)b.take((size_t)B * n_edges * 4);
+  w.scores = (float*)b.take((size_t)B * n_items * 4);
+  w.excl = (uint32_t*)b.take((size_t)B * ((n_items + 31) / 32) * 4);
+  rank_select_grid(n_items, top_n, w.G, w.S);
+  w.part = (unsigned long long*)b.take((size_t)B * w.G * top_n * 8);
+  return (int64_t)(w.plan_bytes + ((b.off + 255) & ~(size_t)255));
+}
+
+template <class T>
+static int prune_propose_impl(P5Engine* e, RankArgs& r, const int* row_edge, const int* row_lmax, float slack, char* prune_ws, hipStream_t s) {
+  P5_TRY(rank_items_impl<T>(e, r, s));
+  RankWs w;
+  layout_rank(e, r.ws, r.B, r.L, r.pl.rows, r.n_edges, r.n_items, r.top_n, &w);
+  PruneWs p;
+  layout_prune(e, prune_ws, r.B, 1, r.pl.rows, 0, r.n_edges, r.n_items, r.top_n, &p);
+  P5_LAUNCH(p5_prune_propose_kernel, dim3(r.B), dim3(256), 0, s, p.sel, p.n_rows, (const float*)w.edge_lp, (long long)r.n_edges, (const float*)r.out_score, r.top_n,
+            r.pl, row_edge, row_lmax, slack);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, p.hdr, (const int*)p.n_rows, r.B);
+  return P5_KCHECK();
+}
+
+struct PruneArgs {
+  RankArgs r;               // (r.pl: the trie's plan; r.ws: the prune workspace; r.exact unused: a user out of range falls back)
+  const int *row_edge, *row_lmax, *edge_row;
+  int rows;                 // rows per user of the pass (>= the header word)
+  float margin;
+};
+template <class T>
+static int prune_decide_impl(P5Engine* e, PruneArgs& a, hipStream_t s) {
+  RankArgs& r = a.r;
+  const int split_on = sizeof(T) == 4 ? g_opt_verify_split : 0;
+  SplitScope split(split_on);
+  PruneWs w;
+  layout_prune(e, r.ws, r.B, r.L, r.pl.rows, a.rows, r.n_edges, r.n_items, r.top_n, &w);
+  const int B = r.B;
+  P5CandPlan pl;
+  pl.g = r.pl;
+  pl.g.rows = a.rows; pl.g.B = B; pl.g.CQ = w.CQ; pl.g.nchunk = w.nchunk;
+  pl.sel = w.sel; pl.n_rows = w.n_rows; pl.cap = w.cap;
+  const int R = B * w.CQ * w.nchunk;
+  P5_TRY((sel_rows_pass<T>(e, w, pl, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.L, split_on, r.out_flagged, s)));
+  // the log-probability of every child edge of every sel row; every other edge keeps the sentinel
+  const size_t ne = (size_t)B * r.n_edges;
+  P5_LAUNCH(p5_prune_fill_kernel, dim3((unsigned)((ne + 255) / 256 > 4096 ? 4096 : (ne + 255) / 256)), dim3(256), 0, s, w.edge_lp, ne, P5_PRUNE_SENTINEL);
+  P5_TRY(P5_KCHECK());
+  P5_TRY((rank_edges<T>(e, w.edge_lp, r.n_edges, w.hn, w.head, w.HC_stream, w.HC_logits, R, pl.g, P5RankSel{w.sel, w.n_rows, w.cap}, r.child_off, r.child_tok,
+                        split_on, s)));
+  // items whose path was not scored in full join the user's exclusion bitmap; then the selection of rank_items_impl
+  const int words = (r.n_items + 31) / 32;
+  P5_LAUNCH(p5_prune_mask_kernel, dim3((words + 255) / 256, B), dim3(256), 0, s, w.excl, r.excluded, words, (const float*)w.edge_lp, (long long)r.n_edges,
+            r.item_edges, r.n_items, r.path_len);
+  P5_TRY(P5_KCHECK());
+  P5_TRY(rank_select(w.scores, w.edge_lp, r.n_edges, r.item_edges, r.n_items, r.path_len, w.excl, w.part, w.G, w.S, B, r.top_n, r.out_index, r.out_score, s));
+  P5_LAUNCH(p5_prune_certify_kernel, dim3((w.CQ * w.nchunk + 255) / 256, B), dim3(256), 0, s, r.out_flagged, (const float*)w.edge_lp, (long long)r.n_edges, pl,
+            a.row_edge, a.edge_row, a.row_lmax, r.child_off, (const int*)r.out_index, (const float*)r.out_score, r.top_n, a.margin);
+  return P5_KCHECK();
 }
 
 // =====================================================================================================
@@ -3129,6 +3249,59 @@ int p5_cand_score(P5Engine* e, const int64_t* input_ids, const int64_t* whole_wo
   r.rows = rows_per_user; r.top_n = top_n; r.exact = exact_products;
   r.out_scores = out_scores; r.out_order = out_order; r.out_index = out_index; r.out_score = out_score; r.out_flagged = out_flagged; r.ws = (char*)ws;
   return e->c.dtype == 1 ? cand_score_impl<bf16>(e, r, (hipStream_t)stream) : cand_score_impl<float>(e, r, (hipStream_t)stream);
+}
+int64_t p5_prune_workspace_bytes(const P5Engine* e, int B, int L, int rows_total, int rows_per_user, int64_t n_edges, int n_items, int top_n) {
+  return layout_prune(const_cast<P5Engine*>(e), nullptr, B, L, rows_total, rows_per_user, n_edges, n_items, top_n, nullptr);
+}
+static int prune_rank_args(P5Engine* e, RankArgs& r, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask,
+                           int B, int L, const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth,
+                           const int* row_node, const int* row_anc, int rows_total, int max_depth, const int* item_edges, int n_items, int path_len,
+                           const uint32_t* excluded_items, int top_n, int* out_index, float* out_score, int* out_flagged) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_REQUIRE(B >= 1 && L >= 1 && L <= 512, "prune: B >= 1, 1 <= L <= 512");
+  P5_REQUIRE(child_off && child_tok && n_edges >= 1 && row_tok && row_depth && row_node && row_anc && item_edges, "prune: trie / plan / path arrays");
+  P5_REQUIRE(rows_total >= 1 && max_depth >= 1 && max_depth <= e->lut_half, "prune: rows_total >= 1, 1 <= max_depth <= the bucket LUT's half length");
+  P5_REQUIRE((int64_t)B * ((rows_total + 15) / 16 * 16 + 16 * ((rows_total + 511) / 512)) * e->c.n_heads < ((int64_t)1 << 31), "prune: B x rows_total x heads must stay below 2^31 (rank fewer users per call)");
+  P5_REQUIRE(n_items >= 1 && path_len >= 1, "prune: n_items, path_len");
+  P5_REQUIRE(top_n >= 1 && top_n <= P5_WIDE_MAX_K, "prune: 1 <= top_n <= 4096");
+  P5_REQUIRE(out_index && out_score && out_flagged, "prune: out_index / out_score / out_flagged");
+  r.input_ids = input_ids; r.whole_word_ids = whole_word_ids; r.attention_mask = attention_mask; r.B = B; r.L = L;
+  r.child_off = child_off; r.child_tok = child_tok; r.n_edges = n_edges;
+  r.pl.row_tok = row_tok; r.pl.row_depth = row_depth; r.pl.row_node = row_node; r.pl.anc = row_anc; r.pl.rows = rows_total; r.pl.max_depth = max_depth;
+  r.pl.B = B; r.pl.CQ = 0; r.pl.nchunk = 0;
+  r.item_edges = item_edges; r.n_items = n_items; r.path_len = path_len; r.excluded = excluded_items; r.top_n = top_n; r.exact = 0;
+  r.out_scores_all = nullptr; r.out_index = out_index; r.out_score = out_score; r.out_flagged = out_flagged; r.ws = nullptr;
+  return 0;
+}
+int p5_prune_propose(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                     const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                     const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* item_edges, int n_items,
+                     int path_len, const uint32_t* excluded_items, int top_n, float slack, int* out_index, float* out_score, int* out_flagged,
+                     void* rank_ws, int64_t rank_ws_bytes, void* prune_ws, int64_t prune_ws_bytes, void* stream) {
+  RankArgs r;
+  P5_TRY(prune_rank_args(e, r, input_ids, whole_word_ids, attention_mask, B, L, child_off, child_tok, n_edges, row_tok, row_depth, row_node, row_anc,
+                         rows_total, max_depth, item_edges, n_items, path_len, excluded_items, top_n, out_index, out_score, out_flagged));
+  P5_REQUIRE(row_edge && row_lmax && slack >= 0.f, "prune_propose: row_edge / row_lmax / slack >= 0");
+  P5_REQUIRE(rank_ws && rank_ws_bytes >= layout_rank(e, nullptr, B, L, rows_total, n_edges, n_items, top_n, nullptr), "rank workspace too small");
+  P5_REQUIRE(prune_ws && prune_ws_bytes >= layout_prune(e, nullptr, B, 1, rows_total, 0, n_edges, n_items, top_n, nullptr), "prune workspace too small");
+  r.ws = (char*)rank_ws;
+  return e->c.dtype == 1 ? prune_propose_impl<bf16>(e, r, row_edge, row_lmax, slack, (char*)prune_ws, (hipStream_t)stream)
+                         : prune_propose_impl<float>(e, r, row_edge, row_lmax, slack, (char*)prune_ws, (hipStream_t)stream);
+}
+int p5_prune_decide(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                    const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                    const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* edge_row,
+                    const int* item_edges, int n_items, int path_len, const uint32_t* excluded_items, int top_n, int rows_per_user, float margin,
+                    int* out_index, float* out_score, int* out_flagged, void* prune_ws, int64_t prune_ws_bytes, void* stream) {
+  PruneArgs a;
+  P5_TRY(prune_rank_args(e, a.r, input_ids, whole_word_ids, attention_mask, B, L, child_off, child_tok, n_edges, row_tok, row_depth, row_node, row_anc,
+                         rows_total, max_depth, item_edges, n_items, path_len, excluded_items, top_n, out_index, out_score, out_flagged));
+  P5_REQUIRE(row_edge && row_lmax && edge_row && margin >= 0.f, "prune_decide: row_edge / row_lmax / edge_row / margin >= 0");
+  P5_REQUIRE(rows_per_user >= 1 && rows_per_user <= rows_total, "prune_decide: 1 <= rows_per_user <= rows_total");
+  P5_REQUIRE(prune_ws && prune_ws_bytes >= layout_prune(e, nullptr, B, L, rows_total, rows_per_user, n_edges, n_items, top_n, nullptr), "prune workspace too small");
+  a.r.ws = (char*)prune_ws;
+  a.row_edge = row_edge; a.row_lmax = row_lmax; a.edge_row = edge_row; a.rows = rows_per_user; a.margin = margin;
+  return e->c.dtype == 1 ? prune_decide_impl<bf16>(e, a, (hipStream_t)stream) : prune_decide_impl<float>(e, a, (hipStream_t)stream);
 }
 int p5_generate_timing(P5Engine* e, int enable, float* encode_ms, float* decode_ms) {
 #ifndef P5_EMU

@@ -37,6 +37,15 @@ __device__ static __forceinline__ int p5_rank_pass_row(const P5RankPlan& pl, int
   return ((ru / pl.CQ) * pl.B + b) * pl.CQ + ru % pl.CQ;
 }
 
+// a pass over a per-user subset of the plan's rows (p5_prune.h): row `ru` of user b of the pass is plan row sel[b][ru], ru < n_rows[b];
+// sel == nullptr: the pass holds every plan row
+struct P5RankSel { const int* sel; const int* n_rows; int cap; };
+__device__ static __forceinline__ int p5_rank_plan_row(const P5RankPlan& pl, const P5RankSel& rs, int g, int& b) {    // pass row -> (user, plan row); -1: padding
+  const int ru = p5_rank_user_row(pl, g, b);
+  if (rs.sel == nullptr) return ru < pl.rows ? ru : -1;
+  return ru < rs.n_rows[b] ? rs.sel[(size_t)b * rs.cap + ru] : -1;
+}
+
 // decoder input ids of the pass (padding rows: the pad token)
 __global__ __launch_bounds__(256) void p5_rank_rows_kernel(int64_t* __restrict__ ids, P5RankPlan pl, int pad_id) {
   const int g = blockIdx.x * 256 + threadIdx.x;
@@ -97,13 +106,13 @@ template <class T>
 __global__ __launch_bounds__(256) void p5_rank_score_kernel(float* __restrict__ edge_lp, long long n_edges, const float* __restrict__ part_m,
                                                            const float* __restrict__ part_s, int ntiles, const T* __restrict__ hn,
                                                            const T* __restrict__ E, int d, float alpha, P5RankPlan pl, int g0,
-                                                           const int* __restrict__ child_off, const int* __restrict__ child_tok) {
+                                                           const int* __restrict__ child_off, const int* __restrict__ child_tok, P5RankSel rs) {
   constexpr int EPF = TT<T>::EPF;
   __shared__ float sm[4], ss[4];
   const int lr = blockIdx.x, g = g0 + lr, tid = threadIdx.x;
   int b;
-  const int ru = p5_rank_user_row(pl, g, b);
-  if (ru >= pl.rows) return;                   // padding row (uniform per block)
+  const int ru = p5_rank_plan_row(pl, rs, g, b);
+  if (ru < 0) return;                          // padding row (uniform per block)
   const int nd = pl.row_node[ru];
   const int c0 = child_off[nd], nc = child_off[nd + 1] - c0;
   const float lse = p5_rank_lse_from_partials(part_m + (size_t)lr * ntiles, part_s + (size_t)lr * ntiles, ntiles, sm, ss);
@@ -177,12 +186,12 @@ __device__ static __forceinline__ float p5_rank_lse_from_logits(const float* __r
 // p5_dec_score_kernel computes it ----
 __global__ __launch_bounds__(256) void p5_rank_score_logits_kernel(float* __restrict__ edge_lp, long long n_edges, const float* __restrict__ logits,
                                                                   int ldl, int V, P5RankPlan pl, int g0, const int* __restrict__ child_off,
-                                                                  const int* __restrict__ child_tok) {
+                                                                  const int* __restrict__ child_tok, P5RankSel rs) {
   __shared__ float sm[4], ss[4];
   const int g = g0 + blockIdx.x, tid = threadIdx.x;
   int b;
-  const int ru = p5_rank_user_row(pl, g, b);
-  if (ru >= pl.rows) return;
+  const int ru = p5_rank_plan_row(pl, rs, g, b);
+  if (ru < 0) return;
   const float* lr = logits + (size_t)blockIdx.x * ldl;
   const float lse = p5_rank_lse_from_logits(lr, V, sm, ss);
   const int nd = pl.row_node[ru];

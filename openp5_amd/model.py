@@ -193,7 +193,20 @@ class P5T5Native(nn.Module):
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
         self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
-        self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}
+        self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
+                           "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0}
+        # rank_items(pruned=True), csrc/p5_prune.h.  slack: how far below the bf16 N-th score a prefix's bound may lie and still get fp32
+        # numbers (3 x the bf16 score tolerance 0.04: one on the threshold, one on the bound, one of headroom); margin: the certificate's
+        # (the tolerance fp32 scores are held to at T5-small width); max_fraction: above this share of the trie's rows the proposal is
+        # declined and the full fp32 pass runs instead.  0.6 is the measured break-even (profiles/rank_pruned.jsonl, T5-small, 3416 items,
+        # 8 users: bf16 pass 1.19 ms per user, full fp32 pass 3.86, pruned call 2.73 at a kept share of 0.36 and 4.70 at 0.81): up to a
+        # share of 0.62 the whole pruned call, bf16 pass included, costs less than the full fp32 pass alone, and the fp32 work still to do
+        # at 0.6 (2.6 ms) leaves room for a third of the users falling back before declining would have been cheaper.
+        # slack and max_fraction change cost and the fallback share, never a returned list.
+        self.rank_prune_slack = 0.12
+        self.rank_prune_margin = 1e-4
+        self.rank_prune_max_fraction = 0.6
+        self._prune_sabotage = None         # test hook: called as _prune_sabotage(sel [nb, rows], n_rows [nb]) between propose and decide
         self.cand_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}      # score_candidates()
         self._warned_wide_verified = False
         self._shadow_t = None       # transposed bf16 copy of the layer weights (data gradients run on the forward GEMM kernel)
@@ -820,7 +833,7 @@ class P5T5Native(nn.Module):
     # ------------------------------------------------------------------ exhaustive catalogue ranking (csrc/p5_rank.h)
     @torch.no_grad()
     def rank_items(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, top_n: int = 10, excluded_items=None,
-                   return_all_scores: bool = False, generation_mode: Optional[str] = None, roots=None):
+                   return_all_scores: bool = False, generation_mode: Optional[str] = None, roots=None, pruned: bool = False):
         """Rank the WHOLE catalogue for every user, exactly: one teacher-forced decoder pass over every prefix of the item trie gives each
         item the score HF's beam search would assign it (sum of its tokens' log-probabilities up to and including </s>, divided by their
         number), then an exact top-`top_n` per user -- what `generate(num_beams = number of items + 1)` returns, without a search.
@@ -829,6 +842,13 @@ class P5T5Native(nn.Module):
         Arithmetic follows `generation_mode` as generate() does: a bf16 model in "verified" mode ranks with the fp32 verification engine,
         in "draft" mode with the bf16 engine; an fp32 model ranks in fp32.  fp32 passes multiply with split products; a user whose pass
         leaves their range is rescored with exact fp32 products.  Users go through in chunks whose workspace fits `rank_max_bytes`.
+        `pruned=True` (a bf16 model in "verified" mode; no effect on an fp32 model or in "draft" mode): certified pruned ranking
+        (csrc/p5_prune.h).  The bf16 pass over the whole trie proposes the prefixes whose score bound is within `rank_prune_slack` of its
+        N-th score, the fp32 engine scores those prefixes alone, and a certificate (margin `rank_prune_margin`) proves that no item
+        outside them reaches the fp32 N-th score: the returned lists are the fp32 lists.  A user without a certificate is ranked by the
+        full fp32 pass (`rank_stats["fallback_users"]`); when the proposal keeps more than `rank_prune_max_fraction` of the rows the
+        chunk's users are (`"declined_users"`).  `last_generate_path` is "rank_pruned" when at least one user of the call was certified.
+        Only survivors have fp32 scores, so `return_all_scores` cannot be combined with it.
         Returns {"sequences" int64 [B * top_n, S] (decoder start first, pad-filled), "sequences_scores" [B * top_n], "item_index"
         [B, top_n] (-1 and score -1e9 where a user has fewer than top_n candidates), "scores" [B, n_items] or None}."""
         lib, dev = self._lib, self._be.device
@@ -882,7 +902,21 @@ class P5T5Native(nn.Module):
             engine, path = self._verify_engine(lane), "rank_fp32"
         else:
             engine, path = lane.engine, "rank_fp32"
-        need = lambda nb: int(lib.p5_rank_workspace_bytes(engine, nb, L, rows, n_edges, n_items, N))      # noqa: E731
+        prune = bool(pruned) and self.compute_dtype == 1 and mode == "verified"
+        if prune and return_all_scores:
+            raise ValueError("rank_items(pruned=True, return_all_scores=True): only the prefixes that survive pruning get fp32 scores")
+        need_full = lambda nb: int(lib.p5_rank_workspace_bytes(engine, nb, L, rows, n_edges, n_items, N))      # noqa: E731
+        need = need_full
+        if prune:
+            frac = float(self.rank_prune_max_fraction)
+            slack, margin = float(self.rank_prune_slack), float(self.rank_prune_margin)
+            if not (slack >= 0.0 and margin >= 0.0 and 0.0 < frac <= 1.0):
+                raise ValueError("rank_prune_slack >= 0, rank_prune_margin >= 0, 0 < rank_prune_max_fraction <= 1")
+            max_keep = max(1, min(rows, int(frac * rows)))          # a proposal that keeps more rows per user is declined
+            row_lmax, row_edge, edge_row = trie.prune_device_arrays(dev, start)
+            need_prune = lambda nb, kept: int(lib.p5_prune_workspace_bytes(engine, nb, L, rows, kept, n_edges, n_items, N))      # noqa: E731
+            need_draft = lambda nb: int(lib.p5_rank_workspace_bytes(lane.engine, nb, L, rows, n_edges, n_items, N))      # noqa: E731
+            need = lambda nb: max(need_full(nb), need_draft(nb), need_prune(nb, max_keep))      # noqa: E731
         budget = int(self.rank_max_bytes)
         if need(1) > budget:
             raise ValueError(f"rank_items: one user of this catalogue needs a workspace of {need(1)} bytes, rank_max_bytes is {budget}")
@@ -903,21 +937,67 @@ class P5T5Native(nn.Module):
             o_sc = torch.empty(nb, N, dtype=torch.float32, device=dev)
             o_all = torch.empty(nb, n_items, dtype=torch.float32, device=dev) if return_all_scores else None
             flagged = torch.zeros(nb, dtype=torch.int32, device=dev)
-            ws = self._lane_workspace(lane, need(nb), "rank")
+            ws = self._lane_workspace(lane, need_full(nb), "rank")
             self._be.check(lib.p5_rank_items(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, _ptr(off), _ptr(tok), n_edges, _ptr(row_tok),
                                              _ptr(row_depth), _ptr(row_node), _ptr(row_anc), rows, int(row_anc.shape[1]), _ptr(item_edges), n_items,
                                              int(item_edges.shape[1]), _ptr(ex_c), N, 1 if exact else 0, _ptr(o_all), _ptr(o_idx), _ptr(o_sc),
                                              _ptr(flagged), _ptr(ws), ws.numel(), sp), "p5_rank_items")
             return o_idx, o_sc, o_all, flagged
 
-        rescored = 0
+        def run_pruned(users):
+            """PROPOSE on the bf16 engine, DECIDE on the fp32 engine: (index, score, flagged) of the users, or the largest kept-row count
+            alone when the proposal is declined"""
+            nb = int(users.numel())
+            whole = nb == B
+            cut = lambda t: None if t is None else (t if whole else t[users].contiguous())      # noqa: E731
+            ids_c, ww_c, mask_c, ex_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(excl_t)
+            o_idx = torch.empty(nb, N, dtype=torch.int32, device=dev)
+            o_sc = torch.empty(nb, N, dtype=torch.float32, device=dev)
+            flagged = torch.zeros(nb, dtype=torch.int32, device=dev)
+            ws_r = self._lane_workspace(lane, need_draft(nb), "rank")
+            ws_p = self._lane_workspace(lane, need_prune(nb, max_keep), "prune")         # (sized for the largest pass that is not declined: the head stays put)
+            trie_args = (_ptr(off), _ptr(tok), n_edges, _ptr(row_tok), _ptr(row_depth), _ptr(row_node), _ptr(row_anc), rows, int(row_anc.shape[1]))
+            self._be.check(lib.p5_prune_propose(lane.engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, *trie_args, _ptr(row_edge), _ptr(row_lmax),
+                                                _ptr(item_edges), n_items, int(item_edges.shape[1]), _ptr(ex_c), N, slack, _ptr(o_idx), _ptr(o_sc), _ptr(flagged),
+                                                _ptr(ws_r), ws_r.numel(), _ptr(ws_p), ws_p.numel(), sp), "p5_prune_propose")
+            off_sel = 256 + (nb * 4 + 255) // 256 * 256
+            n_rows_t = ws_p[256:256 + nb * 4].view(torch.int32)
+            sel_t = ws_p[off_sel:off_sel + nb * rows * 4].view(torch.int32).view(nb, rows)
+            if self._prune_sabotage is not None:
+                self._prune_sabotage(sel_t, n_rows_t)
+                ws_p[:4].view(torch.int32).copy_(n_rows_t.max().reshape(1))
+            kept = int(ws_p[:4].view(torch.int32).item())        # the one integer the host reads: it sizes the pass
+            if kept > max_keep:
+                return kept, None
+            kept = max(kept, 1)
+            self._be.check(lib.p5_prune_decide(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, *trie_args, _ptr(row_edge), _ptr(row_lmax), _ptr(edge_row),
+                                               _ptr(item_edges), n_items, int(item_edges.shape[1]), _ptr(ex_c), N, kept, margin, _ptr(o_idx), _ptr(o_sc),
+                                               _ptr(flagged), _ptr(ws_p), ws_p.numel(), sp), "p5_prune_decide")
+            return kept, (o_idx, o_sc, flagged)
+
+        rescored = certified = fallback = declined = kept_max = 0
         for a in range(0, B, per):
             users = torch.arange(a, min(B, a + per), device=dev)
-            o_idx, o_sc, o_all, flagged = run(users, False)
-            index[users], score[users] = o_idx, o_sc
+            todo = users
+            if prune:
+                kept, res = run_pruned(users)
+                kept_max = max(kept_max, kept)
+                if res is None:
+                    declined += int(users.numel())
+                else:
+                    o_idx, o_sc, flagged = res
+                    index[users], score[users] = o_idx, o_sc
+                    # no certificate: these users through the full fp32 pass (their pruned results are overwritten, never returned)
+                    todo = users[flagged.nonzero().flatten()]
+                    fallback += int(todo.numel())
+                    certified += int(users.numel()) - int(todo.numel())
+                if not todo.numel():
+                    continue
+            o_idx, o_sc, o_all, flagged = run(todo, False)
+            index[todo], score[todo] = o_idx, o_sc
             if scores_all is not None:
-                scores_all[users] = o_all
-            bad = users[flagged.nonzero().flatten()]
+                scores_all[todo] = o_all
+            bad = todo[flagged.nonzero().flatten()]
             if bad.numel():
                 # a value of the split-product pass left the range of the two-term fp16 split: these users again, with exact fp32 products
                 rescored += int(bad.numel())
@@ -928,6 +1008,11 @@ class P5T5Native(nn.Module):
         with self._stats_lock:
             st = self.rank_stats
             st["calls"] += 1; st["users"] += B; st["rescored_users"] += rescored; st["users_per_pass"] = per; st["rows_per_user"] = rows
+            if prune:
+                st["pruned_calls"] += 1; st["certified_users"] += certified; st["fallback_users"] += fallback; st["declined_users"] += declined
+                st["kept_rows_per_user"] = kept_max
+        if prune and certified:
+            path = "rank_pruned"
         self.last_generate_path = path
         item_index = index.to(torch.int64)
         sequences = item_tokens[item_index.clamp(min=0)] * (item_index >= 0).unsqueeze(-1)       # (a missing candidate: the all-pad sequence)

@@ -320,6 +320,43 @@ class CompiledTrie:
         cache[key] = plan
         return plan
 
+    def prune_plan(self, start_id: int):
+        """What certified pruned ranking (csrc/p5_prune.h) adds to `rank_plan(start_id)`, ONE per trie.  dict of int32 arrays: row_lmax
+        [rows] the largest token count (generated tokens up to and including the last one: what p5_rank_items_kernel divides by) of any
+        item below the row's node; row_edge [rows] the edge (index into child_tok / child_node) that leads into the row, -1 for row 0;
+        edge_row [n_edges] the plan row of the edge's child node, -1 for a leaf (and for an edge that is not behind the start token).
+        Cached per start token."""
+        cache = self.__dict__.setdefault("_prune_plans", {})
+        key = int(start_id)
+        if key in cache:
+            return cache[key]
+        plan = self.rank_plan(start_id)
+        rows = plan["rows"]
+        node_row = np.full(self.n_nodes, -1, dtype=np.int32)
+        node_row[plan["row_node"]] = np.arange(rows, dtype=np.int32)
+        edge_row = node_row[self.child_node]
+        row_edge = np.full(rows, -1, dtype=np.int32)
+        e = np.nonzero(edge_row > 0)[0]                 # (a tree: one edge per node; row 0 sits behind the start token, which is not scored)
+        row_edge[edge_row[e]] = e.astype(np.int32)
+        # a row has a leaf child (an item of depth + 1 tokens) or non-leaf children only (then their maxima are larger): level by level from the deepest
+        depth, parent = plan["row_depth"], plan["row_parent"]
+        lmax = (depth + 1).astype(np.int32)
+        for d in range(plan["levels"] - 1, 0, -1):
+            r = np.nonzero(depth == d)[0]
+            np.maximum.at(lmax, parent[r], lmax[r])
+        out = {"row_lmax": lmax, "row_edge": row_edge, "edge_row": np.ascontiguousarray(edge_row)}
+        cache[key] = out
+        return out
+
+    def prune_device_arrays(self, device, start_id: int):
+        """(row_lmax, row_edge, edge_row) of `prune_plan` on `device`, cached per (device, start token)."""
+        import torch
+        key = (str(device), int(start_id), "prune")
+        if key not in self._dev_items:
+            pp = self.prune_plan(start_id)
+            self._dev_items[key] = tuple(torch.from_numpy(np.ascontiguousarray(pp[k])).to(device) for k in ("row_lmax", "row_edge", "edge_row"))
+        return self._dev_items[key]
+
     def rank_device_arrays(self, device, start_id: int):
         """(plan tensors row_tok, row_depth, row_node, row_anc; item_edges behind the start token [n_items, depth - 1]; item_tokens int64) on
         `device`, cached per (device, start token)."""
