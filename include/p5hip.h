@@ -300,6 +300,33 @@ int p5_prune_decide(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
                     const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* edge_row,
                     const int* item_edges, int n_items, int path_len, const uint32_t* excluded_items, int top_n, int rows_per_user, float margin,
                     int* out_index, float* out_score, int* out_flagged, void* prune_ws, int64_t prune_ws_bytes, void* stream);
+/* ---- bounded trie search: the exact top_n of p5_rank_items without a pass over the whole trie (openp5_amd/csrc/p5_bound.h) ----
+ * For a bf16 model's fp32 engine and for an fp32 model.  The decoder runs over a per-user set of plan rows that starts from the prefixes
+ * of a few seed sequences and grows, round by round, by exactly the frontier rows whose score bound still reaches the top_n-th score;
+ * when nothing is admitted, the certificate of p5_prune_decide holds for the round that found it so.  Arrays as p5_prune_decide.
+ * The head of the workspace: int32 hdr[0] = the largest row count at byte 0, int32 hdr[1] = the number of users whose set grew in the last
+ * round at byte 4 (the TWO integers the host reads per round), int32 n_rows[B] at byte 256, int32 sel[B][rows_total] at byte 256 + (4 B
+ * rounded up to 256), then the search's own scratch.  p5_bound_workspace_bytes(.., rows_per_user = 0, ..) = the head alone; the
+ * workspace passed to every call must hold its value for the rows_per_user of that call, and its head must stay where it is.
+ *   p5_bound_begin: the encoder and the cross-attention K/V of every decoder layer (they stay in the workspace for every round), then
+ *     per user the plan rows of the prefixes of seeds int64 [B][n_seeds][seed_len] (token 0 = the decoder start; a sequence that leaves
+ *     the trie or does not end on a leaf contributes nothing) plus row 0, sorted and distinct, into sel; hdr[0] set, hdr[1] = 0.
+ *   p5_bound_round (rows_per_user >= hdr[0]): p5_prune_decide's pass over sel -- out_index / out_score / out_flagged as it leaves them --
+ *     then sel grows by the child rows c outside it with NOT (UB(c) < out_score[top_n - 1] - margin); hdr[0], hdr[1] set.  Repeat while
+ *     hdr[1] > 0, at most max_depth + 1 times; after a round with hdr[1] == 0 the outputs of that round are final, and a user with
+ *     out_flagged set must be ranked with p5_rank_items.
+ * Limits as p5_rank_items; 1 <= n_seeds <= 4096 and the same value in every call of a search.  All calls enqueue on `stream` only. */
+int64_t p5_bound_workspace_bytes(const P5Engine* e, int B, int L, int rows_total, int rows_per_user, int64_t n_edges, int n_items, int top_n, int n_seeds,
+                                 int max_depth);
+int p5_bound_begin(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                   const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_node, int rows_total, int max_depth,
+                   const int* edge_row, const int64_t* seeds, int n_seeds, int seed_len, int n_items, int top_n, void* ws, int64_t ws_bytes,
+                   void* stream);
+int p5_bound_round(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                   const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                   const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* edge_row,
+                   const int* item_edges, int n_items, int path_len, const uint32_t* excluded_items, int top_n, int n_seeds, int rows_per_user,
+                   float margin, int* out_index, float* out_score, int* out_flagged, void* ws, int64_t ws_bytes, void* stream);
 /* Device-time brackets of p5_generate for benchmarks: p5_generate_timing(e, 1, NULL, NULL) arms it; after a p5_generate call,
  * p5_generate_timing(e, enable, &encode_ms, &decode_ms) WAITS for that call to finish and returns the time between its start and
  * its first decode step (encoder pass + cross-attention K/V projection + beam state) and the time of the decode loop itself. */

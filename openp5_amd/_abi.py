@@ -84,6 +84,9 @@ PROTOTYPES = {
     "p5_prune_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i64, i32, i32]),
     "p5_prune_propose": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, i32, f32, vp, vp, vp, vp, i64, vp, i64, vp]),
     "p5_prune_decide": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, f32, vp, vp, vp, vp, i64, vp]),
+    "p5_bound_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i64, i32, i32, i32, i32]),
+    "p5_bound_begin": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
+    "p5_bound_round": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp]),
     "p5_generate_timing": (i32, [vp, i32, C.POINTER(f32), C.POINTER(f32)]),
     "p5_decode_begin": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, i64, vp]),
     "p5_decode_step": (i32, [vp, vp]),

@@ -25,6 +25,7 @@
 #include "p5_rank.h"
 #include "p5_cand.h"
 #include "p5_prune.h"
+#include "p5_bound.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -2144,21 +2145,32 @@ static int cand_plan_impl(P5Engine* e, const int* cand, int B, int C, const int*
   return P5_KCHECK();
 }
 
-// encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl; `pass`: where its buffers start, behind the plan's) + the
-// decoder over every user's own rows pl.sel + the range guard of the split-product pass into out_flagged (cleared first).  Shared by
-// cand_score_impl and prune_decide_impl.
-template <class T>
-static int sel_rows_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids,
-                         const int64_t* attention_mask, int L, int split_on, int* out_flagged, hipStream_t s) {
-  const P5Config& c = e->c;
-  const int d = c.d_model, in = e->inner, H = c.n_heads, B = pl.g.B;
-  const int R = B * w.CQ * w.nchunk;
+// A pass over per-user subsets of the plan's rows, in two parts (`pass`: where its buffers start, behind the plan's).  layout_sel_pass puts
+// the encoder's buffers and kv_all in front of everything that depends on the row count, so what the first part leaves stays where it is
+// while the second runs again with more rows (bound_round_impl).
+static void sel_pass_bind(P5Engine* e, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L) {
   layout_ws(e, pass, B, L, 0, false);
   e->B = B; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
+}
+// first part: encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl)
+template <class T>
+static int sel_encode_pass(P5Engine* e, const CandWs& w, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask,
+                           int B, int L, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int in = e->inner;
+  sel_pass_bind(e, pass, input_ids, whole_word_ids, attention_mask, B, L);
   P5_TRY(encoder_fwd<T>(e, s));
-  P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * L, c.n_dec_layers * 2 * in, c.d_model));
-  // the decoder over every user's own prefixes
+  return linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * L, c.n_dec_layers * 2 * in, c.d_model);
+}
+// second part: the decoder over every user's own rows pl.sel + the range guard of the split-product pass into out_flagged (cleared first)
+template <class T>
+static int sel_decode_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids,
+                           const int64_t* attention_mask, int L, int split_on, int* out_flagged, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int d = c.d_model, H = c.n_heads, B = pl.g.B;
+  const int R = B * w.CQ * w.nchunk;
+  sel_pass_bind(e, pass, input_ids, whole_word_ids, attention_mask, B, L);
   P5_LAUNCH(p5_cand_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, w.ids, pl, c.pad_id);
   P5_TRY(P5_KCHECK());
   RowsPassBufs pb;
@@ -2175,6 +2187,13 @@ static int sel_rows_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, cha
     P5_TRY(P5_KCHECK());
   }
   return 0;
+}
+// the two parts back to back: cand_score_impl and prune_decide_impl
+template <class T>
+static int sel_rows_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids,
+                         const int64_t* attention_mask, int L, int split_on, int* out_flagged, hipStream_t s) {
+  P5_TRY((sel_encode_pass<T>(e, w, pass, input_ids, whole_word_ids, attention_mask, pl.g.B, L, s)));
+  return sel_decode_pass<T>(e, w, pl, pass, input_ids, whole_word_ids, attention_mask, L, split_on, out_flagged, s);
 }
 
 struct CandArgs {
@@ -2241,6 +2260,16 @@ struct PruneWs : CandWs {
   unsigned long long* part;
   int G, S;
 };
+// the pass behind a head of w.plan_bytes: shared by layout_prune and layout_bound
+static int64_t layout_prune_pass(P5Engine* e, char* base, int B, int L, int rows, int64_t n_edges, int n_items, int top_n, PruneWs& w) {
+  Bump b = layout_sel_pass(e, base ? base + w.plan_bytes : nullptr, B, L, rows, w);
+  w.edge_lp = (float*)b.take((size_t)B * n_edges * 4);
+  w.scores = (float*)b.take((size_t)B * n_items * 4);
+  w.excl = (uint32_t*)b.take((size_t)B * ((n_items + 31) / 32) * 4);
+  rank_select_grid(n_items, top_n, w.G, w.S);
+  w.part = (unsigned long long*)b.take((size_t)B * w.G * top_n * 8);
+  return (int64_t)(w.plan_bytes + ((b.off + 255) & ~(size_t)255));
+}
 static int64_t layout_prune(P5Engine* e, char* base, int B, int L, int rows_total, int rows, int64_t n_edges, int n_items, int top_n, PruneWs* out) {
   PruneWs tmp;
   PruneWs& w = out ? *out : tmp;
@@ -2252,13 +2281,7 @@ static int64_t layout_prune(P5Engine* e, char* base, int B, int L, int rows_tota
   w.sel = (int*)p.take((size_t)B * w.cap * 4);
   w.plan_bytes = (p.off + 255) & ~(size_t)255;
   if (rows <= 0) return (int64_t)w.plan_bytes;
-  Bump b = layout_sel_pass(e, base ? base + w.plan_bytes : nullptr, B, L, rows, w);
-  w.edge_lp = (float*)b.take((size_t)B * n_edges * 4);
-  w.scores = (float*)b.take((size_t)B * n_items * 4);
-  w.excl = (uint32_t*)b.take((size_t)B * ((n_items + 31) / 32) * 4);
-  rank_select_grid(n_items, top_n, w.G, w.S);
-  w.part = (unsigned long long*)b.take((size_t)B * w.G * top_n * 8);
-  return (int64_t)(w.plan_bytes + ((b.off + 255) & ~(size_t)255));
+  return layout_prune_pass(e, base, B, L, rows, n_edges, n_items, top_n, w);
 }
 
 template <class T>
@@ -2281,20 +2304,14 @@ struct PruneArgs {
   int rows;                 // rows per user of the pass (>= the header word)
   float margin;
 };
+// DECIDE + CERTIFY behind the encoder: the decoder over sel, the edges, the mask, the selection, the certificate.  Shared by
+// prune_decide_impl (once) and bound_round_impl (every round, over a sel that grows).
 template <class T>
-static int prune_decide_impl(P5Engine* e, PruneArgs& a, hipStream_t s) {
+static int prune_decide_rows(P5Engine* e, PruneArgs& a, const PruneWs& w, const P5CandPlan& pl, int split_on, hipStream_t s) {
   RankArgs& r = a.r;
-  const int split_on = sizeof(T) == 4 ? g_opt_verify_split : 0;
-  SplitScope split(split_on);
-  PruneWs w;
-  layout_prune(e, r.ws, r.B, r.L, r.pl.rows, a.rows, r.n_edges, r.n_items, r.top_n, &w);
   const int B = r.B;
-  P5CandPlan pl;
-  pl.g = r.pl;
-  pl.g.rows = a.rows; pl.g.B = B; pl.g.CQ = w.CQ; pl.g.nchunk = w.nchunk;
-  pl.sel = w.sel; pl.n_rows = w.n_rows; pl.cap = w.cap;
   const int R = B * w.CQ * w.nchunk;
-  P5_TRY((sel_rows_pass<T>(e, w, pl, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.L, split_on, r.out_flagged, s)));
+  P5_TRY((sel_decode_pass<T>(e, w, pl, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.L, split_on, r.out_flagged, s)));
   // the log-probability of every child edge of every sel row; every other edge keeps the sentinel
   const size_t ne = (size_t)B * r.n_edges;
   P5_LAUNCH(p5_prune_fill_kernel, dim3((unsigned)((ne + 255) / 256 > 4096 ? 4096 : (ne + 255) / 256)), dim3(256), 0, s, w.edge_lp, ne, P5_PRUNE_SENTINEL);
@@ -2309,6 +2326,89 @@ static int prune_decide_impl(P5Engine* e, PruneArgs& a, hipStream_t s) {
   P5_TRY(rank_select(w.scores, w.edge_lp, r.n_edges, r.item_edges, r.n_items, r.path_len, w.excl, w.part, w.G, w.S, B, r.top_n, r.out_index, r.out_score, s));
   P5_LAUNCH(p5_prune_certify_kernel, dim3((w.CQ * w.nchunk + 255) / 256, B), dim3(256), 0, s, r.out_flagged, (const float*)w.edge_lp, (long long)r.n_edges, pl,
             a.row_edge, a.edge_row, a.row_lmax, r.child_off, (const int*)r.out_index, (const float*)r.out_score, r.top_n, a.margin);
+  return P5_KCHECK();
+}
+static P5CandPlan prune_pass_plan(const PruneArgs& a, const PruneWs& w) {
+  P5CandPlan pl;
+  pl.g = a.r.pl;
+  pl.g.rows = a.rows; pl.g.B = a.r.B; pl.g.CQ = w.CQ; pl.g.nchunk = w.nchunk;
+  pl.sel = w.sel; pl.n_rows = w.n_rows; pl.cap = w.cap;
+  return pl;
+}
+template <class T>
+static int prune_decide_impl(P5Engine* e, PruneArgs& a, hipStream_t s) {
+  RankArgs& r = a.r;
+  const int split_on = sizeof(T) == 4 ? g_opt_verify_split : 0;
+  SplitScope split(split_on);
+  PruneWs w;
+  layout_prune(e, r.ws, r.B, r.L, r.pl.rows, a.rows, r.n_edges, r.n_items, r.top_n, &w);
+  const P5CandPlan pl = prune_pass_plan(a, w);
+  P5_TRY((sel_encode_pass<T>(e, w, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.B, r.L, s)));
+  return prune_decide_rows<T>(e, a, w, pl, split_on, s);
+}
+
+// ---- bounded trie search (p5_bound.h).  The workspace: the head of the prune workspace (hdr | n_rows [B] | sel [B][rows of the plan]) +
+// grew [B] + the sort keys [B][KP], then the pass of layout_prune.  BEGIN: encoder + K/V, the seeds' rows into sel.  ROUND: the rows part
+// of the pass over sel, DECIDE + CERTIFY as prune_decide_impl, then the frontier rows within reach of tau join sel. ----
+struct BoundWs : PruneWs {
+  int* grew;
+  int KP;                   // keys per user: a power of two >= max(the plan's rows, n_seeds * max_depth + 1, 256)
+};
+static int64_t layout_bound(P5Engine* e, char* base, int B, int L, int rows_total, int rows, int64_t n_edges, int n_items, int top_n, int n_seeds,
+                            int max_depth, BoundWs* out) {
+  BoundWs tmp;
+  BoundWs& w = out ? *out : tmp;
+  Bump p{base, 0};
+  w.cap = rows_total;
+  w.P = 0; w.row_lse = nullptr;
+  w.hdr = (int*)p.take(64);
+  w.n_rows = (int*)p.take((size_t)B * 4);
+  w.sel = (int*)p.take((size_t)B * w.cap * 4);
+  w.grew = (int*)p.take((size_t)B * 4);
+  const int64_t slots = (int64_t)n_seeds * max_depth + 1;
+  w.KP = 256;
+  while (w.KP < rows_total || w.KP < slots) w.KP <<= 1;
+  w.keys = (unsigned long long*)p.take((size_t)B * w.KP * 8);
+  w.plan_bytes = (p.off + 255) & ~(size_t)255;
+  if (rows <= 0) return (int64_t)w.plan_bytes;
+  return layout_prune_pass(e, base, B, L, rows, n_edges, n_items, top_n, w);
+}
+struct BoundArgs {
+  PruneArgs p;              // (p.r.ws: the bound workspace)
+  const int64_t* seeds;     // [B][n_seeds][seed_len] (p5_bound_begin)
+  int n_seeds, seed_len;
+};
+template <class T>
+static int bound_begin_impl(P5Engine* e, BoundArgs& a, hipStream_t s) {
+  RankArgs& r = a.p.r;
+  const int split_on = sizeof(T) == 4 ? g_opt_verify_split : 0;
+  SplitScope split(split_on);
+  BoundWs w;
+  layout_bound(e, r.ws, r.B, r.L, r.pl.rows, 1, r.n_edges, r.n_items, r.top_n, a.n_seeds, r.pl.max_depth, &w);
+  P5_TRY((sel_encode_pass<T>(e, w, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.B, r.L, s)));
+  int P = 256;
+  while (P < a.n_seeds * r.pl.max_depth + 1) P <<= 1;
+  P5_LAUNCH(p5_bound_seed_kernel, dim3((a.n_seeds + 255) / 256, r.B), dim3(256), 0, s, w.keys, w.KP, P, a.seeds, a.n_seeds, a.seed_len, r.child_off, r.child_tok,
+            a.p.edge_row, r.pl.row_tok, r.pl.row_node, r.pl.max_depth);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_bound_union_kernel, dim3(r.B), dim3(256), 0, s, w.sel, w.n_rows, w.keys, w.KP, P, w.cap);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_bound_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, (const int*)nullptr, r.B);
+  return P5_KCHECK();
+}
+template <class T>
+static int bound_round_impl(P5Engine* e, BoundArgs& a, hipStream_t s) {
+  RankArgs& r = a.p.r;
+  const int split_on = sizeof(T) == 4 ? g_opt_verify_split : 0;
+  SplitScope split(split_on);
+  BoundWs w;
+  layout_bound(e, r.ws, r.B, r.L, r.pl.rows, a.p.rows, r.n_edges, r.n_items, r.top_n, a.n_seeds, r.pl.max_depth, &w);
+  const P5CandPlan pl = prune_pass_plan(a.p, w);
+  P5_TRY((prune_decide_rows<T>(e, a.p, w, pl, split_on, s)));
+  P5_LAUNCH(p5_bound_expand_kernel, dim3(r.B), dim3(256), 0, s, w.sel, w.n_rows, w.grew, w.keys, w.KP, (const float*)w.edge_lp, (long long)r.n_edges, pl,
+            a.p.row_edge, a.p.edge_row, a.p.row_lmax, r.child_off, (const float*)r.out_score, r.top_n, a.p.margin);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_bound_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, (const int*)w.grew, r.B);
   return P5_KCHECK();
 }
 
@@ -3302,6 +3402,49 @@ int p5_prune_decide(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
   a.r.ws = (char*)prune_ws;
   a.row_edge = row_edge; a.row_lmax = row_lmax; a.edge_row = edge_row; a.rows = rows_per_user; a.margin = margin;
   return e->c.dtype == 1 ? prune_decide_impl<bf16>(e, a, (hipStream_t)stream) : prune_decide_impl<float>(e, a, (hipStream_t)stream);
+}
+int64_t p5_bound_workspace_bytes(const P5Engine* e, int B, int L, int rows_total, int rows_per_user, int64_t n_edges, int n_items, int top_n, int n_seeds,
+                                 int max_depth) {
+  return layout_bound(const_cast<P5Engine*>(e), nullptr, B, L, rows_total, rows_per_user, n_edges, n_items, top_n, n_seeds, max_depth, nullptr);
+}
+int p5_bound_begin(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                   const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_node, int rows_total, int max_depth,
+                   const int* edge_row, const int64_t* seeds, int n_seeds, int seed_len, int n_items, int top_n, void* ws, int64_t ws_bytes,
+                   void* stream) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_REQUIRE(B >= 1 && L >= 1 && L <= 512, "bound_begin: B >= 1, 1 <= L <= 512");
+  P5_REQUIRE(child_off && child_tok && n_edges >= 1 && row_tok && row_node && edge_row, "bound_begin: trie / plan arrays");
+  P5_REQUIRE(rows_total >= 1 && max_depth >= 1 && max_depth <= e->lut_half, "bound_begin: rows_total >= 1, 1 <= max_depth <= the bucket LUT's half length");
+  P5_REQUIRE(seeds && n_seeds >= 1 && n_seeds <= P5_WIDE_MAX_K && seed_len >= 1, "bound_begin: seeds, 1 <= n_seeds <= 4096, seed_len >= 1");
+  P5_REQUIRE(n_items >= 1 && top_n >= 1 && top_n <= P5_WIDE_MAX_K, "bound_begin: n_items, 1 <= top_n <= 4096");
+  P5_REQUIRE(ws && ws_bytes >= layout_bound(e, nullptr, B, L, rows_total, 1, n_edges, n_items, top_n, n_seeds, max_depth, nullptr), "workspace too small");
+  BoundArgs a;
+  memset(&a, 0, sizeof(a));
+  RankArgs& r = a.p.r;
+  r.input_ids = input_ids; r.whole_word_ids = whole_word_ids; r.attention_mask = attention_mask; r.B = B; r.L = L;
+  r.child_off = child_off; r.child_tok = child_tok; r.n_edges = n_edges;
+  r.pl.row_tok = row_tok; r.pl.row_node = row_node; r.pl.rows = rows_total; r.pl.max_depth = max_depth; r.pl.B = B;
+  r.n_items = n_items; r.top_n = top_n; r.ws = (char*)ws;
+  a.p.edge_row = edge_row; a.p.rows = 1;
+  a.seeds = seeds; a.n_seeds = n_seeds; a.seed_len = seed_len;
+  return e->c.dtype == 1 ? bound_begin_impl<bf16>(e, a, (hipStream_t)stream) : bound_begin_impl<float>(e, a, (hipStream_t)stream);
+}
+int p5_bound_round(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                   const int* child_off, const int* child_tok, int64_t n_edges, const int* row_tok, const int* row_depth, const int* row_node,
+                   const int* row_anc, int rows_total, int max_depth, const int* row_edge, const int* row_lmax, const int* edge_row,
+                   const int* item_edges, int n_items, int path_len, const uint32_t* excluded_items, int top_n, int n_seeds, int rows_per_user,
+                   float margin, int* out_index, float* out_score, int* out_flagged, void* ws, int64_t ws_bytes, void* stream) {
+  BoundArgs a;
+  P5_TRY(prune_rank_args(e, a.p.r, input_ids, whole_word_ids, attention_mask, B, L, child_off, child_tok, n_edges, row_tok, row_depth, row_node, row_anc,
+                         rows_total, max_depth, item_edges, n_items, path_len, excluded_items, top_n, out_index, out_score, out_flagged));
+  P5_REQUIRE(row_edge && row_lmax && edge_row && margin >= 0.f, "bound_round: row_edge / row_lmax / edge_row / margin >= 0");
+  P5_REQUIRE(n_seeds >= 1 && n_seeds <= P5_WIDE_MAX_K, "bound_round: 1 <= n_seeds <= 4096 (as given to p5_bound_begin)");
+  P5_REQUIRE(rows_per_user >= 1 && rows_per_user <= rows_total, "bound_round: 1 <= rows_per_user <= rows_total");
+  P5_REQUIRE(ws && ws_bytes >= layout_bound(e, nullptr, B, L, rows_total, rows_per_user, n_edges, n_items, top_n, n_seeds, max_depth, nullptr), "workspace too small");
+  a.p.r.ws = (char*)ws;
+  a.p.row_edge = row_edge; a.p.row_lmax = row_lmax; a.p.edge_row = edge_row; a.p.rows = rows_per_user; a.p.margin = margin;
+  a.seeds = nullptr; a.n_seeds = n_seeds; a.seed_len = 0;
+  return e->c.dtype == 1 ? bound_round_impl<bf16>(e, a, (hipStream_t)stream) : bound_round_impl<float>(e, a, (hipStream_t)stream);
 }
 int p5_generate_timing(P5Engine* e, int enable, float* encode_ms, float* decode_ms) {
 #ifndef P5_EMU

@@ -194,7 +194,9 @@ class P5T5Native(nn.Module):
                              "wide_fp32_users": 0}
         self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
-                           "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0}
+                           "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0,
+                           "search_calls": 0, "search_certified_users": 0, "search_fallback_users": 0, "search_declined_users": 0,
+                           "search_rounds": 0, "search_rows_per_user": 0}
         # rank_items(pruned=True), csrc/p5_prune.h.  slack: how far below the bf16 N-th score a prefix's bound may lie and still get fp32
         # numbers (3 x the bf16 score tolerance 0.04: one on the threshold, one on the bound, one of headroom); margin: the certificate's
         # (the tolerance fp32 scores are held to at T5-small width); max_fraction: above this share of the trie's rows the proposal is
@@ -207,6 +209,16 @@ class P5T5Native(nn.Module):
         self.rank_prune_margin = 1e-4
         self.rank_prune_max_fraction = 0.6
         self._prune_sabotage = None         # test hook: called as _prune_sabotage(sel [nb, rows], n_rows [nb]) between propose and decide
+        # rank_items(pruned="search"), csrc/p5_bound.h.  The certificate's margin is rank_prune_margin.  max_fraction: when a user's set of
+        # scored rows outgrows this share of the trie's rows the chunk is declined and the full pass runs instead.  0.1 is the largest share
+        # at which the search was still measured faster than the full fp32 pass, rounded down to one decimal (profiles/rank_search.jsonl,
+        # T5-small, 8 users: at a share of 0.13 of the 12101-item trie's rows 6.71 ms per user against 11.3 for the full pass; at 0.30 of the
+        # 3416-item trie's 5.32 against 3.84 -- every round re-runs the cumulative row set).
+        # seed_beams: width of the beam search that proposes the seeds (None: top_n).  Both change cost and the fallback share, never a list.
+        self.rank_search_max_fraction = 0.1
+        self.rank_search_seed_beams = None
+        self._search_hook = None            # test hook: _search_hook(round, sel [nb, rows], n_rows [nb]) after each round's header read; may edit sel in place
+        self._search_seed_hook = None       # test hook: _search_seed_hook(seeds int64 [B, S, T]) before the search begins; may edit the sequences in place
         self.cand_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}      # score_candidates()
         self._warned_wide_verified = False
         self._shadow_t = None       # transposed bf16 copy of the layer weights (data gradients run on the forward GEMM kernel)
@@ -833,7 +845,7 @@ class P5T5Native(nn.Module):
     # ------------------------------------------------------------------ exhaustive catalogue ranking (csrc/p5_rank.h)
     @torch.no_grad()
     def rank_items(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, top_n: int = 10, excluded_items=None,
-                   return_all_scores: bool = False, generation_mode: Optional[str] = None, roots=None, pruned: bool = False):
+                   return_all_scores: bool = False, generation_mode: Optional[str] = None, roots=None, pruned=False, seed_items=None):
         """Rank the WHOLE catalogue for every user, exactly: one teacher-forced decoder pass over every prefix of the item trie gives each
         item the score HF's beam search would assign it (sum of its tokens' log-probabilities up to and including </s>, divided by their
         number), then an exact top-`top_n` per user -- what `generate(num_beams = number of items + 1)` returns, without a search.
@@ -849,6 +861,15 @@ class P5T5Native(nn.Module):
         full fp32 pass (`rank_stats["fallback_users"]`); when the proposal keeps more than `rank_prune_max_fraction` of the rows the
         chunk's users are (`"declined_users"`).  `last_generate_path` is "rank_pruned" when at least one user of the call was certified.
         Only survivors have fp32 scores, so `return_all_scores` cannot be combined with it.
+        `pruned="search"` (a bf16 model in "verified" mode AND an fp32 model; no effect in "draft" mode): bounded trie search
+        (csrc/p5_bound.h), no pass over the whole trie at all.  The deciding engine scores the prefixes of a few seed items -- the model's
+        own constrained beam search with `rank_search_seed_beams` (default `top_n`) beams, or `seed_items` [B, S] item indices, -1 = empty
+        slot -- and round by round exactly the frontier prefixes whose score bound still reaches the N-th score, until none does: that is
+        the certificate of `pruned=True`, so the returned lists are the fp32 lists.  The two integers read per round are the only host
+        synchronisation.  Users without a certificate fall back to the full pass (`rank_stats["search_fallback_users"]`); a chunk whose
+        users outgrow `rank_search_max_fraction` of the rows is declined (`"search_declined_users"`); `"search_rounds"` is the last chunk's
+        round count, `"search_rows_per_user"` the largest final row count.  `last_generate_path` is "rank_search" when at least one user was
+        certified.  Not with `return_all_scores`.
         Returns {"sequences" int64 [B * top_n, S] (decoder start first, pad-filled), "sequences_scores" [B * top_n], "item_index"
         [B, top_n] (-1 and score -1e9 where a user has fewer than top_n candidates), "scores" [B, n_items] or None}."""
         lib, dev = self._lib, self._be.device
@@ -902,9 +923,19 @@ class P5T5Native(nn.Module):
             engine, path = self._verify_engine(lane), "rank_fp32"
         else:
             engine, path = lane.engine, "rank_fp32"
-        prune = bool(pruned) and self.compute_dtype == 1 and mode == "verified"
+        if isinstance(pruned, str):
+            if pruned != "search":
+                raise ValueError(f"rank_items(pruned={pruned!r}): False | True | \"search\"")
+        elif pruned is None or pruned not in (True, False):
+            raise ValueError(f"rank_items(pruned={pruned!r}): False | True | \"search\"")
+        search = isinstance(pruned, str) and not (self.compute_dtype == 1 and mode == "draft")
+        prune = not isinstance(pruned, str) and bool(pruned) and self.compute_dtype == 1 and mode == "verified"
         if prune and return_all_scores:
             raise ValueError("rank_items(pruned=True, return_all_scores=True): only the prefixes that survive pruning get fp32 scores")
+        if search and return_all_scores:
+            raise ValueError("rank_items(pruned=\"search\", return_all_scores=True): only the prefixes the search reaches get fp32 scores")
+        if seed_items is not None and not isinstance(pruned, str):
+            raise ValueError("rank_items: seed_items goes with pruned=\"search\"")
         need_full = lambda nb: int(lib.p5_rank_workspace_bytes(engine, nb, L, rows, n_edges, n_items, N))      # noqa: E731
         need = need_full
         if prune:
@@ -917,6 +948,32 @@ class P5T5Native(nn.Module):
             need_prune = lambda nb, kept: int(lib.p5_prune_workspace_bytes(engine, nb, L, rows, kept, n_edges, n_items, N))      # noqa: E731
             need_draft = lambda nb: int(lib.p5_rank_workspace_bytes(lane.engine, nb, L, rows, n_edges, n_items, N))      # noqa: E731
             need = lambda nb: max(need_full(nb), need_draft(nb), need_prune(nb, max_keep))      # noqa: E731
+        if search:
+            frac, margin = float(self.rank_search_max_fraction), float(self.rank_prune_margin)
+            if not (margin >= 0.0 and 0.0 < frac <= 1.0):
+                raise ValueError("rank_prune_margin >= 0, 0 < rank_search_max_fraction <= 1")
+            max_keep = max(1, min(rows, int(frac * rows)))          # a user whose set of scored rows outgrows this declines the chunk
+            row_lmax, row_edge, edge_row = trie.prune_device_arrays(dev, start)
+            levels = int(row_anc.shape[1])
+            if seed_items is not None:
+                seed_idx = torch.as_tensor(seed_items, dtype=torch.int64, device=dev)
+                if seed_idx.dim() != 2 or seed_idx.shape[0] != B or not 1 <= seed_idx.shape[1] <= self.WIDE_MAX_K:
+                    raise ValueError(f"seed_items: item indices [B={B}, 1 .. {self.WIDE_MAX_K}] (-1 = empty slot), got {tuple(seed_idx.shape)}")
+                if int(seed_idx.max()) >= n_items or int(seed_idx.min()) < -1:
+                    raise ValueError(f"seed_items: item indices must be in -1 .. {n_items - 1}")
+                seeds = (item_tokens[seed_idx.clamp(min=0)] * (seed_idx >= 0).unsqueeze(-1)).contiguous()
+            else:
+                # the model's own constrained beam search proposes: the draft search of a bf16 model, the fp32 search of an fp32 model
+                n_beams = max(1, min(int(self.rank_search_seed_beams or N), self.WIDE_MAX_K))
+                bm = None if excluded_items is None else trie.excluded_bitmap(excluded_items)
+                seeds = self.generate(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, max_length=trie.max_depth,
+                                      num_beams=n_beams, trie=trie, excluded=bm, generation_mode="draft")
+                seeds = seeds.view(B, n_beams, -1).contiguous()
+            if self._search_seed_hook is not None:
+                self._search_seed_hook(seeds)
+            n_seeds, seed_len = int(seeds.shape[1]), int(seeds.shape[2])
+            need_search = lambda nb, kept: int(lib.p5_bound_workspace_bytes(engine, nb, L, rows, kept, n_edges, n_items, N, n_seeds, levels))      # noqa: E731
+            need = lambda nb: max(need_full(nb), need_search(nb, max_keep))      # noqa: E731
         budget = int(self.rank_max_bytes)
         if need(1) > budget:
             raise ValueError(f"rank_items: one user of this catalogue needs a workspace of {need(1)} bytes, rank_max_bytes is {budget}")
@@ -975,10 +1032,66 @@ class P5T5Native(nn.Module):
                                                _ptr(flagged), _ptr(ws_p), ws_p.numel(), sp), "p5_prune_decide")
             return kept, (o_idx, o_sc, flagged)
 
+        def run_search(users):
+            """BEGIN + ROUNDs on the deciding engine: (largest row count, rounds, (index, score, flagged) of the users or None when the
+            chunk is declined)"""
+            nb = int(users.numel())
+            whole = nb == B
+            cut = lambda t: None if t is None else (t if whole else t[users].contiguous())      # noqa: E731
+            ids_c, ww_c, mask_c, ex_c, seeds_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(excl_t), cut(seeds)
+            o_idx = torch.empty(nb, N, dtype=torch.int32, device=dev)
+            o_sc = torch.empty(nb, N, dtype=torch.float32, device=dev)
+            flagged = torch.zeros(nb, dtype=torch.int32, device=dev)
+            ws = self._lane_workspace(lane, need_search(nb, max_keep), "search")          # (sized for the largest pass that is not declined: the head stays put)
+            self._be.check(lib.p5_bound_begin(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, _ptr(off), _ptr(tok), n_edges, _ptr(row_tok), _ptr(row_node),
+                                              rows, levels, _ptr(edge_row), _ptr(seeds_c), n_seeds, seed_len, n_items, N, _ptr(ws), ws.numel(), sp),
+                           "p5_bound_begin")
+            off_sel = 256 + (nb * 4 + 255) // 256 * 256
+            hdr_t = ws[:8].view(torch.int32)
+            n_rows_t = ws[256:256 + nb * 4].view(torch.int32)
+            sel_t = ws[off_sel:off_sel + nb * rows * 4].view(torch.int32).view(nb, rows)
+            kept, rounds = int(hdr_t[0].item()), 0
+            while True:
+                if kept > max_keep:
+                    return kept, rounds, None
+                if rounds == levels + 1:
+                    # (not reached in exact arithmetic: new rows get strictly deeper.)  No certificate for anybody
+                    flagged.fill_(1)
+                    break
+                kept = max(kept, 1)
+                self._be.check(lib.p5_bound_round(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, _ptr(off), _ptr(tok), n_edges, _ptr(row_tok),
+                                                  _ptr(row_depth), _ptr(row_node), _ptr(row_anc), rows, levels, _ptr(row_edge), _ptr(row_lmax), _ptr(edge_row),
+                                                  _ptr(item_edges), n_items, int(item_edges.shape[1]), _ptr(ex_c), N, n_seeds, kept, margin, _ptr(o_idx),
+                                                  _ptr(o_sc), _ptr(flagged), _ptr(ws), ws.numel(), sp), "p5_bound_round")
+                rounds += 1
+                kept, grew = hdr_t.tolist()          # the two integers the host reads per round
+                if self._search_hook is not None:
+                    self._search_hook(rounds, sel_t, n_rows_t)
+                    kept = int(n_rows_t.max().item())
+                    hdr_t[0] = kept
+                if grew == 0:
+                    break
+            return kept, rounds, (o_idx, o_sc, flagged)
+
         rescored = certified = fallback = declined = kept_max = 0
+        s_rounds = 0
         for a in range(0, B, per):
             users = torch.arange(a, min(B, a + per), device=dev)
             todo = users
+            if search:
+                kept, s_rounds, res = run_search(users)
+                kept_max = max(kept_max, kept)
+                if res is None:
+                    declined += int(users.numel())
+                else:
+                    o_idx, o_sc, flagged = res
+                    index[users], score[users] = o_idx, o_sc
+                    # no certificate: these users through the full pass (their search results are overwritten, never returned)
+                    todo = users[flagged.nonzero().flatten()]
+                    fallback += int(todo.numel())
+                    certified += int(users.numel()) - int(todo.numel())
+                if not todo.numel():
+                    continue
             if prune:
                 kept, res = run_pruned(users)
                 kept_max = max(kept_max, kept)
@@ -1011,8 +1124,13 @@ class P5T5Native(nn.Module):
             if prune:
                 st["pruned_calls"] += 1; st["certified_users"] += certified; st["fallback_users"] += fallback; st["declined_users"] += declined
                 st["kept_rows_per_user"] = kept_max
+            if search:
+                st["search_calls"] += 1; st["search_certified_users"] += certified; st["search_fallback_users"] += fallback
+                st["search_declined_users"] += declined; st["search_rounds"] = s_rounds; st["search_rows_per_user"] = kept_max
         if prune and certified:
             path = "rank_pruned"
+        if search and certified:
+            path = "rank_search"
         self.last_generate_path = path
         item_index = index.to(torch.int64)
         sequences = item_tokens[item_index.clamp(min=0)] * (item_index >= 0).unsqueeze(-1)       # (a missing candidate: the all-pad sequence)

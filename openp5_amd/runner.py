@@ -54,7 +54,9 @@ def parse_runner_args(parser):
                         "the user's history is left out of the ranking, whichever --test_filtered_batch is set): the limit the widened-beam "
                         "protocol approaches, at any catalogue size and history length.  2 = the same ranking with rank_items(pruned=True): on a bf16 "
                         "model the bf16 pass proposes the prefixes worth fp32 numbers and a certificate proves the fp32 list complete "
-                        "(users without one are ranked as under 1).  0 = the beam-search protocols, untouched.")
+                        "(users without one are ranked as under 1).  3 = the same ranking with rank_items(pruned=\"search\"): bounded trie search, for bf16 "
+                        "and fp32 models, which scores the prefixes within reach of the last returned item instead of the catalogue and certifies "
+                        "the list in the same way.  0 = the beam-search protocols, untouched.")
     parser.add_argument("--test_candidates", type=int, default=0, help="N > 0 = the sampled-candidates protocol: every test user is ranked on the gold "
                         "item + N negatives drawn uniformly, without replacement, from the items outside the user's history (all of them if fewer "
                         "exist) by a generator seeded from (--seed, dataset, user) alone, scored exactly in one pass (P5T5Native.score_candidates), "
@@ -466,7 +468,7 @@ class DistributedRunner:
         """--test_exhaustive 1: the batch's metric sums from an exact ranking of the whole catalogue (top generate_num, the items of
         `excluded_items` left out), in either metric form."""
         pred = self.model.rank_items(input_ids=batch[0], attention_mask=batch[1], whole_word_ids=batch[2], trie=ct, top_n=self.generate_num,
-                                     excluded_items=excluded_items, **({"pruned": True} if self.test_exhaustive == 2 else {}))
+                                     excluded_items=excluded_items, **({"pruned": True} if self.test_exhaustive == 2 else {"pruned": "search"} if self.test_exhaustive == 3 else {}))
         if self.id_metrics:
             rel = evaluate.rel_results_ids(pred["sequences"], pred["sequences_scores"], batch[3].to(pred["sequences"].device), self.generate_num)
             return evaluate.get_metrics_results_ids(rel, self.metrics), len(rel)
