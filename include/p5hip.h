@@ -458,13 +458,40 @@ int p5_op_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];
  * amode 1: A = fp32 residual stream [M, K], normalised with T5LayerNorm weight `ln` by the kernel itself.
- * epi: 0 store T (alpha), 1 relu store T, 2 fp32 atomic accumulate (split-K), 3 store fp32 (alpha) */
+ * (K <= 1024 then).  epi: 0 store T (alpha), 1 relu store T, 2 fp32 atomic accumulate (split-K), 3 store fp32 (alpha), 4 fp32 += by one writer */
 int p5_op_skinny_gemm(int dtype, int amode, const void* A, int lda, const float* ln, const void* W, int ldw, void* C, int ldc,
                       int M, int N, int K, int epi, float alpha, float eps, void* stream);
 /* decode-step cross-attention of the Kb beams of each of B items (p5_decode2.h): q T [B*Kb, H*64], kv T [B*L, 2*H*64] (K then V),
  * mask int64 [B, L]; zero position bias (HF modeling_t5.py:336-343).  variant 3 = matrix-core kernel, 2 = scalar kernel */
 int p5_op_dec_cross_attn(int dtype, int variant, void* out, const void* q, const void* kv, const int64_t* mask, int B, int H, int Kb,
                          int L, void* stream);
+/* ---- the kernels of the decode step, each through the launcher the engine uses (tests/decode_matrix.py).  `done` (may be NULL): device
+ * flag, != 0 -> the launch writes nothing.  Every entry refuses (error code, nothing launched) a shape its kernel cannot handle. ---- */
+/* p5_op_dec_cross_attn with a free row stride of kv (ldkv >= 2*H*64 elements: the layer's K|V block inside a wider row) and, with x != NULL
+ * (bf16 only; q ignored), the kernel's own q projection: q = T(T5LayerNorm(x fp32 [B*Kb, d], weight ln, eps) Wq^T), Wq T [H*64, d]; refused
+ * when the rows and the Wq slice do not fit the LDS (d_model > 512) */
+int p5_op_dec_cross_attn_ex(int dtype, int variant, void* out, const void* q, const float* x, const float* ln, const void* Wq, const void* kv,
+                            int ldkv, const int64_t* mask, int B, int H, int Kb, int L, int d, float eps, const int* done, void* stream);
+/* single-token self-attention over the ancestry-indexed cache: qkv T [R, 3*H*64] (this step's q | k | v), cache T [max_len][R][2*H*64];
+ * step[0] = cur_len (1 .. max_len, on the device); this step's k, v are written at position cur_len - 1; position t < cur_len - 1 of row r is
+ * read from row anc[t*R + r], anc = anc_odd for odd cur_len, else anc_even; bias rel_table[lut[t - pos + lut_half]*H + h]; out T [R, H*64] */
+int p5_op_dec_self_attn(int dtype, void* out, const void* qkv, void* cache, const int* anc_odd, const int* anc_even, const float* rel_table,
+                        const int* lut, int lut_half, int R, int H, const int* step, int max_len, const int* done, void* stream);
+/* y T [rows, d] = w * T(x / rms(x)), x fp32 [rows, d]; d a multiple of 8, <= 1024 */
+int p5_op_rmsnorm_f32in(int dtype, void* y, const float* x, const float* w, int rows, int d, float eps, const int* done, void* stream);
+/* streaming tied head: per tile t of nv rows of E (T [V, d]) and row r of hn (T [R, d]): part_m[r*nt + t] = max, part_s = sum exp(. - max)
+ * of alpha * hn[r] . E[v]; nt = ceil(V / nv); nv 16/32/64/128 with nv*d*sizeof(T) <= 128 KiB (64 KiB for 16), d % 256 (bf16) / 128 (fp32) == 0 */
+int p5_op_head_lse(int dtype, int nv, float* part_m, float* part_s, const void* hn, const void* E, int R, int d, int V, float alpha,
+                   const int* done, void* stream);
+/* per decode row r (R rows): the best K2 children c of trie node node[r] (CSR child_off / child_tok / child_node; at most max_c), scored
+ * log_softmax(logits[r])[child_tok] + run_score[r], in (score desc, child asc) order -> top_score / top_c [R, K2], n_top [R]; children whose
+ * node's bit is set in excluded[(r / Kb) * excl_words ..] are dropped; node < 0: n_top = 0.  streaming 1: the log-sum-exp from part_m / part_s
+ * [R, ntiles] and the logits as alpha * hn[r] . E[tok] (T, d <= 1024); streaming 0: fp32 logits [R, ldl], V columns.  cand_scratch fp32
+ * [R, max_c]: needed for fan-outs above 2048 */
+int p5_op_dec_score(int dtype, int streaming, const float* part_m, const float* part_s, int ntiles, const void* hn, const void* E, int d,
+                    float alpha, const float* logits, int ldl, int V, const int* node, const float* run_score, const int* child_off,
+                    const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, int R, int Kb, int max_c, int K2,
+                    float* cand_scratch, float* top_score, int* top_c, int* n_top, const int* done, void* stream);
 int p5_op_tr_probe(void* out64x4_u16, const void* in256_u16, void* stream);  /* ds_read_b64_tr_b16 semantics probe */
 
 #ifdef __cplusplus

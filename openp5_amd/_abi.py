@@ -112,6 +112,11 @@ PROTOTYPES = {
     "p5_op_masked_mean": (i32, [vp, vp, vp, i32, i32, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
+    "p5_op_dec_cross_attn_ex": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "p5_op_dec_self_attn": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]),
+    "p5_op_rmsnorm_f32in": (i32, [i32, vp, vp, vp, i32, i32, f32, vp, vp]),
+    "p5_op_head_lse": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp]),
+    "p5_op_dec_score": (i32, [i32, i32, vp, vp, i32, vp, vp, i32, f32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "p5_op_tr_probe": (i32, [vp, vp, vp]),
     "p5_profile_begin": (i32, []),
     "p5_profile_end": (i32, [C.c_char_p, i32]),

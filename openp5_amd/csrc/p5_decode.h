@@ -102,6 +102,7 @@ __global__ __launch_bounds__(256) void p5_dec_score_kernel(float* __restrict__ c
     int bi = 0x7fffffff;
     for (int c = tid; c < nc; c += 256) {
       const float v = cs[c];
+      if (v == P5_NEG_INF) continue;   // excluded or taken (-inf == -inf with a lower index would win the tie-break below)
       if (v > bv || (v == bv && c < bi)) { bv = v; bi = c; }
     }
     block_argmax(bv, bi, s_val, s_idx);

@@ -1356,16 +1356,25 @@ static int64_t layout_gen(P5Engine* e, char* base, int B, int L, int K, int max_
 }
 
 // ---- latency-shaped decode step (p5_decode2.h) ------------------------------------------------------------
+// what the template parameters of a stringified decode-step kernel name stand for (the profiler's tag of the launch)
+template <class T> static const char* dtype_name() { return sizeof(T) == 2 ? "bf16" : "fp32"; }
+template <class T, int NB, int AMODE, int KB>
+static const char* skinny_tag() {
+  static const std::string t = std::string(dtype_name<T>()) + " NB=" + std::to_string(NB) + " AMODE=" + std::to_string(AMODE) + " LDSKB=" + std::to_string(KB);
+  return t.c_str();
+}
 template <class T, int NB, int AMODE>
 static int launch_skinny_nb(const P5SkinnyArgs& g, int splits, int need_bytes, hipStream_t s) {
   dim3 grid((g.N + NB - 1) / NB, (g.M + 15) / 16, splits), block(256);
   // (the static LDS size is what bounds the workgroups per CU: 52 KiB -> 3, 80 KiB -> 2 of the 160 KiB)
-  if (need_bytes <= 44 * 1024) P5_LAUNCH((p5_skinny_gemm_kernel<T, NB, AMODE, 44>), grid, block, 0, s, g);
-  else if (need_bytes <= 52 * 1024) P5_LAUNCH((p5_skinny_gemm_kernel<T, NB, AMODE, 52>), grid, block, 0, s, g);
-  else if (need_bytes <= 80 * 1024) P5_LAUNCH((p5_skinny_gemm_kernel<T, NB, AMODE, 80>), grid, block, 0, s, g);
-  else if (need_bytes <= 100 * 1024) P5_LAUNCH((p5_skinny_gemm_kernel<T, NB, AMODE, 100>), grid, block, 0, s, g);
-  else if (need_bytes <= 140 * 1024) P5_LAUNCH((p5_skinny_gemm_kernel<T, NB, AMODE, 140>), grid, block, 0, s, g);
+#define P5_SKINNY(KB) do { P5_PROF_TAG((skinny_tag<T, NB, AMODE, KB>())); P5_LAUNCH((p5_skinny_gemm_kernel<T, NB, AMODE, KB>), grid, block, 0, s, g); } while (0)
+  if (need_bytes <= 44 * 1024) P5_SKINNY(44);
+  else if (need_bytes <= 52 * 1024) P5_SKINNY(52);
+  else if (need_bytes <= 80 * 1024) P5_SKINNY(80);
+  else if (need_bytes <= 100 * 1024) P5_SKINNY(100);
+  else if (need_bytes <= 140 * 1024) P5_SKINNY(140);
   else return fail("skinny gemm: tile does not fit the LDS");
+#undef P5_SKINNY
   return P5_KCHECK();
 }
 // C = A W^T over M <= a few hundred rows.  amode 1: A is the fp32 residual stream, normalised (T5LayerNorm, weight `ln`) by the
@@ -1374,7 +1383,8 @@ template <class T>
 static int skinny(hipStream_t s, int amode, const void* A, int lda, const float* ln, const T* W, int ldw, void* C, int ldc, int M, int N, int K,
                   int epi, float alpha, float eps, const int* done) {
   constexpr int EPS = SkT<T>::EPS;
-  P5_REQUIRE(K % EPS == 0 && ldw % TT<T>::EPF == 0 && (amode == 1 || lda % TT<T>::EPF == 0), "skinny gemm: K / leading dims");
+  P5_REQUIRE(M >= 1 && N >= 1 && K >= EPS && K % EPS == 0 && ldw % TT<T>::EPF == 0 && (amode == 1 || lda % TT<T>::EPF == 0), "skinny gemm: K / leading dims");
+  P5_REQUIRE(amode != 1 || K <= 1024, "skinny gemm: the fused T5LayerNorm (sk_norm_rows) holds rows of at most 1024 columns");
   P5SkinnyArgs g;
   g.A = A; g.ln = ln; g.W = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.epi = epi; g.alpha = alpha; g.eps = eps;
   g.done = done;
@@ -1427,15 +1437,17 @@ static int head_nv(const P5Engine* e) {
   return 0;
 }
 
-// streaming tied head over R rows: per vocabulary tile (max, sum exp) only; the logits the search needs are recomputed by p5_dec_score2_kernel
+// streaming tied head over R rows: per vocabulary tile (max, sum exp) only; the logits the search needs are recomputed by p5_dec_score2_kernel.
+// nv = rows of E per workgroup, one of head_nv()'s values for (T, d); part_m / part_s: [R][ceil(V / nv)]
 template <class T>
-static int launch_head_lse(P5Engine* e, float* part_m, float* part_s, const void* hn, int R, const int* done, hipStream_t s) {
-  const P5Config& c = e->c;
-  const int d = c.d_model;
-  const float alpha = 1.0f / sqrtf((float)d);
-  const int nv = head_nv(e), V = c.vocab_size, nt = (V + nv - 1) / nv;
+static int launch_head_lse_t(int nv, const T* E, int d, int V, float* part_m, float* part_s, const void* hn, int R, float alpha, const int* done,
+                             hipStream_t s) {
   const size_t bytes = (size_t)nv * d * sizeof(T);
-#define P5_HEAD(NV, KB) P5_LAUNCH((p5_head_lse_kernel<T, NV, KB>), dim3(nt), dim3(256), 0, s, part_m, part_s, (const T*)hn, Wc<T>(e, e->off_E), R, d, V, alpha, done)
+  P5_REQUIRE(R >= 1 && V >= 1 && d >= 1 && d % (sizeof(T) == 2 ? 256 : 128) == 0, "head_lse: d_model must be a multiple of 256 (bf16) / 128 (fp32)");
+  P5_REQUIRE((nv == 128 || nv == 64 || nv == 32 || nv == 16) && bytes <= (nv == 16 ? 64 : 128) * 1024, "head_lse: nv rows of E must fit the kernel's LDS");
+  const int nt = (V + nv - 1) / nv;
+#define P5_HEAD(NV, KB) do { P5_PROF_TAG(sizeof(T) == 2 ? "bf16 NV=" #NV " LDSKB=" #KB : "fp32 NV=" #NV " LDSKB=" #KB); \
+    P5_LAUNCH((p5_head_lse_kernel<T, NV, KB>), dim3(nt), dim3(256), 0, s, part_m, part_s, (const T*)hn, E, R, d, V, alpha, done); } while (0)
   if (nv == 128) P5_HEAD(128, 128);
   else if (nv == 64 && bytes <= 64 * 1024) P5_HEAD(64, 64);
   else if (nv == 64) P5_HEAD(64, 128);
@@ -1445,6 +1457,94 @@ static int launch_head_lse(P5Engine* e, float* part_m, float* part_s, const void
 #undef P5_HEAD
   return P5_KCHECK();
 }
+template <class T>
+static int launch_head_lse(P5Engine* e, float* part_m, float* part_s, const void* hn, int R, const int* done, hipStream_t s) {
+  const int d = e->c.d_model;
+  return launch_head_lse_t<T>(head_nv(e), Wc<T>(e, e->off_E), d, e->c.vocab_size, part_m, part_s, hn, R, 1.0f / sqrtf((float)d), done, s);
+}
+
+// hn(T) = T5LayerNorm(x32): p5_rmsnorm_f32in_kernel holds a row of at most 2 x 64 x 8 columns per wave
+template <class T>
+static int launch_rmsnorm_f32in(void* y, const float* x, const float* w, int rows, int d, float eps, const int* done, hipStream_t s) {
+  P5_REQUIRE(rows >= 1 && d >= 8 && d % 8 == 0 && d <= 1024, "rmsnorm_f32in: d must be a multiple of 8, <= 1024");
+  P5_LAUNCH((p5_rmsnorm_f32in_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (T*)y, x, w, rows, d, eps, done);
+  return P5_KCHECK();
+}
+
+// single-token self-attention over the ancestry-indexed cache [max_len][R][2 * H * 64]; `step` holds cur_len (1 .. max_len) on the device
+template <class T>
+static int launch_dec_self_attn(void* out, const void* qkv, void* cache, const int* anc_odd, const int* anc_even, const float* rel_table,
+                                const int* lut, int lut_half, int R, int H, const int* step, int max_len, const int* done, hipStream_t s) {
+  P5_REQUIRE(R >= 1 && H >= 1 && max_len >= 1 && max_len <= P5_MAX_LEN && lut_half >= max_len - 1, "dec_self_attn: max_len <= P5_MAX_LEN, lut covers it");
+  const dim3 grid((R * H + 3) / 4), block(256);
+  if (max_len <= 64) {
+    P5_PROF_TAG(sizeof(T) == 2 ? "bf16 NP=8" : "fp32 NP=8");
+    P5_LAUNCH((p5_dec_self_attn2_kernel<T, 8>), grid, block, 0, s, (T*)out, (const T*)qkv, (T*)cache, anc_odd, anc_even, rel_table, lut, lut_half, R, H, step,
+              max_len, done);
+  } else {
+    P5_PROF_TAG(sizeof(T) == 2 ? "bf16 NP=16" : "fp32 NP=16");
+    P5_LAUNCH((p5_dec_self_attn2_kernel<T, P5_MAX_LEN / 8>), grid, block, 0, s, (T*)out, (const T*)qkv, (T*)cache, anc_odd, anc_even, rel_table, lut, lut_half,
+              R, H, step, max_len, done);
+  }
+  return P5_KCHECK();
+}
+
+// LDS of the fused-q cross-attention: q image 2 KiB + scores 8.25 + probabilities 2 x 4.25 + stats + K/V chunk images 2 x 16 KiB + normalised
+// rows + the head's Wq slice + reduction buffer
+template <class T>
+static bool cross_fuseq_fits(int d) {
+  constexpr int EPS = SkT<T>::EPS;
+  return sizeof(T) == 2 && d >= EPS && d % EPS == 0 && (d / EPS) * (2048 + 64 * 128) + 3072 + 19712 + 2 * 16384 <= 136 * 1024;
+}
+// single-token cross-attention of B x Kb beam rows (a.R = B * a.Kb): variant 3 = matrix-core kernel, 2 = scalar kernel; fuseq: the kernel
+// normalises a.x and projects q itself (bf16, d_model within cross_fuseq_fits)
+template <class T>
+static int launch_dec_cross(const P5CrossArgs& a, int B, int variant, bool fuseq, hipStream_t s) {
+  P5_REQUIRE(variant == 2 || variant == 3, "dec_cross_attn: variant 2 or 3");
+  P5_REQUIRE(B >= 1 && a.H >= 1 && a.Kb >= 1 && a.L >= 1 && a.R == B * a.Kb && a.out && a.kv && a.mask, "dec_cross_attn: shape / null argument");
+  P5_REQUIRE(a.ldkv >= 2 * a.H * 64 && a.ldkv % TT<T>::EPF == 0, "dec_cross_attn: ldkv >= 2 * inner, rows 16-byte aligned");
+  const dim3 cgrid(B * ((a.Kb + 15) / 16), a.H), block(256);
+  if (fuseq) {
+    P5_REQUIRE(cross_fuseq_fits<T>(a.d) && a.x && a.ln && a.Wq, "dec_cross_attn: fused q needs bf16 and a d_model whose rows and Wq slice fit the LDS");
+    if constexpr (sizeof(T) == 2) {
+      if (variant == 3) { P5_PROF_TAG("bf16 fuseq"); P5_LAUNCH((p5_dec_cross_attn3_kernel<T, true, 136>), cgrid, block, 0, s, a); }
+      else { P5_PROF_TAG("bf16 fuseq"); P5_LAUNCH((p5_dec_cross_attn2_kernel<T, true, 128>), cgrid, block, 0, s, a); }
+    }
+  } else {
+    P5_REQUIRE(a.q != nullptr, "dec_cross_attn: q");
+    P5_PROF_TAG(dtype_name<T>());
+    if (variant == 3) P5_LAUNCH((p5_dec_cross_attn3_kernel<T, false, sizeof(T) == 2 ? 52 : 96>), cgrid, block, 0, s, a);
+    else P5_LAUNCH((p5_dec_cross_attn2_kernel<T, false, sizeof(T) == 2 ? 48 : 80>), cgrid, block, 0, s, a);
+  }
+  return P5_KCHECK();
+}
+
+// the rows' best K2 trie children (score desc, child asc).  streaming: log-sum-exp from the head's per-tile partials, logits recomputed as dot
+// products (p5_dec_score2_kernel); else from materialised logits [R, ldl] (p5_dec_score_kernel)
+struct P5ScoreArgs {
+  const float* part_m; const float* part_s; int ntiles; const void* hn; const void* E; int d; float alpha;      // streaming
+  const float* logits; int ldl, V;                                                                              // materialised
+  const int* node; const float* run_score; const int* child_off; const int* child_tok; const int* child_node;
+  const uint32_t* excluded; int excl_words, Kb, max_c, K2;
+  float* cand_scratch; float* top_score; int* top_c; int* n_top;
+  const int* done;
+};
+template <class T>
+static int launch_dec_score(bool streaming, int R, const P5ScoreArgs& a, hipStream_t s) {
+  P5_REQUIRE(R >= 1 && a.Kb >= 1 && a.max_c >= 1 && a.K2 >= 1 && (a.excl_words >= 0) && (!a.excluded || a.excl_words > 0), "dec_score: shape");
+  P5_REQUIRE(a.cand_scratch || a.max_c <= (streaming ? P5_POOL : P5_ROW_LDS_CAND), "dec_score: fan-outs beyond the LDS pool need cand_scratch [R, max_c]");
+  if (streaming) {
+    P5_REQUIRE(a.K2 <= P5_MAX_K2 || a.max_c <= 256, "dec_score: K2 <= P5_MAX_K2 when fan-outs above 256 take the radix select (its compacted list lives in LDS)");
+    P5_REQUIRE(a.ntiles >= 1 && a.d >= 8 * TT<T>::EPF && a.d % (8 * TT<T>::EPF) == 0 && a.d <= 1024, "dec_score: d_model a multiple of 8 x 16 bytes, <= 1024");
+    P5_LAUNCH((p5_dec_score2_kernel<T>), dim3(R), dim3(256), 0, s, a.top_score, a.top_c, a.n_top, a.cand_scratch, a.part_m, a.part_s, a.ntiles, (const T*)a.hn,
+              (const T*)a.E, a.d, a.alpha, a.node, a.run_score, a.child_off, a.child_tok, a.child_node, a.excluded, a.excl_words, a.Kb, a.max_c, a.K2, a.done);
+  } else {
+    P5_REQUIRE(a.V >= 1 && a.ldl >= a.V && a.ldl % 4 == 0, "dec_score: ldl >= V, a multiple of 4");
+    P5_LAUNCH(p5_dec_score_kernel, dim3(R), dim3(256), 0, s, a.cand_scratch, a.top_score, a.top_c, a.n_top, a.logits, a.ldl, a.V, a.node, a.run_score,
+              a.child_off, a.child_tok, a.child_node, a.excluded, a.excl_words, a.Kb, a.max_c, a.K2, a.done);
+  }
+  return P5_KCHECK();
+}
 
 template <class T>
 static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len, hipStream_t s) {
@@ -1452,39 +1552,21 @@ static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len,
   const int d = c.d_model, in = e->inner, H = c.n_heads, F = c.d_ff, R = B * K;
   const int* done = w.st.flags + 4;
   float* x = w.x32;       // holds E32[last token] of every row: written by the previous beam step (or the initial state)
-  constexpr int EPS = SkT<T>::EPS;
-  // LDS of the fused kernel: q image 2 KiB + scores 8.25 + probabilities 2 x 4.25 + stats + K/V chunk images 2 x 16 KiB + normalised
-  // rows + the head's Wq slice + reduction buffer
   const int sk_resid = g_opt_dec_atomic ? P5_SK_ATOMIC : P5_SK_RESID;      // how the o / wo projections update the fp32 residual stream
-  const bool fuseq = g_opt_dec_fuseq && sizeof(T) == 2 && (d / EPS) * (2048 + 64 * 128) + 3072 + 19712 + 2 * 16384 <= 136 * 1024;
+  const bool fuseq = g_opt_dec_fuseq && cross_fuseq_fits<T>(d);
   for (int i = 0; i < c.n_dec_layers; ++i) {
     const LayerOff& lo = e->dec[i];
     // ---- self-attention: qkv = norm(x) Wqkv^T ; attention over the ancestry-indexed cache ; x += o Wo^T ----
     P5_TRY(skinny<T>(s, 1, x, d, e->P + lo.sa.ln, Wc<T>(e, lo.sa.q), d, w.qkv, 3 * in, R, 3 * in, d, P5_SK_STORE, 1.f, c.eps, done));
-    if (max_len <= 64)
-      P5_LAUNCH((p5_dec_self_attn2_kernel<T, 8>), dim3((R * H + 3) / 4), dim3(256), 0, s, (T*)w.o, (const T*)w.qkv, (T*)w.cache[i], (const int*)w.st.anc,
-                (const int*)w.st.anc_next, (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, R, H, (const int*)(w.st.flags + 2), max_len, done);
-    else
-      P5_LAUNCH((p5_dec_self_attn2_kernel<T, P5_MAX_LEN / 8>), dim3((R * H + 3) / 4), dim3(256), 0, s, (T*)w.o, (const T*)w.qkv, (T*)w.cache[i], (const int*)w.st.anc,
-                (const int*)w.st.anc_next, (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, R, H, (const int*)(w.st.flags + 2), max_len, done);
-    P5_TRY(P5_KCHECK());
+    P5_TRY(launch_dec_self_attn<T>(w.o, w.qkv, w.cache[i], (const int*)w.st.anc, (const int*)w.st.anc_next, (const float*)(e->P + e->off_dec_rel), e->lut_dec,
+                                   e->lut_half, R, H, (const int*)(w.st.flags + 2), max_len, done, s));
     P5_TRY(skinny<T>(s, 0, w.o, in, nullptr, Wc<T>(e, lo.sa.o), in, x, d, R, d, in, sk_resid, 1.f, 0.f, done));
     // ---- cross-attention ----
     P5CrossArgs a;
     a.out = w.o; a.q = w.q; a.x = x; a.ln = e->P + lo.ca.ln; a.Wq = Wc<T>(e, lo.ca.q); a.kv = w.kv_cross[i]; a.mask = w.mask_copy;
     a.R = R; a.H = H; a.Kb = K; a.L = L; a.d = d; a.eps = c.eps; a.done = done; a.ldkv = w.ldkv;
-    const dim3 cgrid(B * ((K + 15) / 16), H);
-    if (fuseq) {
-      if constexpr (sizeof(T) == 2) {
-        if (g_opt_dec_cross == 3) P5_LAUNCH((p5_dec_cross_attn3_kernel<T, true, 136>), cgrid, dim3(256), 0, s, a);
-        else P5_LAUNCH((p5_dec_cross_attn2_kernel<T, true, 128>), cgrid, dim3(256), 0, s, a);
-      }
-    } else {
-      P5_TRY(skinny<T>(s, 1, x, d, e->P + lo.ca.ln, Wc<T>(e, lo.ca.q), d, w.q, in, R, in, d, P5_SK_STORE, 1.f, c.eps, done));
-      if (g_opt_dec_cross == 3) P5_LAUNCH((p5_dec_cross_attn3_kernel<T, false, sizeof(T) == 2 ? 52 : 96>), cgrid, dim3(256), 0, s, a);
-      else P5_LAUNCH((p5_dec_cross_attn2_kernel<T, false, sizeof(T) == 2 ? 48 : 80>), cgrid, dim3(256), 0, s, a);
-    }
-    P5_TRY(P5_KCHECK());
+    if (!fuseq) P5_TRY(skinny<T>(s, 1, x, d, e->P + lo.ca.ln, Wc<T>(e, lo.ca.q), d, w.q, in, R, in, d, P5_SK_STORE, 1.f, c.eps, done));
+    P5_TRY(launch_dec_cross<T>(a, B, g_opt_dec_cross == 3 ? 3 : 2, fuseq, s));
     P5_TRY(skinny<T>(s, 0, w.o, in, nullptr, Wc<T>(e, lo.ca.o), in, x, d, R, d, in, sk_resid, 1.f, 0.f, done));
     // ---- feed-forward ----
     if (c.gated_gelu) {
@@ -1500,8 +1582,7 @@ static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len,
   }
   // logits = (norm(x) * d^-0.5) E^T   (P5_T5.py:352-361)
   const int Vp = (c.vocab_size + 63) / 64 * 64;
-  P5_LAUNCH((p5_rmsnorm_f32in_kernel<T>), dim3((R + 3) / 4), dim3(256), 0, s, (T*)w.hn, (const float*)x, (const float*)(e->P + e->off_dec_fln), R, d, c.eps, done);
-  P5_TRY(P5_KCHECK());
+  P5_TRY(launch_rmsnorm_f32in<T>(w.hn, (const float*)x, (const float*)(e->P + e->off_dec_fln), R, d, c.eps, done, s));
   const float alpha = 1.0f / sqrtf((float)d);
   if (head_nv(e) > 0) return launch_head_lse<T>(e, w.part_m, w.part_s, w.hn, R, done, s);
   return linear_fwd<T>(s, w.hn, d, Wc<T>(e, e->off_E), w.logits, Vp, R, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1);
@@ -1585,17 +1666,16 @@ static int decode_step_body(P5Engine* e, hipStream_t s) {
   const uint32_t* excl = excl_words > 0 ? w.excluded : nullptr;
   const int* done = w.st.flags + 4;
   P5_TRY(decode_step2<T>(e, w, B, L, K, max_len, s));
-  if (head_nv(e) > 0) {
-    const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
-    P5_LAUNCH((p5_dec_score2_kernel<T>), dim3(R), dim3(256), 0, s, w.row_top_score, w.row_top_c, w.n_cand, w.cand, (const float*)w.part_m,
-              (const float*)w.part_s, nt, (const T*)w.hn, Wc<T>(e, e->off_E), d, 1.0f / sqrtf((float)d), (const int*)w.st.run_node,
-              (const float*)w.st.run_score, g.child_off, g.child_tok, g.child_node, excl, excl_words, K, max_c, 2 * K, done);
-  } else {
-    P5_LAUNCH(p5_dec_score_kernel, dim3(R), dim3(256), 0, s, w.cand, w.row_top_score, w.row_top_c, w.n_cand, (const float*)w.logits, Vp,
-              c.vocab_size, (const int*)w.st.run_node, (const float*)w.st.run_score, g.child_off, g.child_tok, g.child_node, excl, excl_words, K, max_c,
-              2 * K, done);
+  {
+    const int nv = head_nv(e);
+    P5ScoreArgs a;
+    a.part_m = w.part_m; a.part_s = w.part_s; a.ntiles = nv > 0 ? (c.vocab_size + nv - 1) / nv : 0; a.hn = w.hn; a.E = Wc<T>(e, e->off_E); a.d = d;
+    a.alpha = 1.0f / sqrtf((float)d); a.logits = w.logits; a.ldl = Vp; a.V = c.vocab_size;
+    a.node = w.st.run_node; a.run_score = w.st.run_score; a.child_off = g.child_off; a.child_tok = g.child_tok; a.child_node = g.child_node;
+    a.excluded = excl; a.excl_words = excl_words; a.Kb = K; a.max_c = max_c; a.K2 = 2 * K;
+    a.cand_scratch = w.cand; a.top_score = w.row_top_score; a.top_c = w.row_top_c; a.n_top = w.n_cand; a.done = done;
+    P5_TRY(launch_dec_score<T>(nv > 0, R, a, s));
   }
-  P5_TRY(P5_KCHECK());
   P5_LAUNCH(p5_beam_step_kernel, dim3(B), dim3(256), 0, s, w.st, (const float*)w.row_top_score, (const int*)w.row_top_c,
             (const int*)w.n_cand, g.child_off, g.child_tok, g.child_node, max_c, K, max_len, c.eos_id, R);
   return P5_KCHECK();
@@ -1880,17 +1960,20 @@ static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* o
   // (with split products the tied head is one throughput GEMM into materialised logits: the streaming head multiplies on exact-fp32 MFMAs)
   if (head_nv(e) > 0 && !(sizeof(T) == 4 && g_opt_verify_split)) {
     P5_TRY(launch_head_lse<T>(e, w.part_m, w.part_s, w.hn, rows, nullptr, s));
-    const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
-    P5_LAUNCH((p5_dec_score2_kernel<T>), dim3(rows), dim3(256), 0, s, w.row_top_score, w.row_top_c, w.n_top, w.cand, (const float*)w.part_m,
-              (const float*)w.part_s, nt, (const T*)w.hn, Wc<T>(e, e->off_E), d, alpha, (const int*)w.node_flat, (const float*)w.zeros, v.child_off,
-              v.child_tok, v.child_node, excl, v.excl_words, PU, v.max_c, 2 * K, (const int*)nullptr);
   } else {
     P5_TRY(linear_fwd<T>(s, w.hn, d, Wc<T>(e, e->off_E), w.logits, Vp, rows, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
-    P5_LAUNCH(p5_dec_score_kernel, dim3(rows), dim3(256), 0, s, w.cand, w.row_top_score, w.row_top_c, w.n_top, (const float*)w.logits, Vp, c.vocab_size,
-              (const int*)w.node_flat, (const float*)w.zeros, v.child_off, v.child_tok, v.child_node, excl, v.excl_words, PU, v.max_c, 2 * K,
-              (const int*)nullptr);
   }
-  P5_TRY(P5_KCHECK());
+  {
+    const bool streaming = head_nv(e) > 0 && !(sizeof(T) == 4 && g_opt_verify_split);
+    const int nv = head_nv(e);
+    P5ScoreArgs a;
+    a.part_m = w.part_m; a.part_s = w.part_s; a.ntiles = nv > 0 ? (c.vocab_size + nv - 1) / nv : 0; a.hn = w.hn; a.E = Wc<T>(e, e->off_E); a.d = d; a.alpha = alpha;
+    a.logits = w.logits; a.ldl = Vp; a.V = c.vocab_size;
+    a.node = w.node_flat; a.run_score = w.zeros; a.child_off = v.child_off; a.child_tok = v.child_tok; a.child_node = v.child_node;
+    a.excluded = excl; a.excl_words = v.excl_words; a.Kb = PU; a.max_c = v.max_c; a.K2 = 2 * K;
+    a.cand_scratch = w.cand; a.top_score = w.row_top_score; a.top_c = w.row_top_c; a.n_top = w.n_top; a.done = nullptr;
+    P5_TRY(launch_dec_score<T>(streaming, rows, a, s));
+  }
   // REPLAY with the real beam width
   P5_LAUNCH(p5_beam_init_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, w.st, v.child_off, v.child_tok, v.child_node, v.roots, B, K, max_len,
             c.pad_id);
@@ -3724,20 +3807,49 @@ int p5_op_skinny_gemm(int dtype, int amode, const void* A, int lda, const float*
 // single-token cross-attention of R = B * Kb beam rows (q given, not fused): variant 3 = MFMA kernel, 2 = scalar kernel
 int p5_op_dec_cross_attn(int dtype, int variant, void* out, const void* q, const void* kv, const int64_t* mask, int B, int H, int Kb, int L,
                          void* stream) {
+  return p5_op_dec_cross_attn_ex(dtype, variant, out, q, nullptr, nullptr, nullptr, kv, 2 * H * 64, mask, B, H, Kb, L, 0, 0.f, nullptr, stream);
+}
+// ---- kernels of the decode step (p5_decode2.h, p5_decode.h) through the launchers the engine uses (tests/decode_matrix.py) ----
+int p5_op_dec_cross_attn_ex(int dtype, int variant, void* out, const void* q, const float* x, const float* ln, const void* Wq, const void* kv, int ldkv,
+                            const int64_t* mask, int B, int H, int Kb, int L, int d, float eps, const int* done, void* stream) {
   P5CrossArgs a;
   memset(&a, 0, sizeof(a));
-  a.out = out; a.q = q; a.kv = kv; a.mask = mask; a.R = B * Kb; a.H = H; a.Kb = Kb; a.L = L; a.d = 0; a.eps = 0.f; a.done = nullptr;
-  a.ldkv = 2 * H * 64;
-  const dim3 grid(B * ((Kb + 15) / 16), H), block(256);
+  a.out = out; a.q = q; a.x = x; a.ln = ln; a.Wq = Wq; a.kv = kv; a.ldkv = ldkv; a.mask = mask; a.R = B * Kb; a.H = H; a.Kb = Kb; a.L = L; a.d = d; a.eps = eps;
+  a.done = done;
+  const bool fuseq = x != nullptr;
+  P5_REQUIRE(!fuseq || dtype == 1, "dec_cross_attn: the fused q projection exists in bf16 only");
+  return dtype == 1 ? launch_dec_cross<bf16>(a, B, variant, fuseq, (hipStream_t)stream) : launch_dec_cross<float>(a, B, variant, fuseq, (hipStream_t)stream);
+}
+int p5_op_dec_self_attn(int dtype, void* out, const void* qkv, void* cache, const int* anc_odd, const int* anc_even, const float* rel_table, const int* lut,
+                        int lut_half, int R, int H, const int* step, int max_len, const int* done, void* stream) {
+  P5_REQUIRE(out && qkv && cache && anc_odd && anc_even && rel_table && lut && step, "dec_self_attn: null argument");
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == 1) {
-    if (variant == 3) P5_LAUNCH((p5_dec_cross_attn3_kernel<bf16, false, 52>), grid, block, 0, s, a);
-    else P5_LAUNCH((p5_dec_cross_attn2_kernel<bf16, false, 48>), grid, block, 0, s, a);
-  } else {
-    if (variant == 3) P5_LAUNCH((p5_dec_cross_attn3_kernel<float, false, 96>), grid, block, 0, s, a);
-    else P5_LAUNCH((p5_dec_cross_attn2_kernel<float, false, 80>), grid, block, 0, s, a);
-  }
-  return P5_KCHECK();
+  return dtype == 1 ? launch_dec_self_attn<bf16>(out, qkv, cache, anc_odd, anc_even, rel_table, lut, lut_half, R, H, step, max_len, done, s)
+                    : launch_dec_self_attn<float>(out, qkv, cache, anc_odd, anc_even, rel_table, lut, lut_half, R, H, step, max_len, done, s);
+}
+int p5_op_rmsnorm_f32in(int dtype, void* y, const float* x, const float* w, int rows, int d, float eps, const int* done, void* stream) {
+  P5_REQUIRE(y && x && w, "rmsnorm_f32in: null argument");
+  return dtype == 1 ? launch_rmsnorm_f32in<bf16>(y, x, w, rows, d, eps, done, (hipStream_t)stream)
+                    : launch_rmsnorm_f32in<float>(y, x, w, rows, d, eps, done, (hipStream_t)stream);
+}
+int p5_op_head_lse(int dtype, int nv, float* part_m, float* part_s, const void* hn, const void* E, int R, int d, int V, float alpha, const int* done,
+                   void* stream) {
+  P5_REQUIRE(part_m && part_s && hn && E, "head_lse: null argument");
+  return dtype == 1 ? launch_head_lse_t<bf16>(nv, (const bf16*)E, d, V, part_m, part_s, hn, R, alpha, done, (hipStream_t)stream)
+                    : launch_head_lse_t<float>(nv, (const float*)E, d, V, part_m, part_s, hn, R, alpha, done, (hipStream_t)stream);
+}
+int p5_op_dec_score(int dtype, int streaming, const float* part_m, const float* part_s, int ntiles, const void* hn, const void* E, int d, float alpha,
+                    const float* logits, int ldl, int V, const int* node, const float* run_score, const int* child_off, const int* child_tok,
+                    const int* child_node, const uint32_t* excluded, int excl_words, int R, int Kb, int max_c, int K2, float* cand_scratch,
+                    float* top_score, int* top_c, int* n_top, const int* done, void* stream) {
+  P5_REQUIRE(node && run_score && child_off && child_tok && child_node && top_score && top_c && n_top, "dec_score: null argument");
+  P5_REQUIRE(streaming ? (part_m && part_s && hn && E) : logits != nullptr, "dec_score: the inputs of the chosen kernel");
+  P5ScoreArgs a;
+  a.part_m = part_m; a.part_s = part_s; a.ntiles = ntiles; a.hn = hn; a.E = E; a.d = d; a.alpha = alpha; a.logits = logits; a.ldl = ldl; a.V = V;
+  a.node = node; a.run_score = run_score; a.child_off = child_off; a.child_tok = child_tok; a.child_node = child_node;
+  a.excluded = excluded; a.excl_words = excluded ? excl_words : 0; a.Kb = Kb; a.max_c = max_c; a.K2 = K2;
+  a.cand_scratch = cand_scratch; a.top_score = top_score; a.top_c = top_c; a.n_top = n_top; a.done = done;
+  return dtype == 1 ? launch_dec_score<bf16>(streaming != 0, R, a, (hipStream_t)stream) : launch_dec_score<float>(streaming != 0, R, a, (hipStream_t)stream);
 }
 int p5_op_tr_probe(void* out, const void* in, void* stream) {
   P5_LAUNCH(p5_tr_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned short*)out, (const unsigned short*)in);

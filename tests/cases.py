@@ -179,7 +179,7 @@ def _set_opts(be, opts):
 
 GEMM_OPT_DEFAULTS = dict(gemm_v2=0, gemm_tile=0, gemm_ksdma=1, gemm_ring=1, gemm_small_ring=1, gemm_small_ring_tiles=256, gemm_ring32=128,
                          gemm_wide=1, gemm_ws=3, gemm_ws128=1, gemm_ws128_min_k=512, gemm_wide_min_tiles=160, gemm_ring128_min_k=1024,
-                         gemm_ring128_min_tiles=128, gemm_ring_n512=1, g4_nst=3, g4_wgs=256, dec_nb=0)
+                         gemm_ring128_min_tiles=128, gemm_ring_n512=1, g4_nst=3, g4_wgs=256, dec_nb=0, dec_kw=0)
 
 
 def prof_kernels(report):

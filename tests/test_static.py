@@ -116,3 +116,28 @@ def test_every_row_kernel_launch_is_named_in_the_elem_table():
     for k, v in KERNELS.items():
         assert ("fam" in v) != ("checked_by" in v), k
         assert "fam" not in v or v["fam"] in fams, f"{k}: no row of family {v.get('fam')}"
+
+
+def test_every_decode_kernel_launch_is_named_in_the_decode_table():
+    """tests/decode_matrix.py names every kernel of p5_decode.h / p5_decode2.h / p5_decode_wide.h / p5_verify.h that p5_lib.hip launches: with
+    rows checked against float64 (decode_cases.*_ref_case) or with the existing token-exact test that reaches it (`checked_by`), so a new
+    decode kernel cannot arrive without either."""
+    from tests.decode_matrix import KERNELS, ROWS
+    defined = set()
+    for fn in ("p5_decode.h", "p5_decode2.h", "p5_decode_wide.h", "p5_verify.h"):
+        defined |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(p5_\w+)\s*\(", open(os.path.join(CSRC, fn)).read()))
+    assert len(defined) >= 25, sorted(defined)
+    launched = set()
+    for site in _launch_sites("p5_lib.hip"):
+        name = re.match(r"\(*(\w+)", site).group(1)
+        if name in defined:
+            launched.add(name)
+    assert len(launched) >= 25, sorted(launched)
+    missing = sorted(launched - set(KERNELS))
+    assert not missing, f"kernels launched by p5_lib.hip without an entry in tests/decode_matrix.py: {missing}"
+    stale = sorted(set(KERNELS) - launched)
+    assert not stale, f"tests/decode_matrix.py names kernels that the four headers no longer define or p5_lib.hip no longer launches: {stale}"
+    fams = {r["fam"] for r in ROWS}
+    for k, v in KERNELS.items():
+        assert ("fam" in v) != ("checked_by" in v), k
+        assert "fam" not in v or v["fam"] in fams, f"{k}: no row of family {v.get('fam')}"
