@@ -187,6 +187,33 @@ int p5_generate(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word
  * p5_decode_begin / p5_generate / p5_generate_draft on this engine; ignored with per-item roots, n < 2, or option "gen_ff" = 0.
  * The caller guarantees that the chain is really forced for every item of the batch (no excluded node on it). */
 int p5_generate_set_forced_prefix(P5Engine* e, const int* tokens, const int* nodes, int n);
+/* ---- trie-constrained sampling: S independent draws per user from the model's distribution over the trie's items (openp5_amd/csrc/p5_sample.h) ----
+ * What HF's sampling path computes under a PrefixConstrainedLogitsProcessor: the logits processors run before softmax, so the distribution
+ * of a step is softmax(z / temperature) RENORMALISED over the allowed children of the row's trie node (the beam search above normalises
+ * over the full vocabulary first; these log-probabilities are therefore not the beam search's).  A step is the decoder of the beam search
+ * over R = B x S rows without its vocabulary head, plus one launch that recomputes the children's logits, draws one child per row by
+ * Gumbel-max (ties: the lowest child position) and reduces log sum_allowed exp(z / temperature) in the same pass.
+ *   trie, excluded_nodes / excluded_words, max_children: as p5_generate (a child whose bit is set has probability 0; a user without any
+ *     allowed child at the start gets log-probability -inf, length 0 and an all-pad sequence).  No per-item roots.
+ *   seed, stream_ids (DEVICE uint32 [B]), draw_base: the uniform behind every Gumbel is a pure function of (seed, stream_ids[b],
+ *     draw_base + s, step, child position) -- csrc/p5_rng.h::p5_sample_row_key / p5_sample_uniform is the specification -- so a draw does
+ *     not depend on the batch it is made in: splitting users or draw ranges over several calls returns the same bits.
+ *   out_seq int32 [B, S, max_len] (pad-filled, decoder start first), out_logprob fp32 [B, S] (sum of the tokens' log-probabilities),
+ *     out_tok_logprob fp32 [B, S, max_len] by position (position 0, forced positions and positions behind </s>: 0), out_len int32 [B, S]
+ *     generated tokens up to and including </s> (0: the draw did not reach a leaf within max_len).
+ * A forced prefix (p5_generate_set_forced_prefix, option "gen_ff") is honoured as by p5_generate: its tokens have renormalised probability 1.
+ * Enqueues max_len - 1 - (forced steps) steps with plain launches and returns without synchronising; there is no early stop (a finished
+ * row is a no-op of the selection launch): pass max_len = min(max_length, depth of the trie).  The decode-step hipGraph of p5_generate is
+ * neither used nor invalidated.  Every value has one writer: two calls return the same bits.
+ * Limits: 1 <= S <= 4096, 2 <= max_len <= 128, L <= 512, temperature > 0, d_model <= 1024.
+ * The workspace (exact; max_children / excluded_words do not enter it: no buffer follows the fan-out, the bitmap is read in place): the
+ * encoder / forced-prefix buffers, cross-attention K/V, the step KV cache (n_dec_layers x max_len x R x 2 x inner x sizeof(T)), the
+ * decode-step activations and the rows' state (3 x R x max_len x 4 bytes + a few words per row). */
+int64_t p5_sample_workspace_bytes(const P5Engine* e, int B, int L, int S, int max_len, int max_children, int excluded_words);
+int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S,
+                    int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                    int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids /* device uint32 [B] */, uint32_t draw_base,
+                    float temperature, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream);
 /* ---- verified generation: the bf16 search proposes, an fp32 pass decides (openp5_amd/csrc/p5_verify.h) ----
  * The reference ranks by the fp32 scores of HF beam search (DistributedRunner.py:361-387, utils/evaluate.py:37-58).  Protocol, two engines
  * over the SAME master parameter arena (a bf16 one for the draft, an fp32 one -- dtype 0 -- for the verification), one stream:

@@ -26,6 +26,7 @@
 #include "p5_cand.h"
 #include "p5_prune.h"
 #include "p5_bound.h"
+#include "p5_sample.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -1546,11 +1547,14 @@ static int launch_dec_score(bool streaming, int R, const P5ScoreArgs& a, hipStre
   return P5_KCHECK();
 }
 
+// `step`: device int holding cur_len (default: the beam state's counter flags[2]); head = false stops behind the final T5LayerNorm -- w.hn is
+// what a caller that needs no full-vocabulary log-sum-exp reads (sampling, p5_sample.h)
 template <class T>
-static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len, hipStream_t s) {
+static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len, hipStream_t s, const int* step = nullptr, bool head = true) {
   const P5Config& c = e->c;
   const int d = c.d_model, in = e->inner, H = c.n_heads, F = c.d_ff, R = B * K;
   const int* done = w.st.flags + 4;
+  if (!step) step = w.st.flags + 2;
   float* x = w.x32;       // holds E32[last token] of every row: written by the previous beam step (or the initial state)
   const int sk_resid = g_opt_dec_atomic ? P5_SK_ATOMIC : P5_SK_RESID;      // how the o / wo projections update the fp32 residual stream
   const bool fuseq = g_opt_dec_fuseq && cross_fuseq_fits<T>(d);
@@ -1559,7 +1563,7 @@ static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len,
     // ---- self-attention: qkv = norm(x) Wqkv^T ; attention over the ancestry-indexed cache ; x += o Wo^T ----
     P5_TRY(skinny<T>(s, 1, x, d, e->P + lo.sa.ln, Wc<T>(e, lo.sa.q), d, w.qkv, 3 * in, R, 3 * in, d, P5_SK_STORE, 1.f, c.eps, done));
     P5_TRY(launch_dec_self_attn<T>(w.o, w.qkv, w.cache[i], (const int*)w.st.anc, (const int*)w.st.anc_next, (const float*)(e->P + e->off_dec_rel), e->lut_dec,
-                                   e->lut_half, R, H, (const int*)(w.st.flags + 2), max_len, done, s));
+                                   e->lut_half, R, H, step, max_len, done, s));
     P5_TRY(skinny<T>(s, 0, w.o, in, nullptr, Wc<T>(e, lo.sa.o), in, x, d, R, d, in, sk_resid, 1.f, 0.f, done));
     // ---- cross-attention ----
     P5CrossArgs a;
@@ -1583,24 +1587,18 @@ static int decode_step2(P5Engine* e, GenWs& w, int B, int L, int K, int max_len,
   // logits = (norm(x) * d^-0.5) E^T   (P5_T5.py:352-361)
   const int Vp = (c.vocab_size + 63) / 64 * 64;
   P5_TRY(launch_rmsnorm_f32in<T>(w.hn, (const float*)x, (const float*)(e->P + e->off_dec_fln), R, d, c.eps, done, s));
+  if (!head) return 0;
   const float alpha = 1.0f / sqrtf((float)d);
   if (head_nv(e) > 0) return launch_head_lse<T>(e, w.part_m, w.part_s, w.hn, R, done, s);
   return linear_fwd<T>(s, w.hn, d, Wc<T>(e, e->off_E), w.logits, Vp, R, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1);
 }
 
-// ---- the search as three calls (p5_decode_begin / p5_decode_step / p5_decode_finish); p5_generate strings them together ----
+// ---- what every decode loop starts from (beam search and sampling): the encoder pass (or the encoder output handed in), the forced-prefix
+// pass when one applies (*ff_out: the prefix taken, n = 0 for none) and the cross-attention K/V of every layer; `w` is laid out, K = rows per user ----
 template <class T>
-static int decode_begin_impl(P5Engine* e, int B, int L, int K, int max_len, const int* child_off, const int* child_tok, const int* child_node,
-                             const int* roots, const uint32_t* excluded, int excl_words, int max_c, char* ws, hipStream_t s) {
+static int gen_prepare(P5Engine* e, GenWs& w, int B, int L, int K, int max_len, const int* roots, hipStream_t s, P5Forced* ff_out) {
   const P5Config& c = e->c;
   const int d = c.d_model, in = e->inner, R = B * K;
-  GenCtx& g = e->gen;
-  g.active = false;
-  layout_gen(e, ws, B, L, K, max_len, max_c, excl_words, &g.w);
-  GenWs& w = g.w;
-  w.st.hist = e->gen_hist_next;       // (p5_generate_draft) one-shot
-  e->gen_hist_next = nullptr;
-  if (!excluded) excl_words = 0;
   e->B = B; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
   if (e->enc_ext_next) {
     // the encoder output of the verification pass (fp32, same weights), rounded once to this engine's dtype: one encoder pass per batch
@@ -1639,6 +1637,26 @@ static int decode_begin_impl(P5Engine* e, int B, int L, int K, int max_len, cons
   } else {     // K/V projections of every decoder layer in ONE GEMM over the contiguous weight block (build_layout)
     P5_TRY(linear_fwd<T>(s, e->enc_out, d, Wc<T>(e, e->dec[0].ca.k), w.kv_cross[0], w.ldkv, B * L, c.n_dec_layers * 2 * in, d));
   }
+  *ff_out = ff;
+  return 0;
+}
+
+// ---- the search as three calls (p5_decode_begin / p5_decode_step / p5_decode_finish); p5_generate strings them together ----
+template <class T>
+static int decode_begin_impl(P5Engine* e, int B, int L, int K, int max_len, const int* child_off, const int* child_tok, const int* child_node,
+                             const int* roots, const uint32_t* excluded, int excl_words, int max_c, char* ws, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int R = B * K;
+  GenCtx& g = e->gen;
+  g.active = false;
+  layout_gen(e, ws, B, L, K, max_len, max_c, excl_words, &g.w);
+  GenWs& w = g.w;
+  w.st.hist = e->gen_hist_next;       // (p5_generate_draft) one-shot
+  e->gen_hist_next = nullptr;
+  if (!excluded) excl_words = 0;
+  P5Forced ff;
+  P5_TRY(gen_prepare<T>(e, w, B, L, K, max_len, roots, s, &ff));
+  const int F = ff.n;
   P5_LAUNCH(p5_beam_init_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, w.st, child_off, child_tok, child_node, roots, B, K, max_len,
             c.pad_id);
   P5_TRY(P5_KCHECK());
@@ -1767,6 +1785,85 @@ static int decode_finish_impl(P5Engine* e, int* out_seq, float* out_score, int* 
   P5_TRY(P5_KCHECK());
   g.active = false;
   return 0;
+}
+
+// ---- trie-constrained sampling (p5_sample.h): S independent draws per user, R = B * S decode rows ----
+// The workspace holds what the decoder of the step reads and writes and the rows' state: no logits, no head partials, no candidate lists.
+static int64_t layout_sample(P5Engine* e, char* base, int B, int L, int S, int max_len, GenWs* g, P5SampleState* ps) {
+  const P5Config& c = e->c;
+  const size_t sz = c.dtype == 1 ? 2 : 4;
+  const int d = c.d_model, in = e->inner, F = c.d_ff;
+  const size_t R = (size_t)B * S;
+  const int ffcap = g_opt_gen_ff ? (max_len - 2 < P5_FF_MAX ? (max_len - 2 > 0 ? max_len - 2 : 0) : P5_FF_MAX) : 0;
+  const int64_t enc_bytes = layout_ws(e, base, B, L, ffcap, false);
+  Bump b{base, (size_t)enc_bytes};
+  GenWs tmp;
+  GenWs& w = g ? *g : tmp;
+  memset(&w, 0, sizeof(w));
+  w.ff_labels = (int64_t*)b.take((size_t)B * (ffcap > 0 ? ffcap : 1) * 8);
+  w.ff_nll = (float*)b.take((size_t)B * (ffcap > 0 ? ffcap : 1) * 4);
+  {
+    char* kv_all = (char*)b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz);
+    w.ldkv = c.n_dec_layers * 2 * in;
+    for (int i = 0; i < c.n_dec_layers; ++i) {
+      w.kv_cross[i] = base ? (void*)(kv_all + (size_t)i * 2 * in * sz) : nullptr;
+      w.cache[i] = b.take((size_t)max_len * R * 2 * in * sz);
+    }
+  }
+  w.qkv = b.take(R * 3 * in * sz); w.q = b.take(R * in * sz); w.o = b.take(R * in * sz);
+  w.h = b.take(R * (c.gated_gelu ? 3 : 1) * F * sz); w.hn = b.take(R * d * sz);
+  w.x32 = (float*)b.take(R * d * 4);
+  P5SampleState st;
+  memset(&st, 0, sizeof(st));
+  st.seq = (int*)b.take(R * max_len * 4);
+  st.tok_lp = (float*)b.take(R * max_len * 4);
+  st.anc = (int*)b.take(R * max_len * 4);
+  st.sum_lp = (float*)b.take(R * 4); st.node = (int*)b.take(R * 4); st.len = (int*)b.take(R * 4);
+  st.steps = (int*)b.take((size_t)(max_len + 1) * 4);
+  st.flags = (int*)b.take(64);
+  st.x32 = w.x32;
+  st.E32 = e->P ? e->P + e->off_E : nullptr;
+  st.d = d;
+  // the decoder of the step finds the ancestry (one table: rows never change places) and its done flag where the beam state keeps them
+  w.st.anc = st.anc; w.st.anc_next = st.anc; w.st.flags = st.flags;
+  if (ps) *ps = st;
+  return (int64_t)((b.off + 255) & ~(size_t)255);
+}
+
+template <class T>
+static int sample_items_impl(P5Engine* e, int B, int L, int S, int max_len, const int* child_off, const int* child_tok, const int* child_node,
+                             const uint32_t* excluded, int excl_words, int max_c, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base,
+                             float tau, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, char* ws, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int d = c.d_model, R = B * S;
+  GenWs w;
+  P5SampleState st;
+  layout_sample(e, ws, B, L, S, max_len, &w, &st);
+  e->gen.active = false;              // (a search begun on this engine shared the encoder buffers: it cannot be continued)
+  e->gen_hist_next = nullptr;
+  if (!excluded) excl_words = 0;
+  w.mask_copy = (int64_t*)e->mask;    // plain launches: the caller's arrays are read in place
+  P5Forced ff;
+  P5_TRY(gen_prepare<T>(e, w, B, L, S, max_len, nullptr, s, &ff));
+  const int F = ff.n;
+  P5_LAUNCH(p5_sample_init_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, st, ff, child_off, child_tok, child_node, B, S, max_len, c.pad_id,
+            c.pad_id);
+  P5_TRY(P5_KCHECK());
+  P5SampleArgs a;
+  a.hn = w.hn; a.E = Wc<T>(e, e->off_E); a.d = d; a.alpha = 1.0f / sqrtf((float)d); a.tau = tau;
+  a.child_off = child_off; a.child_tok = child_tok; a.child_node = child_node;
+  a.excluded = excl_words > 0 ? excluded : nullptr; a.excl_words = excl_words;
+  a.S = S; a.R = R; a.max_c = max_c; a.max_len = max_len; a.eos_id = c.eos_id;
+  a.seed = seed; a.stream_ids = stream_ids; a.draw_base = draw_base;
+  // no early stop and nothing read back: every draw runs to its leaf, finished rows are no-ops of the selection
+  for (int cur_len = F + 1; cur_len < max_len; ++cur_len) {
+    P5_TRY(decode_step2<T>(e, w, B, L, S, max_len, s, (const int*)(st.steps + cur_len), false));
+    a.cur_len = cur_len;
+    P5_LAUNCH((p5_sample_step_kernel<T>), dim3(R), dim3(256), 0, s, st, a);
+    P5_TRY(P5_KCHECK());
+  }
+  P5_LAUNCH(p5_sample_finish_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, out_seq, out_logprob, out_tok_logprob, out_len, st, R, max_len);
+  return P5_KCHECK();
 }
 
 // ---- verified generation (p5_verify.h): plan -> encode -> run on an fp32 engine bound to the same master parameters ----
@@ -3321,6 +3418,34 @@ int p5_generate_set_forced_prefix(P5Engine* e, const int* tokens, const int* nod
   e->ff_next.n = n < P5_FF_MAX ? n : P5_FF_MAX;
   for (int i = 0; i < e->ff_next.n; ++i) { e->ff_next.tok[i] = tokens[i]; e->ff_next.node[i] = nodes[i]; }
   return 0;
+}
+int64_t p5_sample_workspace_bytes(const P5Engine* e, int B, int L, int S, int max_len, int max_children, int excluded_words) {
+  (void)max_children; (void)excluded_words;       // (no buffer follows the fan-out, and the exclusion bitmap is read in place)
+  P5Engine tmp = *e;
+  return layout_sample(&tmp, nullptr, B, L, S, max_len, nullptr, nullptr);
+}
+int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S,
+                    int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                    int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base, float temperature,
+                    int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_REQUIRE(B >= 1 && S >= 1 && S <= P5_WIDE_MAX_K, "sample_items: 1 <= samples per user <= 4096");
+  P5_REQUIRE(max_len >= 2 && max_len <= P5_MAX_LEN, "sample_items: 2 <= max_length <= 128 (P5_MAX_LEN)");
+  P5_REQUIRE(L >= 1 && L <= 512, "1 <= L <= 512");
+  P5_REQUIRE(max_children >= 1, "max_children");
+  P5_REQUIRE(e->lut_half >= max_len, "bucket LUT too short");
+  P5_REQUIRE(temperature > 0.f && temperature < __builtin_huge_valf(), "sample_items: temperature > 0");
+  P5_REQUIRE(excluded_words >= 0 && (excluded_nodes || excluded_words == 0), "excluded_nodes / excluded_words");
+  P5_REQUIRE(stream_ids && out_seq && out_logprob && out_tok_logprob && out_len, "sample_items: stream_ids / outputs");
+  P5_REQUIRE(e->c.d_model % (8 * (e->c.dtype == 1 ? 8 : 4)) == 0 && e->c.d_model <= 1024, "sample_items: d_model a multiple of 8 x 16 bytes, <= 1024");
+  const int64_t need = layout_sample(e, nullptr, B, L, S, max_len, nullptr, nullptr);
+  P5_REQUIRE(ws_bytes >= need, "sample_items: workspace too small (p5_sample_workspace_bytes)");
+  e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
+  return e->c.dtype == 1
+             ? sample_items_impl<bf16>(e, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed,
+                                       stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream)
+             : sample_items_impl<float>(e, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed,
+                                        stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream);
 }
 int64_t p5_generate_history_count(int B, int K, int max_len) { return 4 + (int64_t)max_len * P5_HIST_FIELDS * B * K; }
 int p5_generate_draft(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int K,

@@ -43,5 +43,28 @@ __device__ static inline uint32_t p5_seed(const P5Drop& d) {
   return d.state ? (d.state[0] + d.state[1] * 0x632BE5ABu) : 0u;
 }
 
+// ---- uniforms of trie-constrained sampling (p5_sample.h).  This comment is the specification; tests restate it in Python. ----
+// The uniform of one Gumbel is a pure function of five coordinates: the call's seed, the user's stream id, the draw index of the row
+// (draw_base + row within the user), the step (position of the token being drawn in the sequence: 1 = the first token behind the decoder
+// start) and the child's position in the node's CSR list.  One p5_mix32 round per coordinate, NESTED -- every coordinate enters the output
+// of the previous round -- so that two distinct coordinate tuples cannot cancel the way a sum or xor of independent terms can:
+//   k = mix32(seed ^ mix32(stream * 0x9E3779B1 + 0x7F4A7C15))
+//   k = mix32(k ^ draw)
+//   k = mix32(k + 0x9E3779B9 * (step + 1))          <- p5_sample_row_key: uniform over a decode row, computed once per row and step
+//   h = mix32(k ^ child)
+//   u = ((h >> 9) + 0.5) * 2^-23                    <- p5_sample_uniform
+// All integer arithmetic is modulo 2^32.  u takes the 2^23 values (j + 0.5) / 2^23: each is exact in fp32 (24 significant bits), so
+// 2^-24 <= u <= 1 - 2^-24 and u is never 0 or 1; with 24 hash bits, (h >> 8) + 0.5f would round to 2^24 for the largest j and give u = 1.
+// The Gumbel of the child is g = -logf(-logf(u)).
+__host__ __device__ static inline uint32_t p5_sample_row_key(uint32_t seed, uint32_t stream, uint32_t draw, uint32_t step) {
+  uint32_t k = p5_mix32(seed ^ p5_mix32(stream * 0x9E3779B1u + 0x7F4A7C15u));
+  k = p5_mix32(k ^ draw);
+  return p5_mix32(k + 0x9E3779B9u * (step + 1u));
+}
+__host__ __device__ static inline float p5_sample_uniform(uint32_t row_key, uint32_t child) {
+  const uint32_t h = p5_mix32(row_key ^ child);
+  return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
+}
+
 // site numbering (shared with oracle.t5_oracle.site_id)
 static inline uint32_t p5_site_id(int stack, int layer, int which) { return (uint32_t)((stack * 64 + layer) * 8 + which); }

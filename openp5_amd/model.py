@@ -192,7 +192,7 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
-        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
+        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("sample": sample_items() / generate(do_sample=True); "rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
                            "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0,
                            "search_calls": 0, "search_certified_users": 0, "search_fallback_users": 0, "search_declined_users": 0,
@@ -220,6 +220,9 @@ class P5T5Native(nn.Module):
         self._search_hook = None            # test hook: _search_hook(round, sel [nb, rows], n_rows [nb]) after each round's header read; may edit sel in place
         self._search_seed_hook = None       # test hook: _search_seed_hook(seeds int64 [B, S, T]) before the search begins; may edit the sequences in place
         self.cand_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}      # score_candidates()
+        self.sample_stats = {"calls": 0, "users": 0, "engine_calls": 0, "rows_per_call": 0, "forced_prefix_steps": 0}      # sample_items()
+        self._sample_seed0 = int(seed) & 0xFFFFFFFF      # sample_items(seed=None): call n of this model draws with seed mix32(seed0 + golden * (n + 1))
+        self._sample_calls = 0
         self._warned_wide_verified = False
         self._shadow_t = None       # transposed bf16 copy of the layer weights (data gradients run on the forward GEMM kernel)
         self._grads_dead = False    # zero_grad(set_to_none=True) was called and no backward has run since: `.grad` holds stale values
@@ -743,7 +746,12 @@ class P5T5Native(nn.Module):
         """Constrained beam search (DistributedRunner.py:361-371).  `prefix_allowed_tokens_fn` made by
         `openp5_amd.trie.prefix_allowed_tokens_fn` -- or by the reference's own generation_trie.prefix_allowed_tokens_fn,
         whose closure holds the Trie -- runs fully on the device.  `trie` may be passed directly (Trie / CompiledTrie).
-        `excluded`: optional uint32 [B, words] bitmap from `CompiledTrie.excluded_bitmap` -- per-user history exclusion."""
+        `excluded`: optional uint32 [B, words] bitmap from `CompiledTrie.excluded_bitmap` -- per-user history exclusion.
+        `do_sample=True` (with num_beams=1; `num_return_sequences` draws per user, `temperature`, optional `seed` / `streams` / `draw_base`)
+        draws items instead of searching: see `sample_items`, whose sequences and log-probabilities ("sequences_scores") it returns."""
+        if unused.get("do_sample"):
+            return self._generate_sampled(input_ids, attention_mask, whole_word_ids, max_length, prefix_allowed_tokens_fn, num_beams, num_return_sequences,
+                                          output_scores, return_dict_in_generate, trie, roots, excluded, unused)
         dev = self._be.device
         K = int(num_beams)
         nret = int(num_return_sequences or K)
@@ -1282,6 +1290,233 @@ class P5T5Native(nn.Module):
         sequences = item_tokens[item_index.clamp(min=0)] * (item_index >= 0).unsqueeze(-1)       # (no candidate at this rank: the all-pad sequence)
         return {"scores": scores, "order": order.to(torch.int64), "item_index": item_index, "sequences": sequences.reshape(B * N, -1),
                 "sequences_scores": score.reshape(B * N)}
+
+    # ------------------------------------------------------------------ trie-constrained sampling (csrc/p5_sample.h)
+    SAMPLE_MAX_S = 4096           # draws per user of one engine call (the decode step's rows-per-user limit); more go in draw ranges
+
+    @staticmethod
+    def _mix32(x):
+        x &= 0xFFFFFFFF
+        x ^= x >> 16
+        x = (x * 0x7FEB352D) & 0xFFFFFFFF
+        x ^= x >> 15
+        x = (x * 0x846CA68B) & 0xFFFFFFFF
+        return x ^ (x >> 16)
+
+    def _generate_sampled(self, input_ids, attention_mask, whole_word_ids, max_length, prefix_allowed_tokens_fn, num_beams, num_return_sequences,
+                          output_scores, return_dict_in_generate, trie, roots, excluded, kw):
+        """generate(do_sample=True, ...): the arguments HF users pass, checked against what is built, then `_sample`."""
+        supported = "generate(do_sample=True) supports num_beams=1, num_return_sequences, temperature, excluded, seed, streams, draw_base"
+        if int(num_beams) != 1:
+            raise ValueError(f"generate(do_sample=True, num_beams={num_beams}): beam sampling is not built; {supported}")
+        if kw.get("top_k") not in (None, 0):
+            raise ValueError(f"generate(do_sample=True, top_k={kw.get('top_k')}): top-k truncation is not built; {supported}")
+        if kw.get("top_p") not in (None, 1, 1.0):
+            raise ValueError(f"generate(do_sample=True, top_p={kw.get('top_p')}): nucleus truncation is not built; {supported}")
+        if roots is not None:
+            raise ValueError(f"generate(do_sample=True, roots=...): per-user roots are not built; {supported}")
+        if trie is None and prefix_allowed_tokens_fn is not None:
+            trie = find_trie(prefix_allowed_tokens_fn)
+            if trie is None:
+                raise ValueError(f"generate(do_sample=True): the prefix_allowed_tokens_fn must be made from a Trie (per-user roots are not built); {supported}")
+        if trie is None:
+            raise ValueError("generate() needs a trie / prefix_allowed_tokens_fn (OpenP5 always decodes under the item trie)")
+        trie = self._compiled_trie(trie)
+        excl_np = None
+        if excluded is not None:
+            excl_np = np.ascontiguousarray(excluded.cpu().numpy() if torch.is_tensor(excluded) else excluded, dtype=np.uint32)
+        S = int(num_return_sequences or 1)
+        seq, lp, _, _ = self._sample(input_ids, attention_mask, whole_word_ids, trie, S, float(kw.get("temperature") or 1.0), excl_np, kw.get("seed"),
+                                     kw.get("streams"), int(kw.get("draw_base") or 0), max_length=max_length)
+        B = seq.shape[0]
+        sequences = seq.reshape(B * S, -1).to(torch.int64)
+        if return_dict_in_generate:
+            return {"sequences": sequences, "sequences_scores": lp.reshape(B * S) if output_scores else None}
+        return sequences
+
+    @torch.no_grad()
+    def sample_items(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, num_samples: int = 1, temperature: float = 1.0,
+                     excluded_items=None, seed: Optional[int] = None, streams=None, draw_base: int = 0):
+        """Draw `num_samples` items per user from the model's distribution over the catalogue (on-policy samples for preference / policy-
+        gradient fine-tuning, exploration, Monte-Carlo estimates).  What HF's sampling path computes under the item trie: at every step
+        softmax(logits / temperature) renormalised over the allowed children of the prefix, one child drawn (Gumbel-max on the device,
+        csrc/p5_sample.h), until </s>.  The draw runs on the model's own engine and dtype -- `generation_mode` does not apply -- and the
+        returned log-probabilities are those of the distribution that was sampled.
+        `excluded_items`: per-user lists of item indices (the order given to `CompiledTrie.index_items`; an unindexed trie is indexed on
+        demand in lexicographic order) that have probability 0; the rest is renormalised.
+        `seed` (None: a fresh one from a per-model counter seeded by the model's seed), `streams` (one uint32 id per user, default
+        arange(B): pass dataset user ids to make a user's draws independent of batch composition) and `draw_base` (index of the first
+        draw) are the coordinates of the counter-based uniforms (csrc/p5_rng.h): a draw is a pure function of (weights, the user's input,
+        seed, stream, draw index), so user chunks (at most `wide_max_rows` decode rows per engine call) and draw ranges (`num_samples` >
+        4096, or split by hand with `draw_base`) do not change a bit of the result.
+        Returns {"sequences" int64 [B * S, T] (decoder start first, pad-filled; T = depth of the trie), "sequences_logprob" fp32 [B * S]
+        (-inf for a user with nothing to draw), "token_logprobs" fp32 [B * S, T - 1] (0 at forced-prefix positions and behind </s>),
+        "item_index" int64 [B, S] (-1 for a user with nothing to draw; None for a trie with an appended trie, which cannot be indexed)}."""
+        if trie is None:
+            raise ValueError("sample_items() needs the item trie (Trie / CompiledTrie)")
+        trie = self._compiled_trie(trie)
+        S = int(num_samples)
+        if S < 1:
+            raise ValueError(f"sample_items(num_samples={num_samples}): at least one draw per user")
+        if not trie.grafted and getattr(trie, "item_edges", None) is None:
+            trie.index_items(trie.enumerate_items())
+        excl_np = None
+        if excluded_items is not None:
+            if trie.grafted:
+                raise ValueError("sample_items(excluded_items=...): a trie with an appended trie (Trie.append) cannot be indexed")
+            if len(excluded_items) != input_ids.shape[0]:
+                raise ValueError(f"excluded_items: one list of item indices per user ({input_ids.shape[0]}), got {len(excluded_items)}")
+            n_items = int(trie.item_edges.shape[0])
+            for b, items in enumerate(excluded_items):
+                it = np.asarray(list(items), dtype=np.int64)
+                if it.size and (it.min() < 0 or it.max() >= n_items):
+                    raise ValueError(f"excluded_items[{b}]: item indices must be in 0 .. {n_items - 1}")
+            excl_np = trie.excluded_bitmap(excluded_items)
+        seq, lp, tok_lp, ln = self._sample(input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base)
+        B, _, T = seq.shape
+        item_index = None
+        if not trie.grafted:
+            item_index = self._sampled_item_index(trie, seq.reshape(B * S, T), ln.reshape(B * S)).view(B, S)
+        return {"sequences": seq.reshape(B * S, T).to(torch.int64), "sequences_logprob": lp.reshape(B * S),
+                "token_logprobs": tok_lp.reshape(B * S, T)[:, 1:].contiguous(), "item_index": item_index}
+
+    def _sampled_item_index(self, trie, seq, ln):
+        """item index of every drawn sequence [R, T] (ln [R] generated tokens): the trie walked on the device, one sorted lookup of
+        (node, token) per position, then the item of the leaf reached; -1 where the draw did not reach a leaf"""
+        dev = seq.device
+        key = (str(dev), "sample")
+        if key not in trie._dev_items:
+            V = int(trie.child_tok.max()) + 1 if trie.child_tok.size else 1
+            nodes = np.repeat(np.arange(trie.n_nodes, dtype=np.int64), np.diff(trie.child_off.astype(np.int64)))
+            keys = nodes * V + trie.child_tok.astype(np.int64)
+            order = np.argsort(keys, kind="stable")
+            paths = trie.item_paths
+            last = np.maximum((paths >= 0).sum(axis=1) - 1, 0)
+            leaf_item = np.full(trie.n_nodes, -1, dtype=np.int64)
+            leaf_item[paths[np.arange(paths.shape[0]), last]] = np.arange(paths.shape[0], dtype=np.int64)
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+            trie._dev_items[key] = (V, t(keys[order]), t(trie.child_node.astype(np.int64)[order]), t(leaf_item))
+        V, keys, edge_node, leaf_item = trie._dev_items[key]
+        R, T = seq.shape
+        node = torch.zeros(R, dtype=torch.int64, device=dev)
+        ok = ln > 0
+        tok = seq.to(torch.int64)
+        for t in range(T):
+            active = ok & (ln >= t)
+            q = node * V + tok[:, t].clamp(max=V - 1)
+            pos = torch.searchsorted(keys, q).clamp(max=keys.numel() - 1)
+            hit = (keys[pos] == q) & (tok[:, t] < V)
+            node = torch.where(active & hit, edge_node[pos], node)
+            ok = ok & (hit | ~active)
+        return torch.where(ok, leaf_item[node], torch.full_like(node, -1))
+
+    def _sample(self, input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, max_length=None):
+        """The engine calls of sample_items / generate(do_sample=True): (sequences int32 [B, S, T], log-probability [B, S], per-position
+        log-probabilities [B, S, T], generated tokens [B, S]).  `excl_np`: uint32 [B, words] excluded-node bitmap or None."""
+        lib, dev = self._lib, self._be.device
+        tau = float(temperature)
+        if not (tau > 0.0 and math.isfinite(tau)):
+            raise ValueError(f"temperature={temperature!r}: a finite value > 0")
+        off, tok, nxt = trie.device_arrays(dev)
+        input_ids = self._i64(input_ids, dev)
+        B, L = input_ids.shape
+        if whole_word_ids is None:
+            whole_word_ids = torch.zeros_like(input_ids)
+        whole_word_ids = self._i64(whole_word_ids, dev)
+        if attention_mask is None:
+            attention_mask = (input_ids != self.config.pad_token_id).long()
+        attention_mask = self._i64(attention_mask, dev)
+        depth = int(trie.max_depth)
+        T = max(2, depth if max_length is None else min(int(max_length), depth))
+        if T > 128:
+            raise ValueError(f"sampling: items of {T} tokens, at most 128")
+        if streams is None:
+            st_np = np.arange(B, dtype=np.uint32)
+        else:
+            st_np = np.asarray(streams.cpu().numpy() if torch.is_tensor(streams) else streams).astype(np.int64).reshape(-1)
+            if st_np.shape[0] != B:
+                raise ValueError(f"streams: one id per user ({B}), got {st_np.shape[0]}")
+            st_np = (st_np & 0xFFFFFFFF).astype(np.uint32)
+        streams_t = torch.from_numpy(st_np.view(np.int32).copy()).to(dev)
+        draw_base = int(draw_base)
+        if draw_base < 0 or draw_base + S > 2 ** 32:
+            raise ValueError(f"draw_base={draw_base}: draw indices are uint32")
+        if seed is None:
+            with self._stats_lock:
+                n = self._sample_calls
+                self._sample_calls += 1
+            seed = self._mix32(self._sample_seed0 + 0x9E3779B9 * (n + 1))
+        seed = int(seed) & 0xFFFFFFFF
+        excl_t, excl_words = None, 0
+        if excl_np is not None:
+            if excl_np.ndim != 2 or excl_np.shape[0] != B or excl_np.shape[1] * 32 < trie.n_nodes:
+                raise ValueError(f"excluded bitmap must be [B={B}, >= {(trie.n_nodes + 31) // 32}] uint32, got {excl_np.shape}")
+            excl_words = int(excl_np.shape[1])
+            excl_t = torch.from_numpy(np.ascontiguousarray(excl_np).view(np.int32)).to(dev)
+        self._sync_shadow()
+        self._sync_transposed()
+        # forced-prefix fast-forward, under generate()'s rule -- no user is fast-forwarded through an excluded node -- applied per user: every
+        # item lies behind the chain, so a user whose exclusion touches it has nothing to draw and is answered here (-inf, the all-pad
+        # sequence: what the kernel answers a user without an allowed child); the others keep the fast-forward, and their bits do not
+        # depend on that user being in the batch
+        ftok, fnode = [], []
+        alive = np.arange(B)
+        if self.prefix_fast_forward:
+            ftok, fnode = trie.forced_prefix(self.config.decoder_start_token_id, self.config.eos_token_id)
+            n = min(len(ftok), T - 2)
+            ftok, fnode = (ftok[:n], fnode[:n]) if n >= 2 else ([], [])
+            if ftok and excl_np is not None:
+                words = excl_np[:, [x >> 5 for x in fnode]]
+                bits = np.asarray([x & 31 for x in fnode], dtype=np.uint32)
+                alive = np.nonzero(~((words >> bits[None, :]) & 1).any(axis=1))[0]
+        lane = self._cur_lane()
+        engine, sp = lane.engine, self._be.stream_ptr()
+        maxc = max(1, trie.max_children)
+        seq = torch.empty(B, S, T, dtype=torch.int32, device=dev)
+        lp = torch.empty(B, S, dtype=torch.float32, device=dev)
+        tok_lp = torch.empty(B, S, T, dtype=torch.float32, device=dev)
+        ln = torch.empty(B, S, dtype=torch.int32, device=dev)
+        nA = int(alive.size)
+        if nA < B:
+            seq.fill_(self.config.pad_token_id)
+            seq[:, :, 0] = self.config.decoder_start_token_id
+            lp.fill_(-math.inf)
+            tok_lp.zero_()
+            ln.zero_()
+            alive_t = torch.from_numpy(alive).to(dev)
+        # at most `wide_max_rows` decode rows per engine call: draw ranges of a user first, then users
+        s_per = max(1, min(S, self.SAMPLE_MAX_S, int(self.wide_max_rows)))
+        u_per = max(1, int(self.wide_max_rows) // s_per)
+        calls = 0
+        for s0 in range(0, S, s_per):
+            sc = min(s_per, S - s0)
+            for a in range(0, nA, u_per):
+                b = min(nA, a + u_per)
+                nb = b - a
+                whole = nb == B and sc == S
+                users = slice(a, b) if nA == B else alive_t[a:b]
+                cut = lambda t: None if t is None else (t if nb == B else t[users].contiguous())      # noqa: E731
+                o_seq = seq if whole else torch.empty(nb, sc, T, dtype=torch.int32, device=dev)
+                o_lp = lp if whole else torch.empty(nb, sc, dtype=torch.float32, device=dev)
+                o_tok = tok_lp if whole else torch.empty(nb, sc, T, dtype=torch.float32, device=dev)
+                o_ln = ln if whole else torch.empty(nb, sc, dtype=torch.int32, device=dev)
+                if ftok:
+                    arr = (ctypes.c_int * len(ftok))
+                    self._be.check(lib.p5_generate_set_forced_prefix(engine, arr(*ftok), arr(*fnode), len(ftok)), "p5_generate_set_forced_prefix")
+                ws = self._lane_workspace(lane, lib.p5_sample_workspace_bytes(engine, nb, L, sc, T, maxc, excl_words), "sample")
+                ids_c, ww_c, mask_c, ex_c, st_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(excl_t), cut(streams_t)
+                self._be.check(lib.p5_sample_items(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, sc, T, _ptr(off), _ptr(tok), _ptr(nxt), _ptr(ex_c),
+                                                   excl_words, maxc, seed, _ptr(st_c), (draw_base + s0) & 0xFFFFFFFF, tau, _ptr(o_seq), _ptr(o_lp),
+                                                   _ptr(o_tok), _ptr(o_ln), _ptr(ws), ws.numel(), sp), "p5_sample_items")
+                if not whole:
+                    seq[users, s0:s0 + sc], lp[users, s0:s0 + sc], tok_lp[users, s0:s0 + sc], ln[users, s0:s0 + sc] = o_seq, o_lp, o_tok, o_ln
+                calls += 1
+        with self._stats_lock:
+            st = self.sample_stats
+            st["calls"] += 1; st["users"] += B; st["engine_calls"] += calls; st["rows_per_call"] = min(nA, u_per) * s_per
+            st["forced_prefix_steps"] = len(ftok)
+        self.last_generate_path = "sample"
+        return seq, lp, tok_lp, ln
 
     def _in_user_chunks(self, fn, args):
         """fn(*args) for a search wider than the narrow step, over consecutive chunks of users of at most `wide_max_rows` decode rows each,
