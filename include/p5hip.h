@@ -519,6 +519,58 @@ int p5_op_dec_score(int dtype, int streaming, const float* part_m, const float* 
                     float alpha, const float* logits, int ldl, int V, const int* node, const float* run_score, const int* child_off,
                     const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, int R, int Kb, int max_c, int K2,
                     float* cand_scratch, float* top_score, int* top_c, int* n_top, const int* done, void* stream);
+/* ---- catalogue ranking (csrc/p5_rank.h, p5_cand.h, p5_prune.h, p5_bound.h and p5_tree_attn_row) through the launch helpers the engine uses;
+ * tests/rank_matrix.py.  Layout of a pass: B * CQ * nchunk rows, row ru of user b at ((ru / CQ) * B + b) * CQ + ru % CQ. ---- */
+/* the streaming head's tile (rows of E per workgroup) the engine picks for a model of this type and width; 0: materialised logits */
+int p5_op_head_nv(int dtype, int d_model);
+/* items 1: scores [B, n_items] = the depth-ordered sum of edge_lp [B, n_edges] over item_edges [n_items, path_len] (-1 ends a path) / the
+ * number of edges (none: -1e9), then the selection; 2: the item scores only; 0: scores are given.  Selection: per user the top_n items by
+ * (score desc, index asc) outside the bitmap excluded [B, ceil(n_items / 32)] -> out_index / out_score [B, top_n] (-1 / -1e9 beyond the live
+ * items; with items 2 part, out_index and out_score may be null).  grid (host, may be null) receives G, S of the first stage; part: [B, G, top_n] 64-bit scratch, G <= 64 */
+int p5_op_rank_select(int items, float* scores, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len,
+                      const uint32_t* excluded, unsigned long long* part, int B, int top_n, int* out_index, float* out_score, int* grid, void* stream);
+/* edge_lp[b, child_off[nd] + i] = log_softmax(d^-0.5 hn[g] . E^T)[child_tok[..]] for every child i of node nd = row_node[plan row] of every pass
+ * row g that is no padding; plan row = the user's row (< rows) or, with sel [B, cap] / n_rows [B], sel[b][row].  nv > 0: streaming head of
+ * that tile (p5_op_head_lse's conditions), head fp32 [2, HC, ceil(V / nv)]; nv 0: materialised logits, head fp32 [HC, V rounded up to 64].
+ * HC = rows per head chunk.  d a multiple of 64 (bf16) / 32 (fp32), <= 1024 */
+int p5_op_rank_edges(int dtype, int nv, float* edge_lp, int64_t n_edges, const void* hn, const void* E, int d, int V, float* head, int HC,
+                     const int* row_node, int rows, int B, int CQ, int nchunk, const int* sel, const int* n_rows, int cap, const int* child_off,
+                     const int* child_tok, void* stream);
+/* row_lse[g] = log sum exp(d^-0.5 hn[g] . E^T) for the R rows of a pass, by the two head routes of p5_op_rank_edges */
+int p5_op_cand_row_lse(int dtype, int nv, float* row_lse, const void* hn, const void* E, int d, int V, float* head, int HC, int R, void* stream);
+/* self-attention of every pass row over its ancestors and itself; qkv T [R, 3*H*64], out T [R, H*64], bias rel_table[lut[t - depth + lut_half]*H + h].
+ * variant 0 (p5_rank_tree_attn_kernel): plan rows row_depth [rows], anc [rows, max_depth]; 1 (p5_cand_tree_attn_kernel): the same plan through
+ * sel / n_rows; 2 (p5_tree_attn_kernel): row_depth = depth per pass row [B * CQ], anc [B, cap, max_depth], nchunk 1 */
+int p5_op_tree_attn(int dtype, int variant, void* out, const void* qkv, const int* row_depth, const int* anc, int rows, int max_depth, int B, int CQ,
+                    int nchunk, const int* sel, const int* n_rows, int cap, const float* rel_table, const int* lut, int lut_half, int H, void* stream);
+/* p5_cand_plan_kernel + p5_cand_hdr_kernel: sel [B, cap], n_rows [B], hdr[0] = the largest n_rows; keys [B, P] scratch */
+int p5_op_cand_plan(int* sel, int* n_rows, int* hdr, unsigned long long* keys, const int* cand, const int* item_rows, int B, int C, int n_items,
+                    int path_len, int cap, int P, void* stream);
+/* p5_cand_rows_kernel: decoder input ids [B * CQ * nchunk] of a pass over sel */
+int p5_op_cand_rows(int64_t* ids, const int* row_tok, int B, int CQ, int nchunk, const int* sel, const int* n_rows, int cap, int pad_id, void* stream);
+/* p5_cand_score_kernel + p5_cand_order_kernel: scores [B, C], out_order / out_index / out_score [B, top_n] */
+int p5_op_cand_score(int dtype, float* scores, const void* hn, const void* E, int d, const float* row_lse, int B, int CQ, int nchunk, const int* sel,
+                     const int* n_rows, int cap, const int* cand, int C, const int* item_rows, const int64_t* item_tok, int ldt, int n_items,
+                     int path_len, int* out_order, int* out_index, float* out_score, int top_n, void* stream);
+int p5_op_prune_fill(float* p, int64_t n, float v, void* stream);
+/* p5_prune_propose_kernel + p5_cand_hdr_kernel: sel [B, rows], n_rows [B], hdr[0]; top_score [B, N] */
+int p5_op_prune_propose(int* sel, int* n_rows, int* hdr, const float* edge_lp, int64_t n_edges, const float* top_score, int N, const int* row_depth,
+                        const int* anc, int rows, int max_depth, const int* row_edge, const int* row_lmax, float slack, int B, void* stream);
+int p5_op_prune_mask(uint32_t* out, const uint32_t* excluded, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len,
+                     int B, void* stream);
+/* p5_prune_certify_kernel over sel [B, cap] / n_rows of a pass of CQ * nchunk rows per user: flagged[b] = 1 unless the list is proven complete */
+int p5_op_prune_certify(int* flagged, const float* edge_lp, int64_t n_edges, const int* row_depth, const int* row_node, const int* anc, int max_depth,
+                        int B, int CQ, int nchunk, const int* sel, const int* n_rows, int cap, const int* row_edge, const int* edge_row,
+                        const int* row_lmax, const int* child_off, const int* out_index, const float* out_score, int N, float margin, void* stream);
+/* p5_bound_seed_kernel + p5_bound_union_kernel + p5_bound_hdr_kernel: seeds int64 [B, S, T]; keys [B, KP], KP a power of two >= S * max_depth + 1 */
+int p5_op_bound_seed(int* sel, int* n_rows, int* hdr, unsigned long long* keys, int KP, int cap, const int64_t* seeds, int S, int T,
+                     const int* child_off, const int* child_tok, const int* edge_row, const int* row_tok, const int* row_node, int max_depth, int B,
+                     void* stream);
+/* p5_bound_expand_kernel + p5_bound_hdr_kernel: sel / n_rows read and written, grew [B], hdr = (largest n_rows, users that grew) */
+int p5_op_bound_expand(int* sel, int* n_rows, int* grew, int* hdr, unsigned long long* keys, int KP, const float* edge_lp, int64_t n_edges,
+                       const int* row_depth, const int* row_node, const int* anc, int max_depth, int B, int CQ, int nchunk, int cap,
+                       const int* row_edge, const int* edge_row, const int* row_lmax, const int* child_off, const float* out_score, int N, float margin,
+                       void* stream);
 int p5_op_tr_probe(void* out64x4_u16, const void* in256_u16, void* stream);  /* ds_read_b64_tr_b16 semantics probe */
 
 #ifdef __cplusplus

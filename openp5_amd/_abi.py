@@ -119,6 +119,20 @@ PROTOTYPES = {
     "p5_op_rmsnorm_f32in": (i32, [i32, vp, vp, vp, i32, i32, f32, vp, vp]),
     "p5_op_head_lse": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp]),
     "p5_op_dec_score": (i32, [i32, i32, vp, vp, i32, vp, vp, i32, f32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "p5_op_head_nv": (i32, [i32, i32]),
+    "p5_op_rank_select": (i32, [i32, vp, vp, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "p5_op_rank_edges": (i32, [i32, i32, vp, i64, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "p5_op_cand_row_lse": (i32, [i32, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp]),
+    "p5_op_tree_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp]),
+    "p5_op_cand_plan": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "p5_op_cand_rows": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp]),
+    "p5_op_cand_score": (i32, [i32, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "p5_op_prune_fill": (i32, [vp, i64, f32, vp]),
+    "p5_op_prune_propose": (i32, [vp, vp, vp, vp, i64, vp, i32, vp, vp, i32, i32, vp, vp, f32, i32, vp]),
+    "p5_op_prune_mask": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, vp]),
+    "p5_op_prune_certify": (i32, [vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, f32, vp]),
+    "p5_op_bound_seed": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]),
+    "p5_op_bound_expand": (i32, [vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, vp]),
     "p5_op_tr_probe": (i32, [vp, vp, vp]),
     "p5_profile_begin": (i32, []),
     "p5_profile_end": (i32, [C.c_char_p, i32]),

@@ -29,9 +29,10 @@ __device__ static __forceinline__ float p5_okey_inv(unsigned o) {
   c.u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
   return c.f;
 }
-// candidate key: larger = better.  Finite scores only (0 marks "no candidate"; p5_okey of a finite float is never 0)
+// candidate key: larger = better.  Finite scores only (0 marks "no candidate"; p5_okey of a finite float is never 0).  -0.0 and +0.0 tie as
+// numbers but p5_okey orders their bits, so a zero of either sign takes +0.0's key: between them the index decides (score desc, index asc)
 __device__ static __forceinline__ unsigned long long p5_wkey(float v, unsigned idx) {
-  return ((unsigned long long)p5_okey(v) << 32) | (unsigned long long)(~idx);
+  return ((unsigned long long)p5_okey(v == 0.f ? 0.f : v) << 32) | (unsigned long long)(~idx);
 }
 
 // exclusive prefix sum of one int per thread over the 256 threads; `total` = the block's sum (s_w: 4 ints of LDS)

@@ -1426,17 +1426,18 @@ static int skinny(hipStream_t s, int amode, const void* A, int lda, const float*
 
 // streaming head: rows of E kept in LDS per workgroup (0 = materialised-logits path): the largest of 128/64/32/16 whose tile
 // fits 128 KiB (bf16 d_model 512 -> 128, 768/1024 -> 64; fp32 512 -> 64, 768/1024 -> 32)
-static int head_nv(const P5Engine* e) {
+static int head_nv_of(int dtype, int d_model) {       // (p5_op_head_nv reports it: tests/rank_matrix.py)
   if (!g_opt_dec_head) return 0;
   // the kernel walks K in units of eight 64-byte chunks (p5_decode2.h): d_model % 256 (bf16) / % 128 (fp32) -- every T5 size;
   // other widths (toy models) take the materialised-logits head
-  if (e->c.d_model % (e->c.dtype == 1 ? 256 : 128) != 0) return 0;
-  const size_t row = (size_t)e->c.d_model * (e->c.dtype == 1 ? 2 : 4);
+  if (d_model % (dtype == 1 ? 256 : 128) != 0) return 0;
+  const size_t row = (size_t)d_model * (dtype == 1 ? 2 : 4);
   if (g_opt_dec_head_nv) return (size_t)g_opt_dec_head_nv * row <= 128 * 1024 ? g_opt_dec_head_nv : 0;
   for (int nv = 128; nv >= 16; nv >>= 1)
     if ((size_t)nv * row <= 128 * 1024) return nv;
   return 0;
 }
+static int head_nv(const P5Engine* e) { return head_nv_of(e->c.dtype, e->c.d_model); }
 
 // streaming tied head over R rows: per vocabulary tile (max, sum exp) only; the logits the search needs are recomputed by p5_dec_score2_kernel.
 // nv = rows of E per workgroup, one of head_nv()'s values for (T, d); part_m / part_s: [R][ceil(V / nv)]
@@ -2029,6 +2030,28 @@ static int decoder_rows_pass(P5Engine* e, const RowsPassBufs& w, int B, int CQ, 
   return rmsnorm_fwd<T>(s, w.hn, nullptr, x, e->P + e->off_dec_fln, rows, d, c.eps, no_drop());
 }
 
+// the three launches of p5_tree_attn_row with their operands as arguments (p5_op_tree_attn runs them too)
+template <class T>
+static int verify_tree_attn(T* o, const T* qkv, const P5VerifyPlan& pl, const int* depth_flat, const float* rel_table, const int* lut, int lut_half, int B, int PU,
+                            int H, hipStream_t s) {
+  P5_PROF_TAG(sizeof(T) == 2 ? "bf16" : "fp32");
+  P5_LAUNCH((p5_tree_attn_kernel<T>), dim3((B * PU * H + 3) / 4), dim3(256), 0, s, o, qkv, pl, depth_flat, rel_table, lut, lut_half, B, PU, H);
+  return P5_KCHECK();
+}
+template <class T>
+static int rank_tree_attn(T* o, const T* qkv, const P5RankPlan& pl, const float* rel_table, const int* lut, int lut_half, int H, hipStream_t s) {
+  const long long R = (long long)pl.B * pl.CQ * pl.nchunk;
+  P5_PROF_TAG(sizeof(T) == 2 ? "bf16" : "fp32");
+  P5_LAUNCH((p5_rank_tree_attn_kernel<T>), dim3((unsigned)((R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, rel_table, lut, lut_half, H);
+  return P5_KCHECK();
+}
+template <class T>
+static int cand_tree_attn(T* o, const T* qkv, const P5CandPlan& pl, const float* rel_table, const int* lut, int lut_half, int H, hipStream_t s) {
+  const long long R = (long long)pl.g.B * pl.g.CQ * pl.g.nchunk;
+  P5_PROF_TAG(sizeof(T) == 2 ? "bf16" : "fp32");
+  P5_LAUNCH((p5_cand_tree_attn_kernel<T>), dim3((unsigned)((R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, rel_table, lut, lut_half, H);
+  return P5_KCHECK();
+}
 // SCORE + REPLAY.  PU: rows per user of this pass (>= the plan's largest row count, a multiple of 16, <= cap): the decoder runs on
 // [B x PU] rows (decoder_rows_pass, one chunk).
 template <class T>
@@ -2045,9 +2068,7 @@ static int verify_run_impl(P5Engine* e, int PU, const uint32_t* excluded, int* o
   RowsPassBufs pb;
   pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
   auto tree_attn = [&](T* o, const T* qkv) -> int {
-    P5_LAUNCH((p5_tree_attn_kernel<T>), dim3((rows * H + 3) / 4), dim3(256), 0, s, o, qkv, w.pl, (const int*)w.depth_flat,
-              (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, B, PU, H);
-    return P5_KCHECK();
+    return verify_tree_attn<T>(o, qkv, w.pl, (const int*)w.depth_flat, (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, B, PU, H, s);
   };
   P5_TRY((decoder_rows_pass<T>(e, pb, B, PU, 1, v.L, tree_attn, s)));
   // log-sum-exp over the full vocabulary per row + the log-probabilities of the row's trie children (running score 0)
@@ -2159,42 +2180,59 @@ static int64_t layout_rank(P5Engine* e, char* base, int B, int L, int rows, int6
 // tied head + the log-probability of every child edge of every row of a pass, in row chunks (the buffers of this phase do not grow with
 // the catalogue).  rs.sel == nullptr: the pass holds every plan row (rank_items_impl); else row i of user b is plan row sel[b][i]
 // (prune_decide_impl).  head: the partials of the streaming head or the logits of one chunk.
+// the part of rank_edges that takes its operands as arguments (p5_op_rank_edges runs it too): E [V][d] the tied embedding, nv the streaming
+// head's tile (head_nv; 0: materialised logits, ld = V rounded up to 64), HC_stream / HC_logits the rows per head chunk
 template <class T>
-static int rank_edges(P5Engine* e, float* edge_lp, int64_t n_edges, const void* hn_all, float* head, int HC_stream, int HC_logits, int R, const P5RankPlan& pl,
-                      P5RankSel rs, const int* child_off, const int* child_tok, int split_on, hipStream_t s) {
-  const P5Config& c = e->c;
-  const int d = c.d_model;
-  const int Vp = (c.vocab_size + 63) / 64 * 64;
+static int rank_edges_t(const T* E, int d, int V, int nv, float* edge_lp, int64_t n_edges, const void* hn_all, float* head, int HC_stream, int HC_logits, int R,
+                        const P5RankPlan& pl, P5RankSel rs, const int* child_off, const int* child_tok, hipStream_t s) {
+  const int Vp = (V + 63) / 64 * 64;
   const float alpha = 1.0f / sqrtf((float)d);
-  const bool streaming = head_nv(e) > 0 && !split_on;     // (with split products the head is a throughput GEMM into logits, as in verify_run_impl)
+  const bool streaming = nv > 0;
   const int HC = streaming ? HC_stream : HC_logits;
   for (int g0 = 0; g0 < R; g0 += HC) {
     const int nr = R - g0 < HC ? R - g0 : HC;
     const T* hn = (const T*)hn_all + (size_t)g0 * d;
     if (streaming) {
-      const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
+      const int nt = (V + nv - 1) / nv;
       float* part_m = head; float* part_s = head + (size_t)HC_stream * nt;
-      P5_TRY(launch_head_lse<T>(e, part_m, part_s, hn, nr, nullptr, s));
+      P5_TRY(launch_head_lse_t<T>(nv, E, d, V, part_m, part_s, hn, nr, alpha, nullptr, s));
+      P5_PROF_TAG(sizeof(T) == 2 ? "bf16" : "fp32");
       P5_LAUNCH((p5_rank_score_kernel<T>), dim3(nr), dim3(256), 0, s, edge_lp, (long long)n_edges, (const float*)part_m, (const float*)part_s, nt,
-                (const T*)hn_all, Wc<T>(e, e->off_E), d, alpha, pl, g0, child_off, child_tok, rs);
+                (const T*)hn_all, E, d, alpha, pl, g0, child_off, child_tok, rs);
     } else {
-      P5_TRY(linear_fwd<T>(s, hn, d, Wc<T>(e, e->off_E), head, Vp, nr, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
-      P5_LAUNCH(p5_rank_score_logits_kernel, dim3(nr), dim3(256), 0, s, edge_lp, (long long)n_edges, (const float*)head, Vp, c.vocab_size, pl, g0,
+      P5_TRY(linear_fwd<T>(s, hn, d, E, head, Vp, nr, V, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
+      P5_LAUNCH(p5_rank_score_logits_kernel, dim3(nr), dim3(256), 0, s, edge_lp, (long long)n_edges, (const float*)head, Vp, V, pl, g0,
                 child_off, child_tok, rs);
     }
     P5_TRY(P5_KCHECK());
   }
   return 0;
 }
-// item scores and the per-user top N
-static int rank_select(float* scores, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len, const uint32_t* excluded,
-                       unsigned long long* part, int G, int S, int B, int top_n, int* out_index, float* out_score, hipStream_t s) {
+template <class T>
+static int rank_edges(P5Engine* e, float* edge_lp, int64_t n_edges, const void* hn_all, float* head, int HC_stream, int HC_logits, int R, const P5RankPlan& pl,
+                      P5RankSel rs, const int* child_off, const int* child_tok, int split_on, hipStream_t s) {
+  const int nv = split_on ? 0 : head_nv(e);     // (with split products the head is a throughput GEMM into logits, as in verify_run_impl)
+  return rank_edges_t<T>(Wc<T>(e, e->off_E), e->c.d_model, e->c.vocab_size, nv, edge_lp, n_edges, hn_all, head, HC_stream, HC_logits, R, pl, rs, child_off,
+                         child_tok, s);
+}
+// item scores
+static int rank_item_scores(float* scores, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len, int B, hipStream_t s) {
   P5_LAUNCH(p5_rank_items_kernel, dim3((n_items + 255) / 256, B), dim3(256), 0, s, scores, edge_lp, (long long)n_edges, item_edges, n_items, path_len);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_rank_select_part_kernel, dim3(G, B), dim3(256), 0, s, part, (const float*)scores, excluded, (n_items + 31) / 32, n_items, S, top_n);
+  return P5_KCHECK();
+}
+// the per-user top N of scores [B][n_items] (G, S: rank_select_grid)
+static int rank_top_n(const float* scores, int n_items, const uint32_t* excluded, unsigned long long* part, int G, int S, int B, int top_n, int* out_index,
+                      float* out_score, hipStream_t s) {
+  P5_LAUNCH(p5_rank_select_part_kernel, dim3(G, B), dim3(256), 0, s, part, scores, excluded, (n_items + 31) / 32, n_items, S, top_n);
   P5_TRY(P5_KCHECK());
   P5_LAUNCH(p5_rank_select_kernel, dim3(B), dim3(256), 0, s, out_index, out_score, (const unsigned long long*)part, G, top_n);
   return P5_KCHECK();
+}
+// item scores and the per-user top N
+static int rank_select(float* scores, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len, const uint32_t* excluded,
+                       unsigned long long* part, int G, int S, int B, int top_n, int* out_index, float* out_score, hipStream_t s) {
+  P5_TRY(rank_item_scores(scores, edge_lp, n_edges, item_edges, n_items, path_len, B, s));
+  return rank_top_n(scores, n_items, excluded, part, G, S, B, top_n, out_index, out_score, s);
 }
 
 struct RankArgs {
@@ -2233,9 +2271,7 @@ static int rank_items_impl(P5Engine* e, RankArgs& r, hipStream_t s) {
   RowsPassBufs pb;
   pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
   auto tree_attn = [&](T* o, const T* qkv) -> int {
-    P5_LAUNCH((p5_rank_tree_attn_kernel<T>), dim3((unsigned)(((long long)R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, (const float*)(e->P + e->off_dec_rel),
-              e->lut_dec, e->lut_half, H);
-    return P5_KCHECK();
+    return rank_tree_attn<T>(o, qkv, pl, (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, H, s);
   };
   P5_TRY((decoder_rows_pass<T>(e, pb, B, w.CQ, w.nchunk, r.L, tree_attn, s)));
   hipMemsetAsync(r.out_flagged, 0, (size_t)B * 4, s);
@@ -2316,13 +2352,35 @@ static Bump layout_sel_pass(P5Engine* e, char* pass, int B, int L, int rows, Can
   return b;
 }
 
+// the launches of p5_cand.h with their operands as arguments (the p5_op_cand_* entries run them too)
+static int cand_plan_rows(int* sel, int* n_rows, int* hdr, unsigned long long* keys, const int* cand, const int* item_rows, int B, int C, int n_items, int path_len,
+                          int cap, int P, hipStream_t s) {
+  P5_LAUNCH(p5_cand_plan_kernel, dim3(B), dim3(256), 0, s, sel, n_rows, keys, cand, item_rows, C, n_items, path_len, cap, P);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, hdr, (const int*)n_rows, B);
+  return P5_KCHECK();
+}
+static int cand_pass_ids(int64_t* ids, const P5CandPlan& pl, int pad_id, hipStream_t s) {
+  const int R = pl.g.B * pl.g.CQ * pl.g.nchunk;
+  P5_LAUNCH(p5_cand_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, ids, pl, pad_id);
+  return P5_KCHECK();
+}
+template <class T>
+static int cand_score_order(float* scores, const T* hn, const T* E, int d, const float* row_lse, const P5CandPlan& pl, const int* cand, int C, const int* item_rows,
+                            const int64_t* item_tok, int ldt, int n_items, int path_len, int* out_order, int* out_index, float* out_score, int top_n,
+                            hipStream_t s) {
+  const float alpha = 1.0f / sqrtf((float)d);
+  P5_PROF_TAG(sizeof(T) == 2 ? "bf16" : "fp32");
+  P5_LAUNCH((p5_cand_score_kernel<T>), dim3((C + 31) / 32, pl.g.B), dim3(256), 0, s, scores, hn, E, d, alpha, row_lse, pl, cand, C, item_rows, item_tok, ldt, n_items,
+            path_len);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_cand_order_kernel, dim3(pl.g.B), dim3(256), 0, s, out_order, out_index, out_score, (const float*)scores, cand, C, n_items, top_n);
+  return P5_KCHECK();
+}
 static int cand_plan_impl(P5Engine* e, const int* cand, int B, int C, const int* item_rows, int n_items, int path_len, char* ws, hipStream_t s) {
   CandWs w;
   layout_cand(e, ws, B, 1, C, path_len, 0, &w);
-  P5_LAUNCH(p5_cand_plan_kernel, dim3(B), dim3(256), 0, s, w.sel, w.n_rows, w.keys, cand, item_rows, C, n_items, path_len, w.cap, w.P);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, B);
-  return P5_KCHECK();
+  return cand_plan_rows(w.sel, w.n_rows, w.hdr, w.keys, cand, item_rows, B, C, n_items, path_len, w.cap, w.P, s);
 }
 
 // A pass over per-user subsets of the plan's rows, in two parts (`pass`: where its buffers start, behind the plan's).  layout_sel_pass puts
@@ -2351,14 +2409,11 @@ static int sel_decode_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, c
   const int d = c.d_model, H = c.n_heads, B = pl.g.B;
   const int R = B * w.CQ * w.nchunk;
   sel_pass_bind(e, pass, input_ids, whole_word_ids, attention_mask, B, L);
-  P5_LAUNCH(p5_cand_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, s, w.ids, pl, c.pad_id);
-  P5_TRY(P5_KCHECK());
+  P5_TRY(cand_pass_ids(w.ids, pl, c.pad_id, s));
   RowsPassBufs pb;
   pb.ids = w.ids; pb.x = w.x; pb.y = w.y; pb.n = w.n; pb.qkv = w.qkv; pb.q = w.q; pb.o = w.o; pb.h = w.h; pb.hn = w.hn; pb.lse = w.lse; pb.kv_all = w.kv_all;
   auto tree_attn = [&](T* o, const T* qkv) -> int {
-    P5_LAUNCH((p5_cand_tree_attn_kernel<T>), dim3((unsigned)(((long long)R * H + 3) / 4)), dim3(256), 0, s, o, qkv, pl, (const float*)(e->P + e->off_dec_rel),
-              e->lut_dec, e->lut_half, H);
-    return P5_KCHECK();
+    return cand_tree_attn<T>(o, qkv, pl, (const float*)(e->P + e->off_dec_rel), e->lut_dec, e->lut_half, H, s);
   };
   P5_TRY((decoder_rows_pass<T>(e, pb, B, w.CQ, w.nchunk, L, tree_attn, s)));
   hipMemsetAsync(out_flagged, 0, (size_t)B * 4, s);
@@ -2374,6 +2429,30 @@ static int sel_rows_pass(P5Engine* e, const CandWs& w, const P5CandPlan& pl, cha
                          const int64_t* attention_mask, int L, int split_on, int* out_flagged, hipStream_t s) {
   P5_TRY((sel_encode_pass<T>(e, w, pass, input_ids, whole_word_ids, attention_mask, pl.g.B, L, s)));
   return sel_decode_pass<T>(e, w, pl, pass, input_ids, whole_word_ids, attention_mask, L, split_on, out_flagged, s);
+}
+
+// the log-sum-exp over the vocabulary of every row of a pass, in row chunks: rank_edges_t's two head routes (p5_op_cand_row_lse runs it too)
+template <class T>
+static int cand_row_lse_t(const T* E, int d, int V, int nv, float* row_lse, const void* hn_all, float* head, int HC_stream, int HC_logits, int R, hipStream_t s) {
+  const int Vp = (V + 63) / 64 * 64;
+  const float alpha = 1.0f / sqrtf((float)d);
+  const bool streaming = nv > 0;
+  const int HC = streaming ? HC_stream : HC_logits;
+  for (int g0 = 0; g0 < R; g0 += HC) {
+    const int nr = R - g0 < HC ? R - g0 : HC;
+    const T* hn = (const T*)hn_all + (size_t)g0 * d;
+    if (streaming) {
+      const int nt = (V + nv - 1) / nv;
+      float* part_m = head; float* part_s = head + (size_t)HC_stream * nt;
+      P5_TRY(launch_head_lse_t<T>(nv, E, d, V, part_m, part_s, hn, nr, alpha, nullptr, s));
+      P5_LAUNCH(p5_cand_lse_kernel, dim3(nr), dim3(256), 0, s, row_lse, (const float*)part_m, (const float*)part_s, nt, g0);
+    } else {
+      P5_TRY(linear_fwd<T>(s, hn, d, E, head, Vp, nr, V, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
+      P5_LAUNCH(p5_cand_lse_logits_kernel, dim3(nr), dim3(256), 0, s, row_lse, (const float*)head, Vp, V, g0);
+    }
+    P5_TRY(P5_KCHECK());
+  }
+  return 0;
 }
 
 struct CandArgs {
@@ -2400,32 +2479,12 @@ static int cand_score_impl(P5Engine* e, CandArgs& r, hipStream_t s) {
   pl.g.rows = r.rows; pl.g.max_depth = r.max_depth; pl.g.B = B; pl.g.CQ = w.CQ; pl.g.nchunk = w.nchunk;
   pl.sel = w.sel; pl.n_rows = w.n_rows; pl.cap = w.cap;
   const int R = B * w.CQ * w.nchunk;
-  const int Vp = (c.vocab_size + 63) / 64 * 64;
   P5_TRY((sel_rows_pass<T>(e, w, pl, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.L, split_on, r.out_flagged, s)));
   // tied head: the log-sum-exp of every row, in row chunks (the two routes of rank_items_impl, chosen by the same condition)
-  const float alpha = 1.0f / sqrtf((float)d);
-  const bool streaming = head_nv(e) > 0 && !split_on;
-  const int HC = streaming ? w.HC_stream : w.HC_logits;
-  for (int g0 = 0; g0 < R; g0 += HC) {
-    const int nr = R - g0 < HC ? R - g0 : HC;
-    const T* hn = (const T*)w.hn + (size_t)g0 * d;
-    if (streaming) {
-      const int nv = head_nv(e), nt = (c.vocab_size + nv - 1) / nv;
-      float* part_m = w.head; float* part_s = w.head + (size_t)w.HC_stream * nt;
-      P5_TRY(launch_head_lse<T>(e, part_m, part_s, hn, nr, nullptr, s));
-      P5_LAUNCH(p5_cand_lse_kernel, dim3(nr), dim3(256), 0, s, w.row_lse, (const float*)part_m, (const float*)part_s, nt, g0);
-    } else {
-      P5_TRY(linear_fwd<T>(s, hn, d, Wc<T>(e, e->off_E), w.head, Vp, nr, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
-      P5_LAUNCH(p5_cand_lse_logits_kernel, dim3(nr), dim3(256), 0, s, w.row_lse, (const float*)w.head, Vp, c.vocab_size, g0);
-    }
-    P5_TRY(P5_KCHECK());
-  }
+  P5_TRY((cand_row_lse_t<T>(Wc<T>(e, e->off_E), d, c.vocab_size, split_on ? 0 : head_nv(e), w.row_lse, w.hn, w.head, w.HC_stream, w.HC_logits, R, s)));
   // the candidates' scores and the per-user order
-  P5_LAUNCH((p5_cand_score_kernel<T>), dim3((r.C + 31) / 32, B), dim3(256), 0, s, w.scores, (const T*)w.hn, Wc<T>(e, e->off_E), d, alpha,
-            (const float*)w.row_lse, pl, r.cand, r.C, r.item_rows, r.item_tokens, r.ldt, r.n_items, r.path_len);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_cand_order_kernel, dim3(B), dim3(256), 0, s, r.out_order, r.out_index, r.out_score, (const float*)w.scores, r.cand, r.C, r.n_items, r.top_n);
-  P5_TRY(P5_KCHECK());
+  P5_TRY((cand_score_order<T>(w.scores, (const T*)w.hn, Wc<T>(e, e->off_E), d, w.row_lse, pl, r.cand, r.C, r.item_rows, r.item_tokens, r.ldt, r.n_items,
+                              r.path_len, r.out_order, r.out_index, r.out_score, r.top_n, s)));
   hipMemcpyAsync(r.out_scores, w.scores, (size_t)B * r.C * 4, hipMemcpyDeviceToDevice, s);
   return 0;
 }
@@ -2464,6 +2523,32 @@ static int64_t layout_prune(P5Engine* e, char* base, int B, int L, int rows_tota
   return layout_prune_pass(e, base, B, L, rows, n_edges, n_items, top_n, w);
 }
 
+// the launches of p5_prune.h with their operands as arguments (the p5_op_prune_* entries run them too)
+// PROPOSE: sel / n_rows from a pass's edge_lp and its selected scores, the largest row count into hdr[0]
+static int prune_propose_rows(int* sel, int* n_rows, int* hdr, const float* edge_lp, int64_t n_edges, const float* top_score, int N, const P5RankPlan& pl,
+                              const int* row_edge, const int* row_lmax, float slack, int B, hipStream_t s) {
+  P5_LAUNCH(p5_prune_propose_kernel, dim3(B), dim3(256), 0, s, sel, n_rows, edge_lp, (long long)n_edges, top_score, N, pl, row_edge, row_lmax, slack);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, hdr, (const int*)n_rows, B);
+  return P5_KCHECK();
+}
+static int prune_fill(float* p, size_t n, float v, hipStream_t s) {
+  P5_LAUNCH(p5_prune_fill_kernel, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, s, p, n, v);
+  return P5_KCHECK();
+}
+static int prune_mask(uint32_t* out, const uint32_t* excluded, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len, int B,
+                      hipStream_t s) {
+  const int words = (n_items + 31) / 32;
+  P5_LAUNCH(p5_prune_mask_kernel, dim3((words + 255) / 256, B), dim3(256), 0, s, out, excluded, words, edge_lp, (long long)n_edges, item_edges, n_items, path_len);
+  return P5_KCHECK();
+}
+static int prune_certify(int* flagged, const float* edge_lp, int64_t n_edges, const P5CandPlan& pl, const int* row_edge, const int* edge_row, const int* row_lmax,
+                         const int* child_off, const int* out_index, const float* out_score, int N, float margin, hipStream_t s) {
+  P5_LAUNCH(p5_prune_certify_kernel, dim3((pl.g.CQ * pl.g.nchunk + 255) / 256, pl.g.B), dim3(256), 0, s, flagged, edge_lp, (long long)n_edges, pl, row_edge,
+            edge_row, row_lmax, child_off, out_index, out_score, N, margin);
+  return P5_KCHECK();
+}
+
 template <class T>
 static int prune_propose_impl(P5Engine* e, RankArgs& r, const int* row_edge, const int* row_lmax, float slack, char* prune_ws, hipStream_t s) {
   P5_TRY(rank_items_impl<T>(e, r, s));
@@ -2471,11 +2556,7 @@ static int prune_propose_impl(P5Engine* e, RankArgs& r, const int* row_edge, con
   layout_rank(e, r.ws, r.B, r.L, r.pl.rows, r.n_edges, r.n_items, r.top_n, &w);
   PruneWs p;
   layout_prune(e, prune_ws, r.B, 1, r.pl.rows, 0, r.n_edges, r.n_items, r.top_n, &p);
-  P5_LAUNCH(p5_prune_propose_kernel, dim3(r.B), dim3(256), 0, s, p.sel, p.n_rows, (const float*)w.edge_lp, (long long)r.n_edges, (const float*)r.out_score, r.top_n,
-            r.pl, row_edge, row_lmax, slack);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_cand_hdr_kernel, dim3(1), dim3(64), 0, s, p.hdr, (const int*)p.n_rows, r.B);
-  return P5_KCHECK();
+  return prune_propose_rows(p.sel, p.n_rows, p.hdr, w.edge_lp, r.n_edges, r.out_score, r.top_n, r.pl, row_edge, row_lmax, slack, r.B, s);
 }
 
 struct PruneArgs {
@@ -2493,20 +2574,13 @@ static int prune_decide_rows(P5Engine* e, PruneArgs& a, const PruneWs& w, const 
   const int R = B * w.CQ * w.nchunk;
   P5_TRY((sel_decode_pass<T>(e, w, pl, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.L, split_on, r.out_flagged, s)));
   // the log-probability of every child edge of every sel row; every other edge keeps the sentinel
-  const size_t ne = (size_t)B * r.n_edges;
-  P5_LAUNCH(p5_prune_fill_kernel, dim3((unsigned)((ne + 255) / 256 > 4096 ? 4096 : (ne + 255) / 256)), dim3(256), 0, s, w.edge_lp, ne, P5_PRUNE_SENTINEL);
-  P5_TRY(P5_KCHECK());
+  P5_TRY(prune_fill(w.edge_lp, (size_t)B * r.n_edges, P5_PRUNE_SENTINEL, s));
   P5_TRY((rank_edges<T>(e, w.edge_lp, r.n_edges, w.hn, w.head, w.HC_stream, w.HC_logits, R, pl.g, P5RankSel{w.sel, w.n_rows, w.cap}, r.child_off, r.child_tok,
                         split_on, s)));
   // items whose path was not scored in full join the user's exclusion bitmap; then the selection of rank_items_impl
-  const int words = (r.n_items + 31) / 32;
-  P5_LAUNCH(p5_prune_mask_kernel, dim3((words + 255) / 256, B), dim3(256), 0, s, w.excl, r.excluded, words, (const float*)w.edge_lp, (long long)r.n_edges,
-            r.item_edges, r.n_items, r.path_len);
-  P5_TRY(P5_KCHECK());
+  P5_TRY(prune_mask(w.excl, r.excluded, w.edge_lp, r.n_edges, r.item_edges, r.n_items, r.path_len, B, s));
   P5_TRY(rank_select(w.scores, w.edge_lp, r.n_edges, r.item_edges, r.n_items, r.path_len, w.excl, w.part, w.G, w.S, B, r.top_n, r.out_index, r.out_score, s));
-  P5_LAUNCH(p5_prune_certify_kernel, dim3((w.CQ * w.nchunk + 255) / 256, B), dim3(256), 0, s, r.out_flagged, (const float*)w.edge_lp, (long long)r.n_edges, pl,
-            a.row_edge, a.edge_row, a.row_lmax, r.child_off, (const int*)r.out_index, (const float*)r.out_score, r.top_n, a.margin);
-  return P5_KCHECK();
+  return prune_certify(r.out_flagged, w.edge_lp, r.n_edges, pl, a.row_edge, a.edge_row, a.row_lmax, r.child_off, r.out_index, r.out_score, r.top_n, a.margin, s);
 }
 static P5CandPlan prune_pass_plan(const PruneArgs& a, const PruneWs& w) {
   P5CandPlan pl;
@@ -2558,6 +2632,30 @@ struct BoundArgs {
   const int64_t* seeds;     // [B][n_seeds][seed_len] (p5_bound_begin)
   int n_seeds, seed_len;
 };
+// the launches of p5_bound.h with their operands as arguments (the p5_op_bound_* entries run them too)
+// BEGIN: the seeds' rows into sel / n_rows, the largest row count into hdr[0] (hdr[1] = 0).  keys: [B][KP], KP a power of two >= S * max_depth + 1
+// (layout_bound sizes KP so; p5_op_bound_seed checks it)
+static int bound_seed_rows(int* sel, int* n_rows, int* hdr, unsigned long long* keys, int KP, int cap, const int64_t* seeds, int S, int T, const int* child_off,
+                           const int* child_tok, const int* edge_row, const int* row_tok, const int* row_node, int max_depth, int B, hipStream_t s) {
+  int P = 256;
+  while (P < S * max_depth + 1) P <<= 1;
+  P5_LAUNCH(p5_bound_seed_kernel, dim3((S + 255) / 256, B), dim3(256), 0, s, keys, KP, P, seeds, S, T, child_off, child_tok, edge_row, row_tok, row_node, max_depth);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_bound_union_kernel, dim3(B), dim3(256), 0, s, sel, n_rows, keys, KP, P, cap);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_bound_hdr_kernel, dim3(1), dim3(64), 0, s, hdr, (const int*)n_rows, (const int*)nullptr, B);
+  return P5_KCHECK();
+}
+// ROUND, after the certificate: the frontier rows within reach of tau join sel; hdr = (the largest row count, the users that grew)
+static int bound_expand_rows(int* sel, int* n_rows, int* grew, int* hdr, unsigned long long* keys, int KP, const float* edge_lp, int64_t n_edges,
+                             const P5CandPlan& pl, const int* row_edge, const int* edge_row, const int* row_lmax, const int* child_off, const float* out_score,
+                             int N, float margin, hipStream_t s) {
+  P5_LAUNCH(p5_bound_expand_kernel, dim3(pl.g.B), dim3(256), 0, s, sel, n_rows, grew, keys, KP, edge_lp, (long long)n_edges, pl, row_edge, edge_row, row_lmax,
+            child_off, out_score, N, margin);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_bound_hdr_kernel, dim3(1), dim3(64), 0, s, hdr, (const int*)n_rows, (const int*)grew, pl.g.B);
+  return P5_KCHECK();
+}
 template <class T>
 static int bound_begin_impl(P5Engine* e, BoundArgs& a, hipStream_t s) {
   RankArgs& r = a.p.r;
@@ -2566,15 +2664,8 @@ static int bound_begin_impl(P5Engine* e, BoundArgs& a, hipStream_t s) {
   BoundWs w;
   layout_bound(e, r.ws, r.B, r.L, r.pl.rows, 1, r.n_edges, r.n_items, r.top_n, a.n_seeds, r.pl.max_depth, &w);
   P5_TRY((sel_encode_pass<T>(e, w, r.ws + w.plan_bytes, r.input_ids, r.whole_word_ids, r.attention_mask, r.B, r.L, s)));
-  int P = 256;
-  while (P < a.n_seeds * r.pl.max_depth + 1) P <<= 1;
-  P5_LAUNCH(p5_bound_seed_kernel, dim3((a.n_seeds + 255) / 256, r.B), dim3(256), 0, s, w.keys, w.KP, P, a.seeds, a.n_seeds, a.seed_len, r.child_off, r.child_tok,
-            a.p.edge_row, r.pl.row_tok, r.pl.row_node, r.pl.max_depth);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_bound_union_kernel, dim3(r.B), dim3(256), 0, s, w.sel, w.n_rows, w.keys, w.KP, P, w.cap);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_bound_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, (const int*)nullptr, r.B);
-  return P5_KCHECK();
+  return bound_seed_rows(w.sel, w.n_rows, w.hdr, w.keys, w.KP, w.cap, a.seeds, a.n_seeds, a.seed_len, r.child_off, r.child_tok, a.p.edge_row, r.pl.row_tok,
+                         r.pl.row_node, r.pl.max_depth, r.B, s);
 }
 template <class T>
 static int bound_round_impl(P5Engine* e, BoundArgs& a, hipStream_t s) {
@@ -2585,11 +2676,8 @@ static int bound_round_impl(P5Engine* e, BoundArgs& a, hipStream_t s) {
   layout_bound(e, r.ws, r.B, r.L, r.pl.rows, a.p.rows, r.n_edges, r.n_items, r.top_n, a.n_seeds, r.pl.max_depth, &w);
   const P5CandPlan pl = prune_pass_plan(a.p, w);
   P5_TRY((prune_decide_rows<T>(e, a.p, w, pl, split_on, s)));
-  P5_LAUNCH(p5_bound_expand_kernel, dim3(r.B), dim3(256), 0, s, w.sel, w.n_rows, w.grew, w.keys, w.KP, (const float*)w.edge_lp, (long long)r.n_edges, pl,
-            a.p.row_edge, a.p.edge_row, a.p.row_lmax, r.child_off, (const float*)r.out_score, r.top_n, a.p.margin);
-  P5_TRY(P5_KCHECK());
-  P5_LAUNCH(p5_bound_hdr_kernel, dim3(1), dim3(64), 0, s, w.hdr, (const int*)w.n_rows, (const int*)w.grew, r.B);
-  return P5_KCHECK();
+  return bound_expand_rows(w.sel, w.n_rows, w.grew, w.hdr, w.keys, w.KP, w.edge_lp, r.n_edges, pl, a.p.row_edge, a.p.edge_row, a.p.row_lmax, r.child_off,
+                           r.out_score, r.top_n, a.p.margin, s);
 }
 
 // =====================================================================================================
@@ -3975,6 +4063,145 @@ int p5_op_dec_score(int dtype, int streaming, const float* part_m, const float* 
   a.excluded = excluded; a.excl_words = excluded ? excl_words : 0; a.Kb = Kb; a.max_c = max_c; a.K2 = K2;
   a.cand_scratch = cand_scratch; a.top_score = top_score; a.top_c = top_c; a.n_top = n_top; a.done = done;
   return dtype == 1 ? launch_dec_score<bf16>(streaming != 0, R, a, (hipStream_t)stream) : launch_dec_score<float>(streaming != 0, R, a, (hipStream_t)stream);
+}
+// ---- kernels of catalogue ranking (p5_rank.h, p5_cand.h, p5_prune.h, p5_bound.h, p5_tree_attn_row) through the launch helpers the engine
+// uses (tests/rank_matrix.py) ----
+static P5RankPlan op_rank_plan(const int* row_tok, const int* row_depth, const int* row_node, const int* anc, int rows, int max_depth, int B, int CQ, int nchunk) {
+  P5RankPlan pl;
+  pl.row_tok = row_tok; pl.row_depth = row_depth; pl.row_node = row_node; pl.anc = anc; pl.rows = rows; pl.max_depth = max_depth;
+  pl.B = B; pl.CQ = CQ; pl.nchunk = nchunk;
+  return pl;
+}
+int p5_op_head_nv(int dtype, int d_model) { return d_model >= 1 ? head_nv_of(dtype, d_model) : 0; }
+int p5_op_rank_select(int items, float* scores, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len,
+                      const uint32_t* excluded, unsigned long long* part, int B, int top_n, int* out_index, float* out_score, int* grid, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(scores && B >= 1 && n_items >= 1 && (items == 2 || (part && out_index && out_score)), "rank_select: null argument");
+  P5_REQUIRE(top_n >= 1 && top_n <= P5_WIDE_MAX_K, "rank_select: 1 <= top_n <= 4096");
+  int G, S;
+  rank_select_grid(n_items, top_n, G, S);
+  if (grid) { grid[0] = G; grid[1] = S; }
+  if (items) {
+    P5_REQUIRE(edge_lp && item_edges && path_len >= 1, "rank_select: the item scores need edge_lp and item_edges");
+    P5_TRY(rank_item_scores(scores, edge_lp, n_edges, item_edges, n_items, path_len, B, s));
+    if (items == 2) return 0;
+  }
+  return rank_top_n(scores, n_items, excluded, part, G, S, B, top_n, out_index, out_score, s);
+}
+int p5_op_rank_edges(int dtype, int nv, float* edge_lp, int64_t n_edges, const void* hn, const void* E, int d, int V, float* head, int HC,
+                     const int* row_node, int rows, int B, int CQ, int nchunk, const int* sel, const int* n_rows, int cap, const int* child_off,
+                     const int* child_tok, void* stream) {
+  P5_REQUIRE(edge_lp && hn && E && head && row_node && child_off && child_tok, "rank_edges: null argument");
+  P5_REQUIRE(B >= 1 && CQ >= 1 && nchunk >= 1 && HC >= 1 && d >= 1 && V >= 1 && (sel == nullptr || n_rows != nullptr), "rank_edges: shape");
+  P5_REQUIRE(d <= 1024 && d % (dtype == 1 ? 64 : 32) == 0, "rank_edges: d_model a multiple of 64 (bf16) / 32 (fp32), at most 1024");
+  const P5RankPlan pl = op_rank_plan(nullptr, nullptr, row_node, nullptr, rows, 0, B, CQ, nchunk);
+  const P5RankSel rs{sel, n_rows, cap};
+  const int R = B * CQ * nchunk;
+  return dtype == 1 ? rank_edges_t<bf16>((const bf16*)E, d, V, nv, edge_lp, n_edges, hn, head, HC, HC, R, pl, rs, child_off, child_tok, (hipStream_t)stream)
+                    : rank_edges_t<float>((const float*)E, d, V, nv, edge_lp, n_edges, hn, head, HC, HC, R, pl, rs, child_off, child_tok, (hipStream_t)stream);
+}
+int p5_op_cand_row_lse(int dtype, int nv, float* row_lse, const void* hn, const void* E, int d, int V, float* head, int HC, int R, void* stream) {
+  P5_REQUIRE(row_lse && hn && E && head && R >= 1 && HC >= 1 && d >= 1 && V >= 1, "cand_row_lse: null argument");
+  return dtype == 1 ? cand_row_lse_t<bf16>((const bf16*)E, d, V, nv, row_lse, hn, head, HC, HC, R, (hipStream_t)stream)
+                    : cand_row_lse_t<float>((const float*)E, d, V, nv, row_lse, hn, head, HC, HC, R, (hipStream_t)stream);
+}
+int p5_op_tree_attn(int dtype, int variant, void* out, const void* qkv, const int* row_depth, const int* anc, int rows, int max_depth, int B, int CQ, int nchunk,
+                    const int* sel, const int* n_rows, int cap, const float* rel_table, const int* lut, int lut_half, int H, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(out && qkv && row_depth && anc && rel_table && lut && B >= 1 && CQ >= 1 && nchunk >= 1 && H >= 1, "tree_attn: null argument");
+  P5_REQUIRE(variant >= 0 && variant <= 2 && (variant != 1 || (sel && n_rows)), "tree_attn: variant 0 rank, 1 cand (sel, n_rows), 2 verify");
+  if (variant == 2) {         // the verification plan: [B][cap] rows, anc [B][cap][max_len]; row_depth = depth_flat [B * PU], PU = CQ
+    P5_REQUIRE(nchunk == 1, "tree_attn: the verification pass has one chunk");
+    P5VerifyPlan vp;
+    memset(&vp, 0, sizeof(vp));
+    vp.anc = const_cast<int*>(anc); vp.cap = cap; vp.max_len = max_depth;
+    return dtype == 1 ? verify_tree_attn<bf16>((bf16*)out, (const bf16*)qkv, vp, row_depth, rel_table, lut, lut_half, B, CQ, H, s)
+                      : verify_tree_attn<float>((float*)out, (const float*)qkv, vp, row_depth, rel_table, lut, lut_half, B, CQ, H, s);
+  }
+  P5CandPlan pl;
+  pl.g = op_rank_plan(nullptr, row_depth, nullptr, anc, rows, max_depth, B, CQ, nchunk);
+  pl.sel = sel; pl.n_rows = n_rows; pl.cap = cap;
+  if (variant == 0)
+    return dtype == 1 ? rank_tree_attn<bf16>((bf16*)out, (const bf16*)qkv, pl.g, rel_table, lut, lut_half, H, s)
+                      : rank_tree_attn<float>((float*)out, (const float*)qkv, pl.g, rel_table, lut, lut_half, H, s);
+  return dtype == 1 ? cand_tree_attn<bf16>((bf16*)out, (const bf16*)qkv, pl, rel_table, lut, lut_half, H, s)
+                    : cand_tree_attn<float>((float*)out, (const float*)qkv, pl, rel_table, lut, lut_half, H, s);
+}
+int p5_op_cand_plan(int* sel, int* n_rows, int* hdr, unsigned long long* keys, const int* cand, const int* item_rows, int B, int C, int n_items, int path_len,
+                    int cap, int P, void* stream) {
+  P5_REQUIRE(sel && n_rows && hdr && keys && cand && item_rows && B >= 1 && n_items >= 1 && path_len >= 1, "cand_plan: null argument");
+  P5_REQUIRE(C >= 1 && C <= P5_WIDE_MAX_K, "cand_plan: 1 <= C <= 4096");
+  P5_REQUIRE(cap >= C * path_len && P >= 256 && P >= C * path_len && (P & (P - 1)) == 0, "cand_plan: cap >= C * path_len, P a power of two >= max(C * path_len, 256)");
+  return cand_plan_rows(sel, n_rows, hdr, keys, cand, item_rows, B, C, n_items, path_len, cap, P, (hipStream_t)stream);
+}
+int p5_op_cand_rows(int64_t* ids, const int* row_tok, int B, int CQ, int nchunk, const int* sel, const int* n_rows, int cap, int pad_id, void* stream) {
+  P5_REQUIRE(ids && row_tok && sel && n_rows && B >= 1 && CQ >= 1 && nchunk >= 1, "cand_rows: null argument");
+  P5CandPlan pl;
+  pl.g = op_rank_plan(row_tok, nullptr, nullptr, nullptr, 0, 0, B, CQ, nchunk);
+  pl.sel = sel; pl.n_rows = n_rows; pl.cap = cap;
+  return cand_pass_ids(ids, pl, pad_id, (hipStream_t)stream);
+}
+int p5_op_cand_score(int dtype, float* scores, const void* hn, const void* E, int d, const float* row_lse, int B, int CQ, int nchunk, const int* sel,
+                     const int* n_rows, int cap, const int* cand, int C, const int* item_rows, const int64_t* item_tok, int ldt, int n_items, int path_len,
+                     int* out_order, int* out_index, float* out_score, int top_n, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(scores && hn && E && row_lse && sel && n_rows && cand && item_rows && item_tok && out_order && out_index && out_score, "cand_score: null argument");
+  P5_REQUIRE(C >= 1 && C <= P5_WIDE_MAX_K && top_n >= 1 && top_n <= C, "cand_score: 1 <= top_n <= C <= 4096");
+  P5_REQUIRE(d >= 1 && d % (dtype == 1 ? 64 : 32) == 0, "cand_score: d_model a multiple of 64 (bf16) / 32 (fp32)");
+  P5CandPlan pl;
+  pl.g = op_rank_plan(nullptr, nullptr, nullptr, nullptr, 0, 0, B, CQ, nchunk);
+  pl.sel = sel; pl.n_rows = n_rows; pl.cap = cap;
+  return dtype == 1 ? cand_score_order<bf16>(scores, (const bf16*)hn, (const bf16*)E, d, row_lse, pl, cand, C, item_rows, item_tok, ldt, n_items, path_len, out_order,
+                                             out_index, out_score, top_n, s)
+                    : cand_score_order<float>(scores, (const float*)hn, (const float*)E, d, row_lse, pl, cand, C, item_rows, item_tok, ldt, n_items, path_len, out_order,
+                                              out_index, out_score, top_n, s);
+}
+int p5_op_prune_fill(float* p, int64_t n, float v, void* stream) {
+  P5_REQUIRE(p && n >= 1, "prune_fill: null argument");
+  return prune_fill(p, (size_t)n, v, (hipStream_t)stream);
+}
+int p5_op_prune_propose(int* sel, int* n_rows, int* hdr, const float* edge_lp, int64_t n_edges, const float* top_score, int N, const int* row_depth, const int* anc,
+                        int rows, int max_depth, const int* row_edge, const int* row_lmax, float slack, int B, void* stream) {
+  P5_REQUIRE(sel && n_rows && hdr && edge_lp && top_score && row_depth && anc && row_edge && row_lmax && N >= 1 && rows >= 1 && B >= 1, "prune_propose: null argument");
+  const P5RankPlan pl = op_rank_plan(nullptr, row_depth, nullptr, anc, rows, max_depth, B, 0, 0);
+  return prune_propose_rows(sel, n_rows, hdr, edge_lp, n_edges, top_score, N, pl, row_edge, row_lmax, slack, B, (hipStream_t)stream);
+}
+int p5_op_prune_mask(uint32_t* out, const uint32_t* excluded, const float* edge_lp, int64_t n_edges, const int* item_edges, int n_items, int path_len, int B,
+                     void* stream) {
+  P5_REQUIRE(out && edge_lp && item_edges && n_items >= 1 && path_len >= 1 && B >= 1, "prune_mask: null argument");
+  return prune_mask(out, excluded, edge_lp, n_edges, item_edges, n_items, path_len, B, (hipStream_t)stream);
+}
+static P5CandPlan op_sel_plan(const int* row_depth, const int* row_node, const int* anc, int max_depth, int B, int CQ, int nchunk, const int* sel, const int* n_rows,
+                              int cap) {
+  P5CandPlan pl;
+  pl.g = op_rank_plan(nullptr, row_depth, row_node, anc, CQ * nchunk, max_depth, B, CQ, nchunk);
+  pl.sel = sel; pl.n_rows = n_rows; pl.cap = cap;
+  return pl;
+}
+int p5_op_prune_certify(int* flagged, const float* edge_lp, int64_t n_edges, const int* row_depth, const int* row_node, const int* anc, int max_depth, int B, int CQ,
+                        int nchunk, const int* sel, const int* n_rows, int cap, const int* row_edge, const int* edge_row, const int* row_lmax,
+                        const int* child_off, const int* out_index, const float* out_score, int N, float margin, void* stream) {
+  P5_REQUIRE(flagged && edge_lp && row_depth && row_node && anc && sel && n_rows && row_edge && edge_row && row_lmax && child_off && out_index && out_score,
+             "prune_certify: null argument");
+  P5_REQUIRE(B >= 1 && CQ >= 1 && nchunk >= 1 && N >= 1, "prune_certify: shape");
+  return prune_certify(flagged, edge_lp, n_edges, op_sel_plan(row_depth, row_node, anc, max_depth, B, CQ, nchunk, sel, n_rows, cap), row_edge, edge_row, row_lmax,
+                       child_off, out_index, out_score, N, margin, (hipStream_t)stream);
+}
+int p5_op_bound_seed(int* sel, int* n_rows, int* hdr, unsigned long long* keys, int KP, int cap, const int64_t* seeds, int S, int T, const int* child_off,
+                     const int* child_tok, const int* edge_row, const int* row_tok, const int* row_node, int max_depth, int B, void* stream) {
+  P5_REQUIRE(sel && n_rows && hdr && keys && seeds && child_off && child_tok && edge_row && row_tok && row_node, "bound_seed: null argument");
+  P5_REQUIRE(S >= 1 && S <= P5_WIDE_MAX_K && T >= 1 && max_depth >= 1 && B >= 1 && cap >= 1, "bound_seed: 1 <= n_seeds <= 4096, seed_len >= 1");
+  P5_REQUIRE(KP >= 256 && (KP & (KP - 1)) == 0 && (long long)KP >= (long long)S * max_depth + 1, "bound_seed: KP a power of two >= max(n_seeds * max_depth + 1, 256)");
+  return bound_seed_rows(sel, n_rows, hdr, keys, KP, cap, seeds, S, T, child_off, child_tok, edge_row, row_tok, row_node, max_depth, B, (hipStream_t)stream);
+}
+int p5_op_bound_expand(int* sel, int* n_rows, int* grew, int* hdr, unsigned long long* keys, int KP, const float* edge_lp, int64_t n_edges, const int* row_depth,
+                       const int* row_node, const int* anc, int max_depth, int B, int CQ, int nchunk, int cap, const int* row_edge, const int* edge_row,
+                       const int* row_lmax, const int* child_off, const float* out_score, int N, float margin, void* stream) {
+  P5_REQUIRE(sel && n_rows && grew && hdr && keys && edge_lp && row_depth && row_node && anc && row_edge && edge_row && row_lmax && child_off && out_score,
+             "bound_expand: null argument");
+  P5_REQUIRE(B >= 1 && CQ >= 1 && nchunk >= 1 && N >= 1 && KP >= 256 && (KP & (KP - 1)) == 0, "bound_expand: KP a power of two >= 256");
+  return bound_expand_rows(sel, n_rows, grew, hdr, keys, KP, edge_lp, n_edges, op_sel_plan(row_depth, row_node, anc, max_depth, B, CQ, nchunk, sel, n_rows, cap),
+                           row_edge, edge_row, row_lmax, child_off, out_score, N, margin, (hipStream_t)stream);
 }
 int p5_op_tr_probe(void* out, const void* in, void* stream) {
   P5_LAUNCH(p5_tr_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned short*)out, (const unsigned short*)in);

@@ -84,8 +84,8 @@ KERNELS = {
     "p5_verify_forced_kernel": dict(checked_by=_VERIFY),
     "p5_verify_range_kernel": dict(checked_by=_VERIFY),
     "p5_verify_step_kernel": dict(checked_by=_VERIFY),
-    # its per-row body (p5_tree_attn_row) is shared with exhaustive ranking, compared item by item with the oracle
-    "p5_tree_attn_kernel": dict(checked_by="tests/rank_cases.py (tests/test_rank_items_emu.py, tests/test_gpu_rank_items.py) through p5_tree_attn_row; " + _VERIFY),
+    # its per-row body (p5_tree_attn_row) is shared with exhaustive ranking: the rows of both against float64 are in the ranking table
+    "p5_tree_attn_kernel": dict(checked_by="tests/rank_matrix.py, family tree_attn, variant 2 (tests/test_rank_ref_emu.py, tests/test_gpu_rank_ref.py); " + _VERIFY),
 }
 
 

@@ -141,3 +141,28 @@ def test_every_decode_kernel_launch_is_named_in_the_decode_table():
     for k, v in KERNELS.items():
         assert ("fam" in v) != ("checked_by" in v), k
         assert "fam" not in v or v["fam"] in fams, f"{k}: no row of family {v.get('fam')}"
+
+
+def test_every_rank_kernel_launch_is_named_in_the_rank_table():
+    """tests/rank_matrix.py names every kernel of p5_rank.h / p5_cand.h / p5_prune.h / p5_bound.h / p5_sample.h that p5_lib.hip launches: with rows
+    checked against an exact restatement or float64 (rank_kernel_cases.*_case) or with the existing test that reaches it (`checked_by`), so a
+    new ranking kernel cannot arrive without either."""
+    from tests.rank_matrix import KERNELS, ROWS
+    defined = set()
+    for fn in ("p5_rank.h", "p5_cand.h", "p5_prune.h", "p5_bound.h", "p5_sample.h"):
+        defined |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(p5_\w+)\s*\(", open(os.path.join(CSRC, fn)).read()))
+    assert len(defined) >= 27, sorted(defined)
+    launched = set()
+    for site in _launch_sites("p5_lib.hip"):
+        name = re.match(r"\(*(\w+)", site).group(1)
+        if name in defined:
+            launched.add(name)
+    assert len(launched) >= 27, sorted(launched)
+    missing = sorted(launched - set(KERNELS))
+    assert not missing, f"kernels launched by p5_lib.hip without an entry in tests/rank_matrix.py: {missing}"
+    stale = sorted(set(KERNELS) - launched)
+    assert not stale, f"tests/rank_matrix.py names kernels that the five headers no longer define or p5_lib.hip no longer launches: {stale}"
+    fams = {r["fam"] for r in ROWS}
+    for k, v in KERNELS.items():
+        assert ("fam" in v) != ("checked_by" in v), k
+        assert "fam" not in v or v["fam"] in fams, f"{k}: no row of family {v.get('fam')}"
