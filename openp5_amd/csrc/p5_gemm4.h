@@ -31,6 +31,46 @@ struct P5GemmGroup {
   P5GemmArgs p[P5_MAX_GROUP];         // .g4_tiles_n / .g4_nk / .splitk filled by the launcher
 };
 
+// FILLER problems of a grouped K-strided launch (p5_gemm5_kernel<true> only): small weight gradients that ride in the workgroups a
+// launch's primary units leave short.  The primary units (P5GemmGroup above) are dealt exactly as without fillers.  Inside XCD x the
+// SHORT workgroups -- those whose primary share is one unit smaller than the largest share of the XCD, all of them when the shares are
+// equal -- take the XCD's filler units round-robin, after their primaries; the ring runs on across the boundary as between any two
+// units.  Every filler unit is a whole 256x128 tile over its whole K range, written by one workgroup: nobody waits for anybody.
+//   * XCD x owns units [x * ceil(n / 8), (x + 1) * ceil(n / 8)) of EVERY entry (n = its units), entry after entry: the tiles of one
+//     problem that an XCD works on are neighbours, and every XCD gets the same mix of long and short units;
+//   * entries [0, nheavy) are dealt over the first `heavy_wgs` short workgroups of the XCD, the others over the rest (one class when
+//     heavy_wgs <= 0 or the XCD has no more short workgroups than that): a K = 8192 tile fills a short workgroup by itself, and plain
+//     round-robin would put the K = 512 tiles behind it on the same workgroup.
+// A compact descriptor instead of P5GemmArgs (280 bytes): `batch` problems of one shape at constant strides are one entry (the decoder
+// layers), so that two encoder layers + the cross-attention K/V block + every decoder layer + the tied head stay below 4 KB of
+// kernel arguments.  bf16 operands, both K-strided; fp32 C, stored or accumulated.
+#define P5_MAX_FILL 12
+struct P5FillProb {
+  const void* A; const void* B; float* C;
+  long long sA, sB, sC;               // element strides from one problem of the batch to the next
+  int M, N, nk;                       // output rows / columns, K-steps of 64 (the whole reduction)
+  int tiles_n, tiles, units;          // launcher-internal: tiles along N, tiles of one problem, batch * tiles
+  int batch;
+  int lda, ldb, ldc;
+  int epi;                            // P5_EPI_STORE or P5_EPI_ACCUM
+  float alpha;
+  int acap;                           // columns of an A row that may be read from A on (lda, less the row offset of a slice by output rows)
+};
+struct P5GemmGroupFill : P5GemmGroup {
+  int nfill, nheavy, heavy_wgs, pad_;
+  P5FillProb f[P5_MAX_FILL];
+  P5GemmGroupFill() = default;
+  P5GemmGroupFill(const P5GemmGroup& g) : P5GemmGroup(g), nfill(0), nheavy(0), heavy_wgs(0), pad_(0) {}      // a group without fillers
+};
+static_assert(sizeof(P5GemmGroupFill) <= 4000, "kernel arguments of the grouped weight-gradient launch");
+// units of entry q that XCD x owns, and the first of them
+static __host__ __device__ inline int p5_fill_share(int units, int xcd, int* first) {
+  const int per = (units + 7) >> 3;
+  const int left = units - xcd * per;
+  *first = xcd * per;
+  return left <= 0 ? 0 : (left < per ? left : per);
+}
+
 // slot swizzles of the K-contiguous LDS images ([rows][128 B], 16-byte slot index XOR sigma(row)): A rows are read 16 consecutive
 // rows at a time, B rows in the permuted order described above -- each makes the 16 lanes of a ds_read_b128 service group hit 16
 // different bank groups
@@ -45,6 +85,20 @@ __device__ static __forceinline__ int g4_sigma_b(int row) { return (row & 3) | (
 // ablation switches (tools/lab): 1 = no MFMA, 2 = no copies after the prologue, 4 = no fragment reads, 8 = no epilogue
 // OCC = workgroups per CU the register allocation must leave room for; FLAGS bit 0: every unit starts its K loop at a different
 // K-step (workgroups that share an operand panel then pull different lines of it at any moment)
+// acc * alpha of the fp32 accumulate / atomic epilogues of the kernels in this file and in p5_gemm5.h (every route a grouped weight
+// gradient can take), rounded BEFORE it is added to C; the generic kernels of p5_gemm.h scale by alpha * rstd and are not changed,
+// no weight gradient of the grouped path reaches them.  Left to the compiler, "c + acc * alpha" becomes
+// an FMA in one kernel instance and a multiply and an add in another, and an accumulating micro-batch then differs in the last bit with
+// the tile shape its problem happened to get (the tied head, the only weight gradient with alpha != 1)
+#ifdef P5_EMU
+static inline float p5_mul_rn(float a, float b) { return a * b; }
+#else
+__device__ static __forceinline__ float p5_mul_rn(float a, float b) {
+  float p = a * b;
+  asm("" : "+v"(p));      // (opaque to the optimizer: the product exists, rounded, before anything is added to it)
+  return p;
+}
+#endif
 #ifdef P5_EMU
 static inline uint64_t sgpr64(uint64_t v) { return v; }
 #else
@@ -277,7 +331,7 @@ __global__ __launch_bounds__(WMW* WNW * 64) P5_WAVES_PER_SIMD(WMW* WNW / 4 * OCC
         if (row >= g.M || col >= g.N) continue;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = a[j][r] * g.alpha;
+        for (int r = 0; r < 4; ++r) v[r] = p5_mul_rn(a[j][r], g.alpha);
         const size_t ci = (size_t)row * g.ldc + col;
         if (g.c_f32 && col + 4 <= g.N && (g.ldc & 3) == 0) {
           float* cp = (float*)g.C + ci;

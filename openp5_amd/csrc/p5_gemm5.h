@@ -25,8 +25,10 @@
 // 128 x 128 but only 128 of 256 x 128 -- half the chip): 2 x 2 compute waves on 64 x 64 wave tiles, four-slot ring of 32 KiB K-steps, the
 // same loader / compute split, so the copies' issue cost stays out of the MFMA stream (p5_gemm2_kernel<128,128,4>, whose four waves do both,
 // moves 8 TB/s into LDS on these shapes).
+template <bool KS> struct P5Gemm5Group { using type = P5GemmGroup; };
+template <> struct P5Gemm5Group<true> { using type = P5GemmGroupFill; };      // the K-strided instance carries filler problems (p5_gemm4.h)
 template <bool KS, int ABL = 0, int VAR = 0, int BMT = 256>
-__global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
+__global__ __launch_bounds__(512) void p5_gemm5_kernel(typename P5Gemm5Group<KS>::type grp) {
   constexpr bool GATE = VAR == 1;
   using T = bf16;
   static_assert(BMT == 256 || BMT == 128, "tile rows");
@@ -53,12 +55,55 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
   const int xcd = (int)blockIdx.x & 7, jx = (int)blockIdx.x >> 3, gx = nwg >> 3;
   const int upx = (grp.total_units + 7) >> 3;
   const int ulast = upx < grp.total_units - xcd * upx ? upx : grp.total_units - xcd * upx;
-  const int nmy = ulast > jx ? (ulast - jx + gx - 1) / gx : 0;
+  const int nmy_p = ulast > jx ? (ulast - jx + gx - 1) / gx : 0;
+  // filler units (K-strided instance; P5GemmGroupFill in p5_gemm4.h): this workgroup's place among the XCD's short workgroups, the entries
+  // of its class, and how many of their units in this XCD fall to it
+  int f_q0 = 0, f_q1 = 0, f_si = 0, f_ns = 1, nmy_f = 0;
+  if constexpr (KS) {
+    if (grp.nfill > 0) {
+      const int rr = ulast > 0 ? ulast % gx : 0;
+      int si = rr == 0 ? jx : jx - rr, ns = rr == 0 ? gx : gx - rr;
+      if (si >= 0) {
+        f_q1 = grp.nfill;
+        const int hw = grp.heavy_wgs;
+        if (hw > 0 && hw < ns) {
+          if (si < hw) { ns = hw; f_q1 = grp.nheavy; }
+          else { si -= hw; ns -= hw; f_q0 = grp.nheavy; }
+        }
+        int fx = 0, first;
+        for (int q = f_q0; q < f_q1; ++q) fx += p5_fill_share(grp.f[q].units, xcd, &first);
+        nmy_f = fx > si ? (fx - si + ns - 1) / ns : 0;
+        f_si = si; f_ns = ns;
+      }
+    }
+  }
+  const int nmy = nmy_p + nmy_f;
   if (nmy <= 0) return;
 
-  struct Unit { int pi, m0, n0, kb, nk; };
+  struct Unit { int pi, m0, n0, kb, nk, bi; };
   auto decode = [&](int it) {
     Unit u;
+    u.bi = 0;
+    if constexpr (KS) {
+      if (it >= nmy_p) {       // a filler: unit fl of the class's units in this XCD, entry after entry
+        int fl = (it - nmy_p) * f_ns + f_si, q = f_q0, first = 0;
+        for (; q < f_q1 - 1; ++q) {
+          const int sh = p5_fill_share(grp.f[q].units, xcd, &first);
+          if (fl < sh) break;
+          fl -= sh;
+        }
+        p5_fill_share(grp.f[q].units, xcd, &first);
+        const P5FillProb& f = grp.f[q];
+        const int id = first + fl, tile = id % f.tiles;
+        u.pi = P5_MAX_GROUP + q;
+        u.bi = id / f.tiles;
+        u.m0 = (tile / f.tiles_n) * BM;
+        u.n0 = (tile % f.tiles_n) * BN;
+        u.nk = f.nk;
+        u.kb = 0;
+        return u;
+      }
+    }
     const int id = xcd * upx + it * gx + jx;
     int pi = 0;
 #pragma unroll
@@ -87,6 +132,24 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
     return u;
   };
 
+  // K-strided instance: what a unit needs from its problem, primary (P5GemmArgs) or filler (P5FillProb, batch member u.bi)
+  struct KSProb { const T* A; const T* B; void* C; int M, N, lda, ldb, ldc, epi, c_f32, acap; float alpha; };
+  auto ksprob = [&](const Unit& u) {
+    KSProb p;
+    if constexpr (KS) {
+      if (u.pi >= P5_MAX_GROUP) {
+        const P5FillProb& f = grp.f[u.pi - P5_MAX_GROUP];
+        p.A = (const T*)f.A + (long long)u.bi * f.sA; p.B = (const T*)f.B + (long long)u.bi * f.sB; p.C = f.C + (long long)u.bi * f.sC;
+        p.M = f.M; p.N = f.N; p.lda = f.lda; p.ldb = f.ldb; p.ldc = f.ldc; p.epi = f.epi; p.c_f32 = 1; p.alpha = f.alpha; p.acap = f.acap;
+        return p;
+      }
+    }
+    const P5GemmArgs& g = grp.p[u.pi];
+    p.A = (const T*)g.A; p.B = (const T*)g.B; p.C = g.C; p.M = g.M; p.N = g.N; p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.epi = g.epi;
+    p.c_f32 = g.c_f32; p.alpha = g.alpha; p.acap = g.lda;
+    return p;
+  };
+
   if (wave >= NWC) {
     // =========================================== loader waves ===========================================
     const int lw = wave - NWC;
@@ -96,18 +159,18 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
     int c_it = 0, c_left = 0;
     auto copy_setup = [&](int it) {
       const Unit u = decode(it);
-      const P5GemmArgs& g = grp.p[u.pi];
       c_left = u.nk;
       if constexpr (KS) {
+        const KSProb g = ksprob(u);
         incA = (size_t)64 * g.lda; incB = (size_t)64 * g.ldb;
 #pragma unroll
         for (int i = 0; i < NDA; ++i) {
           constexpr int CPR = BM / 8, RPI = 512 / BM;
           const int krow = (lw * NDA + i) * RPI + lane / CPR;
           int cg = (lane % CPR) ^ ksd_swz<BM>(krow);
-          const int cmax = (g.lda - u.m0) / 8 - 1;        // (row capacity of the k-row in memory, see stage_dma_ks)
+          const int cmax = (g.acap - u.m0) / 8 - 1;       // (row capacity of the k-row in memory, see stage_dma_ks)
           cg = cg < cmax ? cg : (cmax > 0 ? cmax : 0);
-          srcA[i] = (const T*)g.A + ((size_t)u.kb + krow) * g.lda + u.m0 + cg * 8;
+          srcA[i] = g.A + ((size_t)u.kb + krow) * g.lda + u.m0 + cg * 8;
         }
 #pragma unroll
         for (int i = 0; i < NDB; ++i) {
@@ -116,9 +179,10 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
           int cg = (lane % CPR) ^ ksd_swz<BN>(krow);
           const int cmax = (g.ldb - u.n0) / 8 - 1;
           cg = cg < cmax ? cg : (cmax > 0 ? cmax : 0);
-          srcB[i] = (const T*)g.B + ((size_t)u.kb + krow) * g.ldb + u.n0 + cg * 8;
+          srcB[i] = g.B + ((size_t)u.kb + krow) * g.ldb + u.n0 + cg * 8;
         }
       } else {
+        const P5GemmArgs& g = grp.p[u.pi];
         incA = 64; incB = 64;
 #pragma unroll
         for (int i = 0; i < NDA; ++i) {
@@ -251,7 +315,7 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
   };
 
   // one 16-row block of the 128x64 wave tile, constant row-block index (p5_gemm4.h epi_rows)
-  auto epi_rows = [&](const f32x4(&a)[TN], int i, const Unit& u, const P5GemmArgs& g, uint32_t seed, bool do_drop, bool vec_ok, int le) {
+  auto epi_rows = [&](const f32x4(&a)[TN], int i, const Unit& u, const auto& g, uint32_t seed, bool do_drop, bool vec_ok, int le) {      // (g: P5GemmArgs, or KSProb in the K-strided instance)
     const int gl = le >> 4;
     const int row = u.m0 + wm * WTM + i * 16 + (le & 15);
     if constexpr (KS) {
@@ -261,7 +325,7 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
         if (row >= g.M || col >= g.N) continue;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = a[j][r] * g.alpha;
+        for (int r = 0; r < 4; ++r) v[r] = p5_mul_rn(a[j][r], g.alpha);
         const size_t ci = (size_t)row * g.ldc + col;
         if (g.c_f32 && col + 4 <= g.N && (g.ldc & 3) == 0) {
           float* cp = (float*)g.C + ci;
@@ -369,8 +433,15 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
     bool fast, fast32, do_drop;
   };
   auto load_ctx = [&](const Unit& u) {
-    const P5GemmArgs& g = grp.p[u.pi];
     EpiCtx c;
+    if constexpr (KS) {
+      const KSProb g = ksprob(u);
+      c.C = g.C; c.epi = g.epi; c.ldc = g.ldc; c.alpha = g.alpha;
+      c.fast = u.m0 + BM <= g.M && u.n0 + BN <= g.N && g.c_f32 && (g.ldc & 3) == 0 && ((uintptr_t)g.C & 15) == 0 && (g.epi == P5_EPI_ACCUM || g.epi == P5_EPI_STORE);
+      c.fast32 = false;
+      return c;
+    }
+    const P5GemmArgs& g = grp.p[u.pi];
     c.C = g.C; c.aux = g.aux; c.ssq = g.ssq_out; c.rowss = g.rowss; c.C2 = g.C2;
     c.epi = g.epi; c.N = g.N; c.ldc = g.ldc; c.ldaux = g.ldaux; c.ssq_nt = g.ssq_nt; c.rowss_nt = g.rowss_nt; c.ldc2 = g.ldc2; c.gate_F = g.gate_F;
     c.thr = g.drop.thr; c.dscale = g.drop.scale; c.alpha = g.alpha; c.invd = g.rowss_invd; c.eps = g.rowss_eps;
@@ -870,7 +941,8 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
             for (int j = 0; j < TN; ++j) c[j] = *(const f32x4*)(cp + j * 16);
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-              *(f32x4*)(cp + j * 16) = (f32x4){c[j][0] + a[j][0] * alpha, c[j][1] + a[j][1] * alpha, c[j][2] + a[j][2] * alpha, c[j][3] + a[j][3] * alpha};
+              *(f32x4*)(cp + j * 16) = (f32x4){c[j][0] + p5_mul_rn(a[j][0], alpha), c[j][1] + p5_mul_rn(a[j][1], alpha), c[j][2] + p5_mul_rn(a[j][2], alpha),
+                                               c[j][3] + p5_mul_rn(a[j][3], alpha)};
           } else {
 #pragma unroll
             for (int j = 0; j < TN; ++j) *(f32x4*)(cp + j * 16) = (f32x4){a[j][0] * alpha, a[j][1] * alpha, a[j][2] * alpha, a[j][3] * alpha};
@@ -883,13 +955,20 @@ __global__ __launch_bounds__(512) void p5_gemm5_kernel(P5GemmGroup grp) {
       }
       return;
     }
-    const P5GemmArgs& g = grp.p[u.pi];
-    const uint32_t seed = p5_seed(g.drop);
-    const bool do_drop = g.drop.state != nullptr && g.drop.thr != 0;
-    const bool vec_ok = (g.ldc & 7) == 0 && ((uintptr_t)g.C & 15) == 0 && (g.aux == nullptr || ((g.ldaux & 7) == 0 && ((uintptr_t)g.aux & 15) == 0));
-#define P5_G5_ER(i) epi_rows(acc[i], i, u, g, seed, do_drop, vec_ok, le)
-    P5_G5_ROWBLOCKS(P5_G5_ER);
+    if constexpr (KS) {
+      const KSProb g = ksprob(u);
+#define P5_G5_ER(i) epi_rows(acc[i], i, u, g, 0u, false, false, le)
+      P5_G5_ROWBLOCKS(P5_G5_ER);
 #undef P5_G5_ER
+    } else {
+      const P5GemmArgs& g = grp.p[u.pi];
+      const uint32_t seed = p5_seed(g.drop);
+      const bool do_drop = g.drop.state != nullptr && g.drop.thr != 0;
+      const bool vec_ok = (g.ldc & 7) == 0 && ((uintptr_t)g.C & 15) == 0 && (g.aux == nullptr || ((g.ldaux & 7) == 0 && ((uintptr_t)g.aux & 15) == 0));
+#define P5_G5_ER(i) epi_rows(acc[i], i, u, g, seed, do_drop, vec_ok, le)
+      P5_G5_ROWBLOCKS(P5_G5_ER);
+#undef P5_G5_ER
+    }
   };
 
   // Both operands' fragments double-buffered (96 registers): the 12 reads of the next K-chunk go out under the first 24 of a

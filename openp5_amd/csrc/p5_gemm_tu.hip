@@ -133,7 +133,7 @@ static int launch_gemm4_cfg(P5GemmGroup& grp, hipStream_t s) {
   return P5_KCHECK();
 }
 template <bool KS, int BM = 256>
-static int launch_gemm5(P5GemmGroup& grp, hipStream_t s) {     // same unit bookkeeping as launch_gemm4_cfg<BM, 128, ...>, 4 loader + 4 compute waves
+static int launch_gemm5(typename P5Gemm5Group<KS>::type& grp, hipStream_t s) {     // same unit bookkeeping as launch_gemm4_cfg<BM, 128, ...>, 4 loader + 4 compute waves
   int units = 0;
   for (int i = 0; i < grp.nprob; ++i) {
     P5GemmArgs& g = grp.p[i];
@@ -149,7 +149,26 @@ static int launch_gemm5(P5GemmGroup& grp, hipStream_t s) {     // same unit book
   }
   grp.unit_begin[grp.nprob] = units;
   grp.total_units = units;
-  int nwg = ((units + 7) / 8) * 8;
+  // filler problems (P5GemmGroupFill): they change neither the primaries' units nor who runs them -- only, possibly, the workgroup count,
+  // which is taken over primary and filler demand together
+  int fill_units = 0;
+  double fill_flops = 0.0;
+  if constexpr (KS) {
+    P5_REQUIRE(grp.nfill >= 0 && grp.nfill <= P5_MAX_FILL && grp.nheavy >= 0 && grp.nheavy <= grp.nfill, "gemm5: filler entries");
+    for (int q = 0; q < grp.nfill; ++q) {
+      P5FillProb& f = grp.f[q];
+      P5_REQUIRE(f.M > 0 && f.N > 0 && f.nk >= 1 && f.batch >= 1, "gemm5: empty filler problem");
+      P5_REQUIRE(f.lda % 8 == 0 && f.ldb % 8 == 0 && ((uintptr_t)f.A % 16) == 0 && ((uintptr_t)f.B % 16) == 0 && f.sA % 8 == 0 && f.sB % 8 == 0, "gemm5: filler operand alignment");
+      P5_REQUIRE(f.acap >= ((f.M + 7) / 8) * 8 && f.acap <= f.lda && f.ldb >= ((f.N + 7) / 8) * 8, "gemm5: filler operand extents");
+      P5_REQUIRE(f.C && (f.epi == P5_EPI_STORE || f.epi == P5_EPI_ACCUM), "gemm5: fillers store or accumulate into fp32");
+      f.tiles_n = (f.N + 127) / 128;
+      f.tiles = ((f.M + BM - 1) / BM) * f.tiles_n;
+      f.units = f.tiles * f.batch;
+      fill_units += f.units;
+      fill_flops += 2.0 * f.M * f.N * (64.0 * f.nk) * f.batch;
+    }
+  }
+  int nwg = ((units + fill_units + 7) / 8) * 8;
   if (nwg > g_opt_g4_wgs) nwg = g_opt_g4_wgs;
   for (int i = 0; i < grp.nprob; ++i) grp.p[i].g4_cb = 0;
   // (option 1: only where the B operand does not fit an XCD's 4 MiB L2 beside the A panels -- measured in one call: T5-large 115.2 -> 112.8 ms
@@ -165,10 +184,10 @@ static int launch_gemm5(P5GemmGroup& grp, hipStream_t s) {     // same unit book
     }
   }
   {
-    double fl = 0.0;
+    double fl = fill_flops;
     for (int i = 0; i < grp.nprob; ++i) fl += 2.0 * grp.p[i].M * grp.p[i].N * grp.p[i].K;
     P5_PROF_FLOPS(fl);
-    P5_PROF_TAG(KS ? "KS: grouped weight gradients" : (BM == 128 ? "KC 128x128: N = d_model outputs" : "KC: forward / data-gradient GEMMs"));
+    P5_PROF_TAG(KS ? (fill_units > 0 ? "KS: grouped weight gradients + fillers" : "KS: grouped weight gradients") : (BM == 128 ? "KC 128x128: N = d_model outputs" : "KC: forward / data-gradient GEMMs"));
     if (grp.nprob == 1) P5_PROF_SHAPE(grp.p[0].M, grp.p[0].N, grp.p[0].K);
   }
   if constexpr (BM == 128) {
@@ -227,7 +246,13 @@ int launch_gemm4(int cfg, bool ks, P5GemmGroup& grp, hipStream_t s) {
     P5_REQUIRE(!ks, "gemm5: the 128-row tile is K-contiguous only");
     return launch_gemm5<false, 128>(grp, s);
   }
-  if (cfg == P5_G5_256x128 || (cfg == P5_G4_256x128 && (g_opt_gemm_ws & (ks ? 2 : 1)))) return ks ? launch_gemm5<true>(grp, s) : launch_gemm5<false>(grp, s);
+  if (cfg == P5_G5_256x128 || (cfg == P5_G4_256x128 && (g_opt_gemm_ws & (ks ? 2 : 1)))) {
+    if (!ks) return launch_gemm5<false>(grp, s);
+    P5GemmGroupFill gf(grp);      // (no fillers: decodes exactly as before)
+    const int rc = launch_gemm5<true>(gf, s);
+    static_cast<P5GemmGroup&>(grp) = gf;
+    return rc;
+  }
   if (ks) {
     if (cfg == P5_G4_256x128) return launch_gemm4_cfg<256, 128, 4, 2, 3, true>(grp, s);
     P5_REQUIRE(cfg == P5_G4_128x128, "gemm4: K-strided operands run on 128x128 or 256x128 tiles");
@@ -242,6 +267,14 @@ int launch_gemm4(int cfg, bool ks, P5GemmGroup& grp, hipStream_t s) {
   if (g_opt_g4_nst == 3) return launch_gemm4_cfg<128, 128, 2, 2, 3, false>(grp, s);
   if (g_opt_g4_nst == 4) return launch_gemm4_cfg<128, 128, 2, 2, 4, false>(grp, s);
   return launch_gemm4_cfg<128, 128, 2, 2, 5, false>(grp, s);
+}
+
+// a grouped weight-gradient launch WITH filler problems: the wave-specialised K-strided instance is the only one that decodes them
+bool p5l_gemm_fill_ok() { return (g_opt_gemm_ws & 2) != 0; }
+int launch_gemm_fill(P5GemmGroupFill& grp, hipStream_t s) {
+  P5_REQUIRE(grp.nprob >= 1 && grp.nprob <= P5_MAX_GROUP, "gemm5: 1..8 primary problems per launch");
+  P5_REQUIRE(p5l_gemm_fill_ok(), "gemm5: filler problems need the wave-specialised K-strided kernel (gemm_ws bit 1)");
+  return launch_gemm5<true>(grp, s);
 }
 
 // the fused gated-GELU epilogues exist in the whole-tile path of p5_gemm5.h only: bf16, both operands K-contiguous, every 256x128 tile

@@ -70,6 +70,8 @@ bool p5l_gemm_gate_ok(int M, int N, int K, int lda, int ldb);
 bool p5l_gemm_ce_ok(int M, int N, int K, int lda, int ldb);
 bool p5l_gemm_normbwd_ok(int M, int N, int K, int lda, int ldb);
 int launch_gemm4(int cfg, bool ks, P5GemmGroup& grp, hipStream_t s);
+bool p5l_gemm_fill_ok();
+int launch_gemm_fill(P5GemmGroupFill& grp, hipStream_t s);      // p5_gemm5_kernel<true> with filler problems (p5_gemm4.h)
 int p5l_attn_fwd(int bf16_mode, const P5AttnArgs& a, hipStream_t s);
 int p5l_attn_bwd(int bf16_mode, const P5AttnArgs& a, hipStream_t s);
 int p5l_attn_bwd_slots(int bf16_mode, int B, int Lq, int Lk);

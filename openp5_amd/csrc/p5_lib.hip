@@ -154,6 +154,14 @@ struct P5Engine {
   P5ReduceMulti nr_pending;               // norm-weight partial sums of the current backward stage, reduced by one launch at its end
   std::vector<P5GemmArgs> wg_pending;     // deferred weight-gradient problems (bf16, token count a multiple of 64)
   unsigned wg_sets = 0;                   // bit p: a pending problem reads temporaries of set p
+  // weight-gradient plan of the whole backward (wgrad_plan_flush): the tied head's, the decoder layers' and the cross-attention K/V
+  // block's problems wait in a pool and ride as FILLER units in the short workgroups of the encoder's two-layer launches (p5_gemm4.h)
+  struct WgPoolItem { P5GemmArgs g; int kind, layer, rows_left, rows_all; };   // kind 0 head, 1 decoder layer, 2 K/V block; 256-row tile rows not yet taken
+  std::vector<WgPoolItem> wg_pool;
+  bool wg_plan = false;                   // this backward runs under the plan (decided in stage 0)
+  int wg_pool_kind = -1, wg_pool_layer = 0;   // where linear_wgrad queues: -1 = wg_pending
+  // ... whose decoder sub-layers therefore keep their temporaries (dy, dqkv, dh, du) in slots of their own, Md rows each, in backward order
+  std::vector<void*> ds_dy, ds_dh, ds_du, ds_dqkv;
   bool whole_backward = false;            // inside p5_backward (as opposed to stage-by-stage calls of a data-parallel caller)
   bool stage_pairs = true;                // staged backward: the encoder's weight gradients still leave in two-layer groups (the benchmarked launch)
   int64_t fin_b = 0, fin_e = 0;           // staged backward: gradient range completed by the stages run since the last p5_backward_final_range
@@ -224,6 +232,18 @@ static void begin_sublayer(P5Engine* e) {
   const int p = e->sub % P5_NSETS, pn = (e->sub + 1) % P5_NSETS;
   e->dy = e->dy2[p]; e->dy_next = e->dy2[pn];
   e->dh = e->dh2[p]; e->du = e->du2[p]; e->dqkv = e->dqkv2[p]; e->dkv = e->dkv2[p];
+  if (e->wg_plan) {
+    // decoder sub-layers (1 .. 3 n_dec of the backward) under the weight-gradient plan: what their weight gradients read must survive
+    // until an encoder launch carries them -- slots of their own instead of the rotating sets
+    const int n = (int)e->ds_dy.size(), k = e->sub - 1;
+    if (k >= 0 && k < n) {
+      e->dy = e->ds_dy[k];
+      if (e->ds_dh[k]) e->dh = e->ds_dh[k];
+      if (e->ds_du[k]) e->du = e->ds_du[k];
+      if (e->ds_dqkv[k]) e->dqkv = e->ds_dqkv[k];
+    }
+    if (k + 1 >= 0 && k + 1 < n) e->dy_next = e->ds_dy[k + 1];
+  }
 }
 // side stream waits for everything enqueued on `main` so far
 static void fork_to_side(P5Engine* e, hipStream_t main) {
@@ -459,6 +479,18 @@ static int g_opt_wgrad_wide = getenv("P5_WGRAD_WIDE") ? atoi(getenv("P5_WGRAD_WI
 static int g_opt_wgrad_wide_min = getenv("P5_WGRAD_WIDE_MIN") ? atoi(getenv("P5_WGRAD_WIDE_MIN")) : 160;
 static int g_opt_wgrad_wgs = getenv("P5_WGRAD_WGS") ? atoi(getenv("P5_WGRAD_WGS")) : 0;          // workgroups of a grouped weight-gradient launch (0 = one per unit, <= 256)
 static int g_opt_wgrad_layers = getenv("P5_WGRAD_LAYERS") ? atoi(getenv("P5_WGRAD_LAYERS")) : 2;  // encoder layers per grouped launch (p5_backward only; staged backward: 1)
+// 1 = the weight-gradient plan of the whole backward (wgrad_plan_flush below); 0 = the grouping and the launches of round 6
+static int g_opt_wgrad_fill = getenv("P5_WGRAD_FILL") ? atoi(getenv("P5_WGRAD_FILL")) : 1;
+// Cost model of the plan, in K-steps (one K-step of a 256x128 tile = 48 KiB copied, 64 MFMAs per compute wave): a unit costs its K-steps
+// plus this constant for what does not shrink with K -- the cold first K-steps of a new problem and the 128 KB fp32 tile its epilogue
+// stores (or reads, adds and stores).  Derivation: an encoder group runs 128 K-steps per unit in 122 us, 0.95 us per K-step; the tied
+// head's own launch (504 units of 8 K-steps, two rounds on 256 workgroups, 41 us) spends ~20 us per unit, of which the K-steps explain
+// 7.6 us -- the remaining ~12 us are 13 K-steps.  (The decoder layers' launches, 15.5 us for one round of 128x128 tiles of 8 K-steps, say
+// the same: 7.6 us of K-steps, ~8 us of everything else.)
+// Measured in the step (T5-small, B=64, L=128, T=8; profiles/r07_call1_wgrad_fill_epi_sweep.txt), constant -> ms per step / weight-gradient launches:
+// 4 -> 3.95 / 4, 8 -> 3.92 / 4, 13 -> 3.95 / 5, 24 -> 3.96 / 6 (no plan: 4.11 / 11).  8: lower values overfill the short workgroups (the
+// filled launches grow from 135 to 146 us), higher ones leave a second trailing launch.
+static int g_opt_wgrad_fill_epi = getenv("P5_WGRAD_FILL_EPI") ? atoi(getenv("P5_WGRAD_FILL_EPI")) : 8;
 static int wgrad_flush(P5Engine* e, hipStream_t main, bool is_head, bool on_side = true) {
   if (e->wg_pending.empty()) return 0;
   hipStream_t s = on_side ? wgrad_stream(e, main) : main;        // (side: it now waits for everything the main stream has been given)
@@ -492,6 +524,182 @@ static int wgrad_flush(P5Engine* e, hipStream_t main, bool is_head, bool on_side
   e->wg_sets = 0;
   return 0;
 }
+
+// ---- the weight-gradient plan of the whole backward ------------------------------------------------------------------------------
+// An encoder group of two layers is 192 units of 256x128 on 256 workgroups: a quarter of the CUs idle for the whole launch, while the
+// head's, the decoder's and the K/V block's weight gradients -- finished long before, not needed until the optimizer -- cost launches of
+// their own that barely fill the GPU.  Under the plan they wait in e->wg_pool, and every encoder flush fills its launch's short workgroups
+// from the pool: K/V block first (split by 256-row slices of its output, taken from the bottom rows up so that what is left keeps its
+// base pointers), then decoder layers in the order they became ready, then the head (by slices too).  What the last encoder group could
+// not take goes out as ordinary grouped launches.  Only which problems share a launch changes: every element keeps its one writer, every
+// tile its whole K range.
+// the pool as ordinary problems, appended to wg_pending (what nobody carried)
+static void wgrad_pool_drain(P5Engine* e) {
+  for (int kind : {2, 1, 0})
+    for (const P5Engine::WgPoolItem& it : e->wg_pool) {
+      if (it.kind != kind || it.rows_left <= 0) continue;
+      P5GemmArgs g = it.g;
+      if (it.rows_left < it.rows_all) g.M = it.rows_left * 256;      // (the upper slices were carried: rows [0, rows_left * 256) remain)
+      e->wg_pending.push_back(g);
+    }
+  e->wg_pool.clear();
+}
+// the largest filler load (in cost units) the kernel's dealing puts on one short workgroup -- p5_gemm5.h, the same arithmetic
+static long wgrad_fill_worst(int prim_units, int wcap, int nfill, int nheavy, int heavy_wgs, const int* units, const int* cost) {
+  int fu = 0;
+  for (int q = 0; q < nfill; ++q) fu += units[q];
+  int nwg = ((prim_units + fu + 7) / 8) * 8;
+  if (nwg > wcap) nwg = wcap;
+  const int gx = nwg >> 3, upx = (prim_units + 7) >> 3;
+  if (gx < 1) return -1;
+  long worst = 0;
+  std::vector<long> load((size_t)gx);
+  for (int x = 0; x < 8; ++x) {
+    int ulast = prim_units - x * upx;
+    ulast = ulast < 0 ? 0 : (ulast > upx ? upx : ulast);
+    const int rr = ulast % gx, ns = rr == 0 ? gx : gx - rr;
+    const bool two = heavy_wgs > 0 && heavy_wgs < ns;
+    for (int cls = 0; cls < (two ? 2 : 1); ++cls) {
+      const int q0 = two && cls == 1 ? nheavy : 0, q1 = two && cls == 0 ? nheavy : nfill;
+      const int n = two ? (cls == 0 ? heavy_wgs : ns - heavy_wgs) : ns;
+      for (int w = 0; w < n; ++w) load[w] = 0;
+      int pos = 0, first;
+      for (int q = q0; q < q1; ++q) {
+        const int sh = p5_fill_share(units[q], x, &first);
+        for (int k = 0; k < sh; ++k) load[(pos + k) % n] += cost[q];
+        pos += sh;
+      }
+      for (int w = 0; w < n; ++w) worst = load[w] > worst ? load[w] : worst;
+    }
+  }
+  return worst;
+}
+static void wgrad_fill_entry(P5FillProb& f, const P5GemmArgs& g, int row0, int rows) {
+  memset(&f, 0, sizeof(f));
+  f.A = (const bf16*)g.A + row0; f.B = g.B; f.C = (float*)g.C + (size_t)row0 * g.ldc;
+  f.M = rows; f.N = g.N; f.nk = g.K / 64; f.batch = 1; f.lda = g.lda; f.ldb = g.ldb; f.ldc = g.ldc; f.epi = g.epi; f.alpha = g.alpha;
+  f.acap = g.lda - row0;
+}
+static int wgrad_plan_flush(P5Engine* e, hipStream_t s, bool last) {
+  typedef P5Engine::WgPoolItem Item;
+  std::vector<Item>& pool = e->wg_pool;
+  const int nprim = (int)e->wg_pending.size();
+  long prim_units = 0;
+  int nkp = 0;
+  for (const P5GemmArgs& q : e->wg_pending) {
+    prim_units += (long)((q.M + 255) / 256) * ((q.N + 127) / 128);
+    nkp = q.K / 64 > nkp ? q.K / 64 : nkp;
+  }
+  // fillers exist in the wave-specialised 256x128 K-strided instance only: a group that takes another route today keeps it
+  const bool can_fill = !pool.empty() && nprim >= 1 && nprim <= P5_MAX_GROUP && g_opt_wgrad_wide && prim_units >= g_opt_wgrad_wide_min && p5l_gemm_fill_ok();
+  P5GemmGroupFill grp;
+  memset((void*)&grp, 0, sizeof(grp));
+  if (can_fill) {
+    const int wcap = g_opt_wgrad_wgs > 0 ? g_opt_wgrad_wgs : g_opt_g4_wgs;
+    const int epi_c = g_opt_wgrad_fill_epi > 0 ? g_opt_wgrad_fill_epi : 0;
+    const long allow = nkp + epi_c;          // a short workgroup may carry fillers worth ONE primary unit
+    int units[P5_MAX_FILL], cost[P5_MAX_FILL], nf = 0, nheavy = 0, hw = 0;
+    auto fits = [&](int n) { const long w = wgrad_fill_worst((int)prim_units, wcap, n, nheavy, hw, units, cost); return w >= 0 && w <= allow; };
+    // 1. the K/V block: as many 256-row slices as fit, on workgroups of their own (its K is the encoder's: one tile fills a workgroup)
+    for (Item& it : pool) {
+      if (it.kind != 2 || it.rows_left <= 0 || nf > 0) continue;
+      const int tn = (it.g.N + 127) / 128, c1 = it.g.K / 64 + epi_c, cap = (int)(allow / c1);
+      if (cap < 1) continue;
+      for (int t = it.rows_left; t >= 1; --t) {
+        units[0] = t * tn; cost[0] = c1;
+        nheavy = 1; hw = ((units[0] + 7) / 8 + cap - 1) / cap;
+        if (!fits(1)) continue;
+        const int r0 = (it.rows_left - t) * 256, r1 = it.rows_left * 256 < it.g.M ? it.rows_left * 256 : it.g.M;
+        wgrad_fill_entry(grp.f[0], it.g, r0, r1 - r0);
+        it.rows_left -= t;
+        nf = 1;
+        break;
+      }
+      if (nf == 0) { nheavy = 0; hw = 0; }
+    }
+    // 2. decoder layers, whole, in the order they became ready: one entry per weight, the layers as its batch
+    {
+      std::vector<int> idx;       // pool indices of decoder problems, in order
+      for (size_t k = 0; k < pool.size(); ++k) if (pool[k].kind == 1) idx.push_back((int)k);
+      int per = 0;                // problems per layer
+      while (per < (int)idx.size() && pool[idx[per]].layer == pool[idx[0]].layer) ++per;
+      const int nl = per ? (int)idx.size() / per : 0;
+      int take = 0;
+      P5FillProb ent[P5_MAX_FILL];
+      for (int n = 1; n <= nl && per > 0 && nf + per <= P5_MAX_FILL; ++n) {
+        bool ok = true;
+        for (int k = 0; k < per && ok; ++k) {
+          const P5GemmArgs& g0 = pool[idx[k]].g;
+          P5FillProb f;
+          wgrad_fill_entry(f, g0, 0, g0.M);
+          f.batch = n;
+          if (n > 1) {
+            const P5GemmArgs& g1 = pool[idx[per + k]].g;
+            const long long dA = (const char*)g1.A - (const char*)g0.A, dB = (const char*)g1.B - (const char*)g0.B, dC = (const char*)g1.C - (const char*)g0.C;
+            ok = dA % 16 == 0 && dB % 16 == 0 && dC % 16 == 0;
+            f.sA = dA / 2; f.sB = dB / 2; f.sC = dC / 4;
+            for (int l = 1; l < n && ok; ++l) {
+              const P5GemmArgs& gl = pool[idx[l * per + k]].g;
+              ok = gl.M == g0.M && gl.N == g0.N && gl.K == g0.K && gl.lda == g0.lda && gl.ldb == g0.ldb && gl.ldc == g0.ldc && gl.alpha == g0.alpha && gl.epi == g0.epi &&
+                   (const char*)gl.A - (const char*)g0.A == dA * l && (const char*)gl.B - (const char*)g0.B == dB * l && (const char*)gl.C - (const char*)g0.C == dC * l;
+            }
+          }
+          units[nf + k] = ((g0.M + 255) / 256) * ((g0.N + 127) / 128) * n;
+          cost[nf + k] = g0.K / 64 + epi_c;
+          ent[k] = f;
+        }
+        if (!ok || !fits(nf + per)) break;
+        take = n;
+        for (int k = 0; k < per; ++k) grp.f[nf + k] = ent[k];
+      }
+      if (take > 0) {
+        // (units[] holds the last layer count TRIED, one more than `take` when the loop broke: the head below is fitted against what was taken)
+        for (int k = 0; k < per; ++k) units[nf + k] = grp.f[nf + k].batch * ((grp.f[nf + k].M + 255) / 256) * ((grp.f[nf + k].N + 127) / 128);
+        nf += per;
+        std::vector<Item> rest;
+        int seen = 0;
+        for (const Item& it : pool) {
+          if (it.kind == 1 && seen < take * per) { ++seen; continue; }
+          rest.push_back(it);
+        }
+        pool.swap(rest);
+      }
+    }
+    // 3. the head: the most 256-row slices that still fit (bisection: the worst load grows with the slice count)
+    for (Item& it : pool) {
+      if (it.kind != 0 || it.rows_left <= 0 || nf >= P5_MAX_FILL) continue;
+      const int tn = (it.g.N + 127) / 128;
+      cost[nf] = it.g.K / 64 + epi_c;
+      int lo = 0, hi = it.rows_left;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        units[nf] = mid * tn;
+        if (fits(nf + 1)) lo = mid; else hi = mid - 1;
+      }
+      if (lo > 0) {
+        const int r0 = (it.rows_left - lo) * 256, r1 = it.rows_left * 256 < it.g.M ? it.rows_left * 256 : it.g.M;
+        wgrad_fill_entry(grp.f[nf], it.g, r0, r1 - r0);
+        it.rows_left -= lo;
+        ++nf;
+      }
+      break;
+    }
+    grp.nfill = nf; grp.nheavy = nheavy; grp.heavy_wgs = hw;
+  }
+  if (grp.nfill > 0) {
+    grp.nprob = nprim;
+    for (int k = 0; k < nprim; ++k) grp.p[k] = e->wg_pending[k];
+    const int keep = g_opt_g4_wgs;
+    if (g_opt_wgrad_wgs > 0) g_opt_g4_wgs = g_opt_wgrad_wgs;
+    const int rc = launch_gemm_fill(grp, s);
+    g_opt_g4_wgs = keep;
+    P5_TRY(rc);
+    e->wg_pending.clear();
+    e->wg_sets = 0;
+  }
+  if (last) wgrad_pool_drain(e);
+  return wgrad_flush(e, s, false, false);
+}
 // ONE predicate for "every weight gradient of this step's backward takes the deferred, layer-grouped path" (token counts that are
 // multiples of 64; the other conditions of linear_wgrad -- leading dimensions, 16-byte alignment -- hold by construction of the layout):
 // the folded-norm forward, the storing backward and linear_wgrad itself all depend on it and must not drift apart.
@@ -507,6 +715,13 @@ static int linear_wgrad(P5Engine* e, hipStream_t main, const void* dy, int lddy,
     memset(&g, 0, sizeof(g));
     g.A = dy; g.B = x; g.C = dW; g.M = N_out; g.N = K_in; g.K = M; g.lda = lddy; g.ldb = ldx; g.ldc = K_in;
     g.a_ks = 1; g.b_ks = 1; g.epi = e->wg_epi; g.c_f32 = 1; g.splitk = 1; g.alpha = alpha; g.drop = no_drop();
+    if (e->wg_plan && e->wg_pool_kind >= 0) {      // (reads no rotating set: nothing to note in wg_sets)
+      P5Engine::WgPoolItem it;
+      memset(&it, 0, sizeof(it));
+      it.g = g; it.kind = e->wg_pool_kind; it.layer = e->wg_pool_layer; it.rows_left = it.rows_all = (g.M + 255) / 256;
+      e->wg_pool.push_back(it);
+      return 0;
+    }
     e->wg_pending.push_back(g);
     if (e->sub >= 0) e->wg_sets |= 1u << (e->sub % P5_NSETS);
     return 0;
@@ -691,6 +906,18 @@ static int64_t layout_ws(P5Engine* e, char* base, int B, int L, int T, bool with
     e->dy = e->dy2[0]; e->dqkv = e->dqkv2[0]; e->dkv = e->dkv2[0]; e->dh = e->dh2[0]; e->du = e->du2[0];
     e->dkv_all = T > 0 ? b.take(M * (size_t)c.n_dec_layers * 2 * in * sz) : nullptr;     // d(K/V) of all layers, same column layout
     e->dlogits = b.take(Md * Vp * sz);
+    // the decoder sub-layers' own temporaries (weight-gradient plan, bf16 engine): [ffn | cross attention | self attention] per layer, in
+    // the order the backward reaches them -- constant strides from layer to layer, so that one filler entry covers a weight of all layers
+    e->ds_dy.clear(); e->ds_dh.clear(); e->ds_du.clear(); e->ds_dqkv.clear();
+    if (T > 0 && c.dtype == 1) {
+      for (int l = 0; l < c.n_dec_layers; ++l)
+        for (int k = 0; k < 3; ++k) {
+          e->ds_dy.push_back(b.take(Md * d * sz));
+          e->ds_dh.push_back(k == 0 ? b.take(Md * F * sz) : nullptr);
+          e->ds_du.push_back(k == 0 && c.gated_gelu ? b.take(Md * 2 * F * sz) : nullptr);
+          e->ds_dqkv.push_back(k != 0 ? b.take(Md * (k == 1 ? 1 : 3) * in * sz) : nullptr);      // (cross attention: dQ only)
+        }
+    }
   }
   return (int64_t)((b.off + 255) & ~(size_t)255);
 }
@@ -1054,6 +1281,18 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
   const int d = c.d_model, in = e->inner, H = c.n_heads, M = e->M, Md = e->Md;
   const int nd = c.n_dec_layers, ne = c.n_enc_layers;
   if (stage == 0) {
+    // the weight-gradient plan needs the whole backward in one call (gradient ranges become final in another order), one stream, every
+    // weight gradient on the grouped path, and the decoder's own temporaries in the workspace.  It moves the tied head's weight gradient
+    // from this stage to the encoder's launches, and on a storing micro-batch that store is what initialises shared.weight's gradient:
+    // every embedding kernel that adds into it must run behind the last encoder group.  The segmented sums of the last stage do; the
+    // atomic scatter of embed_det 0 adds the decoder's rows in stage nd + 1 -- no plan then.
+    e->wg_plan = sizeof(T) == 2 && g_opt_wgrad_fill != 0 && g_opt_embed_det != 0 && e->whole_backward && !e->side && wg_all_deferred<T>(e) &&
+                 (int)e->ds_dy.size() == 3 * nd;
+    e->wg_pool.clear();
+  }
+  e->wg_pool_kind = !e->wg_plan ? -1 : stage == 0 ? 0 : stage <= nd ? 1 : stage == nd + 1 ? 2 : -1;
+  e->wg_pool_layer = stage;
+  if (stage == 0) {
     if (e->grads_keep) {
       e->wg_epi = P5_EPI_ACCUM;                 // a later micro-batch of an accumulation group: everything adds
     } else if (g_opt_grad_store_first && wg_all_deferred<T>(e)) {
@@ -1227,6 +1466,11 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     // whole backward runs in one call and nobody waits for per-layer gradient ranges)
     // (the top layer's group also carries the cross-attention K/V block queued in the previous stage: 5 problems; then pairs of layers)
     const bool pairs = (e->whole_backward || e->stage_pairs) && g_opt_wgrad_layers > 1;
+    if (e->wg_plan) {
+      // pairs from the top ([L5,L4] [L3,L2] [L1,L0]; an odd bottom layer alone), each filled from the pool
+      if (!pairs || i == 0 || ((ne - 1 - i) & 1)) return wgrad_plan_flush(e, s, i == 0);
+      return 0;
+    }
     if (!pairs || i == 0 || e->wg_pending.size() >= 5) return wgrad_flush(e, s, false, (g_opt_wgrad_side & 2) != 0);
     return 0;
   }
@@ -2917,6 +3161,8 @@ int p5_set_option(const char* name, int value) {
   else if (!strcmp(name, "wgrad_wide")) g_opt_wgrad_wide = value;
   else if (!strcmp(name, "wgrad_side")) g_opt_wgrad_side = value;
   else if (!strcmp(name, "wgrad_layers")) g_opt_wgrad_layers = value;
+  else if (!strcmp(name, "wgrad_fill")) g_opt_wgrad_fill = value;
+  else if (!strcmp(name, "wgrad_fill_epi")) g_opt_wgrad_fill_epi = value;
   else if (!strcmp(name, "gemm_ring_n512")) g_opt_gemm_ring_n512 = value;
   else if (!strcmp(name, "gemm_wide")) g_opt_gemm_wide = value;
   else if (!strcmp(name, "gemm_ws")) g_opt_gemm_ws = value;
