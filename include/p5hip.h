@@ -214,6 +214,33 @@ int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
                     int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
                     int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids /* device uint32 [B] */, uint32_t draw_base,
                     float temperature, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream);
+/* ---- stochastic beam search: S slates of K DISTINCT items per user, a sample without replacement (openp5_amd/csrc/p5_sbs.h) ----
+ * The distribution is that of p5_sample_items.  A slate is the K items with the largest G(item) = log p(item) + Gumbel noise, largest first:
+ * a sample without replacement in sequential-sampling (Plackett-Luce) order (Kool, van Hoof, Welling 2019), computed top-down over the trie
+ * with K beams per slate.  A live beam (phi_S, G_S) gives its allowed children phi_i = phi_S + token log-probability, g_i = phi_i -
+ * log(-log u_i), Z = max g_i (ties: the lowest edge); the argmax child keeps G_S exactly, every other child gets
+ * G_S - max(v, 0) - log1p(exp(-|v|)) with v = G_S - g_i + log1p(-exp(g_i - Z)).  The beams of the next step are the K best of the children
+ * of the live beams and the finished beams (carried), by (perturbed value desc, global CSR edge index asc).  The root has (0, 0).
+ *   trie, excluded_nodes / excluded_words, max_children, seed, stream_ids, temperature: as p5_sample_items.  The trie must be tree-shaped
+ *     (every edge reached by one prefix): the uniform of a child is a pure function of (seed, stream_ids[b], slate_base + s, step, GLOBAL CSR
+ *     edge index child_off[node] + i) -- csrc/p5_rng.h -- so the perturbed value of a trie node does not depend on K, on the batch or on
+ *     the beam slot: the slate of K' < K is the first K' entries of the slate of K, and user chunks / slate ranges return the same bits.
+ *   out_seq int32 [B, S, K, max_len], out_logprob fp32 [B, S, K] (phi: the item's log-probability), out_perturbed fp32 [B, S, K] (descending,
+ *     <= 0), out_tok_logprob fp32 [B, S, K, max_len] by position, out_len int32 [B, S, K].  Fewer than K allowed items: the trailing slots
+ *     hold the all-pad sequence behind the decoder start, log-probability -inf, perturbed -inf, length 0.
+ * A forced prefix (p5_generate_set_forced_prefix, option "gen_ff") is honoured as by p5_sample_items: behind it beam 0 of every slate is live
+ * with (0, 0).  Enqueues max_len - 1 - (forced steps) steps of plain launches (decoder without head, row / select / commit kernels) and
+ * returns without synchronising; no early stop, no hipGraph.  Every value has one writer: two calls return the same bits.
+ * Limits: 1 <= K <= 4096, 1 <= S, S x K <= 4096 rows per user and call, 2 <= max_len <= 128, L <= 512, temperature > 0, d_model <= 1024.
+ * The workspace (exact; p5_sample_slates_workspace_bytes returns -1 outside the limits): that of p5_sample_items for S x K rows per user,
+ * second sequence / log-probability / ancestry buffers (rows change places), and the step's scratch, which follows the fan-out: two
+ * [R, max_children] fp32 rows and the [R, min(max_children, K)] 64-bit key lists. */
+int64_t p5_sample_slates_workspace_bytes(const P5Engine* e, int B, int L, int S, int K, int max_len, int max_children, int excluded_words);
+int p5_sample_slates(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S, int K,
+                     int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                     int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids /* device uint32 [B] */, uint32_t slate_base,
+                     float temperature, int* out_seq, float* out_logprob, float* out_perturbed, float* out_tok_logprob, int* out_len, void* ws,
+                     int64_t ws_bytes, void* stream);
 /* ---- verified generation: the bf16 search proposes, an fp32 pass decides (openp5_amd/csrc/p5_verify.h) ----
  * The reference ranks by the fp32 scores of HF beam search (DistributedRunner.py:361-387, utils/evaluate.py:37-58).  Protocol, two engines
  * over the SAME master parameter arena (a bf16 one for the draft, an fp32 one -- dtype 0 -- for the verification), one stream:

@@ -67,6 +67,8 @@ PROTOTYPES = {
     "p5_generate_set_forced_prefix": (i32, [vp, vp, vp, i32]),
     "p5_sample_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32, i32]),
     "p5_sample_items": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, u32, vp, u32, f32, vp, vp, vp, vp, vp, i64, vp]),
+    "p5_sample_slates_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32, i32, i32]),
+    "p5_sample_slates": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, u32, vp, u32, f32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "p5_generate_history_count": (i64, [i32, i32, i32]),
     "p5_generate_draft": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     "p5_verify_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32, i32, i32]),

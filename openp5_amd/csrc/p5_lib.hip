@@ -27,6 +27,7 @@
 #include "p5_prune.h"
 #include "p5_bound.h"
 #include "p5_sample.h"
+#include "p5_sbs.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -2111,6 +2112,104 @@ static int sample_items_impl(P5Engine* e, int B, int L, int S, int max_len, cons
   return P5_KCHECK();
 }
 
+// ---- stochastic beam search (p5_sbs.h): S slates of K distinct items per user, R = B * S * K decode rows ----
+// The workspace is layout_sample's for S * K rows per user plus the rows' second sequence / log-probability / ancestry buffers (rows change
+// places) and the step's scratch, which DOES follow the fan-out: two [R, max_c] fp32 rows (token log-probabilities, perturbed values) and
+// the [R, min(max_c, K)] key lists.
+static int64_t layout_sbs(P5Engine* e, char* base, int B, int L, int S, int K, int max_len, int max_c, GenWs* g, P5SbsState* ps) {
+  const P5Config& c = e->c;
+  const size_t sz = c.dtype == 1 ? 2 : 4;
+  const int d = c.d_model, in = e->inner, F = c.d_ff;
+  const size_t R = (size_t)B * S * K;
+  const size_t C = (size_t)(max_c < K ? max_c : K);
+  const int ffcap = g_opt_gen_ff ? (max_len - 2 < P5_FF_MAX ? (max_len - 2 > 0 ? max_len - 2 : 0) : P5_FF_MAX) : 0;
+  const int64_t enc_bytes = layout_ws(e, base, B, L, ffcap, false);
+  Bump b{base, (size_t)enc_bytes};
+  GenWs tmp;
+  GenWs& w = g ? *g : tmp;
+  memset(&w, 0, sizeof(w));
+  w.ff_labels = (int64_t*)b.take((size_t)B * (ffcap > 0 ? ffcap : 1) * 8);
+  w.ff_nll = (float*)b.take((size_t)B * (ffcap > 0 ? ffcap : 1) * 4);
+  {
+    char* kv_all = (char*)b.take((size_t)B * L * c.n_dec_layers * 2 * in * sz);
+    w.ldkv = c.n_dec_layers * 2 * in;
+    for (int i = 0; i < c.n_dec_layers; ++i) {
+      w.kv_cross[i] = base ? (void*)(kv_all + (size_t)i * 2 * in * sz) : nullptr;
+      w.cache[i] = b.take((size_t)max_len * R * 2 * in * sz);
+    }
+  }
+  w.qkv = b.take(R * 3 * in * sz); w.q = b.take(R * in * sz); w.o = b.take(R * in * sz);
+  w.h = b.take(R * (c.gated_gelu ? 3 : 1) * F * sz); w.hn = b.take(R * d * sz);
+  w.x32 = (float*)b.take(R * d * 4);
+  P5SbsState st;
+  memset(&st, 0, sizeof(st));
+  st.seq = (int*)b.take(R * max_len * 4); st.seq_next = (int*)b.take(R * max_len * 4);
+  st.tok_lp = (float*)b.take(R * max_len * 4); st.tok_lp_next = (float*)b.take(R * max_len * 4);
+  st.anc = (int*)b.take(R * max_len * 4); st.anc_next = (int*)b.take(R * max_len * 4);
+  st.phi = (float*)b.take(R * 4); st.G = (float*)b.take(R * 4);
+  st.node = (int*)b.take(R * 4); st.edge = (int*)b.take(R * 4); st.len = (int*)b.take(R * 4);
+  st.steps = (int*)b.take((size_t)(max_len + 1) * 4);
+  st.flags = (int*)b.take(64);
+  st.lp = (float*)b.take(R * max_c * 4); st.gt = (float*)b.take(R * max_c * 4);
+  st.row_key = (unsigned long long*)b.take(R * C * 8); st.row_n = (int*)b.take(R * 4);
+  st.sel_parent = (int*)b.take(R * 4); st.sel_tok = (int*)b.take(R * 4); st.sel_node = (int*)b.take(R * 4);
+  st.sel_edge = (int*)b.take(R * 4); st.sel_len = (int*)b.take(R * 4);
+  st.sel_phi = (float*)b.take(R * 4); st.sel_G = (float*)b.take(R * 4); st.sel_lp = (float*)b.take(R * 4);
+  st.x32 = w.x32;
+  st.E32 = e->P ? e->P + e->off_E : nullptr;
+  st.d = d;
+  // the decoder of the step finds the two ancestry tables and its done flag where the beam state keeps them
+  w.st.anc = st.anc; w.st.anc_next = st.anc_next; w.st.flags = st.flags;
+  if (ps) *ps = st;
+  return (int64_t)((b.off + 255) & ~(size_t)255);
+}
+
+template <class T>
+static int sbs_impl(P5Engine* e, int B, int L, int S, int K, int max_len, const int* child_off, const int* child_tok, const int* child_node,
+                    const uint32_t* excluded, int excl_words, int max_c, uint32_t seed, const uint32_t* stream_ids, uint32_t slate_base, float tau,
+                    int* out_seq, float* out_logprob, float* out_perturbed, float* out_tok_logprob, int* out_len, char* ws, hipStream_t s) {
+  const P5Config& c = e->c;
+  const int d = c.d_model, R = B * S * K;
+  GenWs w;
+  P5SbsState st;
+  layout_sbs(e, ws, B, L, S, K, max_len, max_c, &w, &st);
+  e->gen.active = false;              // (a search begun on this engine shared the encoder buffers: it cannot be continued)
+  e->gen_hist_next = nullptr;
+  if (!excluded) excl_words = 0;
+  w.mask_copy = (int64_t*)e->mask;    // plain launches: the caller's arrays are read in place
+  P5Forced ff;
+  P5_TRY(gen_prepare<T>(e, w, B, L, S * K, max_len, nullptr, s, &ff));
+  const int F = ff.n;
+  P5_LAUNCH(p5_sbs_init_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, st, ff, child_off, child_tok, child_node, B, S, K, max_len, c.pad_id,
+            c.pad_id);
+  P5_TRY(P5_KCHECK());
+  P5SbsArgs a;
+  a.hn = w.hn; a.E = Wc<T>(e, e->off_E); a.d = d; a.alpha = 1.0f / sqrtf((float)d); a.tau = tau;
+  a.child_off = child_off; a.child_tok = child_tok; a.child_node = child_node;
+  a.excluded = excl_words > 0 ? excluded : nullptr; a.excl_words = excl_words;
+  a.S = S; a.K = K; a.R = R; a.max_c = max_c; a.C = max_c < K ? max_c : K; a.max_len = max_len; a.eos_id = c.eos_id; a.pad_id = c.pad_id;
+  a.start_id = c.pad_id; a.F = F;
+  a.seed = seed; a.stream_ids = stream_ids; a.slate_base = slate_base;
+  // no early stop and nothing read back: finished beams are carried, dead slots run the decoder on the pad embedding
+  for (int cur_len = F + 1; cur_len < max_len; ++cur_len) {
+    P5_TRY(decode_step2<T>(e, w, B, L, S * K, max_len, s, (const int*)(st.steps + cur_len), false));
+    a.cur_len = cur_len;
+    P5_LAUNCH((p5_sbs_row_kernel<T>), dim3(R), dim3(256), 0, s, st, a);
+    P5_TRY(P5_KCHECK());
+    P5_LAUNCH(p5_sbs_select_kernel, dim3(B * S), dim3(256), 0, s, st, a);
+    P5_TRY(P5_KCHECK());
+    const bool odd = (cur_len & 1) != 0;       // the decoder of this step read `anc` (odd cur_len) or `anc_next` (even)
+    P5_LAUNCH(p5_sbs_commit_kernel, dim3((R + P5_SBS_COMMIT_ROWS - 1) / P5_SBS_COMMIT_ROWS), dim3(256), 0, s, st, a,
+              (const int*)(odd ? st.anc : st.anc_next), odd ? st.anc_next : st.anc);
+    P5_TRY(P5_KCHECK());
+    { int* t = st.seq; st.seq = st.seq_next; st.seq_next = t; }
+    { float* t = st.tok_lp; st.tok_lp = st.tok_lp_next; st.tok_lp_next = t; }
+  }
+  P5_LAUNCH(p5_sbs_finish_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, out_seq, out_logprob, out_perturbed, out_tok_logprob, out_len, st, R,
+            max_len);
+  return P5_KCHECK();
+}
+
 // ---- verified generation (p5_verify.h): plan -> encode -> run on an fp32 engine bound to the same master parameters ----
 struct VerifyWs {
   P5VerifyPlan pl;
@@ -3780,6 +3879,42 @@ int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
                                        stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream)
              : sample_items_impl<float>(e, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed,
                                         stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream);
+}
+static int sbs_limits(int B, int S, int K, int max_len) {
+  P5_REQUIRE(B >= 1 && K >= 1 && K <= P5_SBS_MAX_K, "sample_slates: 1 <= slate size <= 4096");
+  P5_REQUIRE(S >= 1 && (int64_t)S * K <= P5_WIDE_MAX_K, "sample_slates: 1 <= slates per user, slates x slate size <= 4096 rows per user and call");
+  P5_REQUIRE(max_len >= 2 && max_len <= P5_MAX_LEN, "sample_slates: 2 <= max_length <= 128 (P5_MAX_LEN)");
+  return 0;
+}
+int64_t p5_sample_slates_workspace_bytes(const P5Engine* e, int B, int L, int S, int K, int max_len, int max_children, int excluded_words) {
+  (void)excluded_words;       // (the exclusion bitmap is read in place)
+  if (sbs_limits(B, S, K, max_len) != 0) return -1;
+  if (max_children < 1 || L < 1 || L > 512) { fail("sample_slates: max_children >= 1, 1 <= L <= 512"); return -1; }
+  P5Engine tmp = *e;
+  return layout_sbs(&tmp, nullptr, B, L, S, K, max_len, max_children, nullptr, nullptr);
+}
+int p5_sample_slates(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S, int K,
+                     int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                     int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids, uint32_t slate_base, float temperature,
+                     int* out_seq, float* out_logprob, float* out_perturbed, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes,
+                     void* stream) {
+  P5_REQUIRE(e->P, "engine not bound");
+  P5_TRY(sbs_limits(B, S, K, max_len));
+  P5_REQUIRE(L >= 1 && L <= 512, "1 <= L <= 512");
+  P5_REQUIRE(max_children >= 1, "max_children");
+  P5_REQUIRE(e->lut_half >= max_len, "bucket LUT too short");
+  P5_REQUIRE(temperature > 0.f && temperature < __builtin_huge_valf(), "sample_slates: temperature > 0");
+  P5_REQUIRE(excluded_words >= 0 && (excluded_nodes || excluded_words == 0), "excluded_nodes / excluded_words");
+  P5_REQUIRE(stream_ids && out_seq && out_logprob && out_perturbed && out_tok_logprob && out_len, "sample_slates: stream_ids / outputs");
+  P5_REQUIRE(e->c.d_model % (8 * (e->c.dtype == 1 ? 8 : 4)) == 0 && e->c.d_model <= 1024, "sample_slates: d_model a multiple of 8 x 16 bytes, <= 1024");
+  const int64_t need = layout_sbs(e, nullptr, B, L, S, K, max_len, max_children, nullptr, nullptr);
+  P5_REQUIRE(ws_bytes >= need, "sample_slates: workspace too small (p5_sample_slates_workspace_bytes)");
+  e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
+  return e->c.dtype == 1
+             ? sbs_impl<bf16>(e, B, L, S, K, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed, stream_ids,
+                              slate_base, temperature, out_seq, out_logprob, out_perturbed, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream)
+             : sbs_impl<float>(e, B, L, S, K, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed, stream_ids,
+                               slate_base, temperature, out_seq, out_logprob, out_perturbed, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream);
 }
 int64_t p5_generate_history_count(int B, int K, int max_len) { return 4 + (int64_t)max_len * P5_HIST_FIELDS * B * K; }
 int p5_generate_draft(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int K,

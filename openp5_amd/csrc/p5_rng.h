@@ -56,6 +56,10 @@ __device__ static inline uint32_t p5_seed(const P5Drop& d) {
 // All integer arithmetic is modulo 2^32.  u takes the 2^23 values (j + 0.5) / 2^23: each is exact in fp32 (24 significant bits), so
 // 2^-24 <= u <= 1 - 2^-24 and u is never 0 or 1; with 24 hash bits, (h >> 8) + 0.5f would round to 2^24 for the largest j and give u = 1.
 // The Gumbel of the child is g = -logf(-logf(u)).
+// Stochastic beam search (p5_sbs.h) uses the same two functions with other coordinates: `draw` is the slate index (slate_base + slate
+// within the user) and `child` is the GLOBAL CSR edge index of the child (child_off[node] + position).  The position alone is not enough
+// there: two beams of one slate sit at different nodes in the same step and must not share noise.  In a tree-shaped trie an edge is
+// reached by one prefix, so every (slate, step, edge) names one Gumbel, whatever the beam slot its parent occupies.
 __host__ __device__ static inline uint32_t p5_sample_row_key(uint32_t seed, uint32_t stream, uint32_t draw, uint32_t step) {
   uint32_t k = p5_mix32(seed ^ p5_mix32(stream * 0x9E3779B1u + 0x7F4A7C15u));
   k = p5_mix32(k ^ draw);

@@ -23,6 +23,7 @@ import os
 import ctypes
 import threading
 import math
+import types
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional
 
@@ -192,7 +193,7 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
-        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("sample": sample_items() / generate(do_sample=True); "rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
+        self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("sample": sample_items() / generate(do_sample=True); "slates": sample_slates(); "rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
                            "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0,
                            "search_calls": 0, "search_certified_users": 0, "search_fallback_users": 0, "search_declined_users": 0,
@@ -221,6 +222,7 @@ class P5T5Native(nn.Module):
         self._search_seed_hook = None       # test hook: _search_seed_hook(seeds int64 [B, S, T]) before the search begins; may edit the sequences in place
         self.cand_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0}      # score_candidates()
         self.sample_stats = {"calls": 0, "users": 0, "engine_calls": 0, "rows_per_call": 0, "forced_prefix_steps": 0}      # sample_items()
+        self.slate_stats = {"calls": 0, "users": 0, "engine_calls": 0, "rows_per_call": 0, "forced_prefix_steps": 0}       # sample_slates()
         self._sample_seed0 = int(seed) & 0xFFFFFFFF      # sample_items(seed=None): call n of this model draws with seed mix32(seed0 + golden * (n + 1))
         self._sample_calls = 0
         self._warned_wide_verified = False
@@ -1364,14 +1366,7 @@ class P5T5Native(nn.Module):
         if excluded_items is not None:
             if trie.grafted:
                 raise ValueError("sample_items(excluded_items=...): a trie with an appended trie (Trie.append) cannot be indexed")
-            if len(excluded_items) != input_ids.shape[0]:
-                raise ValueError(f"excluded_items: one list of item indices per user ({input_ids.shape[0]}), got {len(excluded_items)}")
-            n_items = int(trie.item_edges.shape[0])
-            for b, items in enumerate(excluded_items):
-                it = np.asarray(list(items), dtype=np.int64)
-                if it.size and (it.min() < 0 or it.max() >= n_items):
-                    raise ValueError(f"excluded_items[{b}]: item indices must be in 0 .. {n_items - 1}")
-            excl_np = trie.excluded_bitmap(excluded_items)
+            excl_np = self._excluded_items_bitmap(trie, excluded_items, input_ids.shape[0])
         seq, lp, tok_lp, ln = self._sample(input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base)
         B, _, T = seq.shape
         item_index = None
@@ -1410,10 +1405,23 @@ class P5T5Native(nn.Module):
             ok = ok & (hit | ~active)
         return torch.where(ok, leaf_item[node], torch.full_like(node, -1))
 
-    def _sample(self, input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, max_length=None):
-        """The engine calls of sample_items / generate(do_sample=True): (sequences int32 [B, S, T], log-probability [B, S], per-position
-        log-probabilities [B, S, T], generated tokens [B, S]).  `excl_np`: uint32 [B, words] excluded-node bitmap or None."""
-        lib, dev = self._lib, self._be.device
+    @staticmethod
+    def _excluded_items_bitmap(trie, excluded_items, B):
+        """the excluded-node bitmap of per-user lists of item indices, checked"""
+        if len(excluded_items) != B:
+            raise ValueError(f"excluded_items: one list of item indices per user ({B}), got {len(excluded_items)}")
+        n_items = int(trie.item_edges.shape[0])
+        for b, items in enumerate(excluded_items):
+            it = np.asarray(list(items), dtype=np.int64)
+            if it.size and (it.min() < 0 or it.max() >= n_items):
+                raise ValueError(f"excluded_items[{b}]: item indices must be in 0 .. {n_items - 1}")
+        return trie.excluded_bitmap(excluded_items)
+
+    def _sampling_setup(self, input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, base, base_name, max_length=None):
+        """What sample_items and sample_slates share before their engine calls: the checked temperature, the inputs and the trie on the
+        device, T, the stream ids, the index of the first draw / slate (`base`, S of them), the seed (None: the next of the per-model
+        counter), the excluded-node bitmap and the forced-prefix rule with the users it leaves to the engine."""
+        dev = self._be.device
         tau = float(temperature)
         if not (tau > 0.0 and math.isfinite(tau)):
             raise ValueError(f"temperature={temperature!r}: a finite value > 0")
@@ -1438,9 +1446,9 @@ class P5T5Native(nn.Module):
                 raise ValueError(f"streams: one id per user ({B}), got {st_np.shape[0]}")
             st_np = (st_np & 0xFFFFFFFF).astype(np.uint32)
         streams_t = torch.from_numpy(st_np.view(np.int32).copy()).to(dev)
-        draw_base = int(draw_base)
-        if draw_base < 0 or draw_base + S > 2 ** 32:
-            raise ValueError(f"draw_base={draw_base}: draw indices are uint32")
+        base = int(base)
+        if base < 0 or base + S > 2 ** 32:
+            raise ValueError(f"{base_name}={base}: {base_name.split('_')[0]} indices are uint32")
         if seed is None:
             with self._stats_lock:
                 n = self._sample_calls
@@ -1469,6 +1477,18 @@ class P5T5Native(nn.Module):
                 words = excl_np[:, [x >> 5 for x in fnode]]
                 bits = np.asarray([x & 31 for x in fnode], dtype=np.uint32)
                 alive = np.nonzero(~((words >> bits[None, :]) & 1).any(axis=1))[0]
+        return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, input_ids=input_ids, whole_word_ids=whole_word_ids, attention_mask=attention_mask,
+                                     B=B, L=L, T=T, streams_t=streams_t, base=base, seed=seed, excl_t=excl_t, excl_words=excl_words, ftok=ftok, fnode=fnode,
+                                     alive=alive)
+
+    def _sample(self, input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, max_length=None):
+        """The engine calls of sample_items / generate(do_sample=True): (sequences int32 [B, S, T], log-probability [B, S], per-position
+        log-probabilities [B, S, T], generated tokens [B, S]).  `excl_np`: uint32 [B, words] excluded-node bitmap or None."""
+        lib, dev = self._lib, self._be.device
+        q = self._sampling_setup(input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, "draw_base", max_length)
+        tau, off, tok, nxt, input_ids, whole_word_ids, attention_mask = q.tau, q.off, q.tok, q.nxt, q.input_ids, q.whole_word_ids, q.attention_mask
+        B, L, T, streams_t, draw_base, seed, excl_t, excl_words, ftok, fnode, alive = (q.B, q.L, q.T, q.streams_t, q.base, q.seed, q.excl_t, q.excl_words,
+                                                                                       q.ftok, q.fnode, q.alive)
         lane = self._cur_lane()
         engine, sp = lane.engine, self._be.stream_ptr()
         maxc = max(1, trie.max_children)
@@ -1517,6 +1537,103 @@ class P5T5Native(nn.Module):
             st["forced_prefix_steps"] = len(ftok)
         self.last_generate_path = "sample"
         return seq, lp, tok_lp, ln
+
+    # ------------------------------------------------------------------ stochastic beam search (csrc/p5_sbs.h)
+    SLATE_MAX_K = 4096            # beams of one slate, and decode rows per user of one engine call (slates x slate size)
+
+    @torch.no_grad()
+    def sample_slates(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, slate_size: int = 1, num_slates: int = 1,
+                      temperature: float = 1.0, excluded_items=None, seed: Optional[int] = None, streams=None, slate_base: int = 0):
+        """Draw `num_slates` slates of `slate_size` DISTINCT items per user: each slate is a sample without replacement from the
+        distribution `sample_items` draws from, in sequential-sampling (Plackett-Luce) order -- exploration slates, on-policy lists for
+        listwise / policy-gradient fine-tuning, without-replacement estimators.  Stochastic beam search (Kool, van Hoof, Welling 2019) on
+        the item trie (csrc/p5_sbs.h): the slate is the top `slate_size` of log p(item) + Gumbel noise, found with `slate_size` decode rows.
+        `excluded_items`, `seed`, `streams`, `temperature`: as `sample_items`; `slate_base` is the index of the first slate.  The perturbed
+        value of an item is a pure function of (weights, the user's input, seed, stream, slate index): the slate of K' < K is the first K'
+        entries of the slate of K, and user chunks (at most `wide_max_rows` decode rows per engine call; users first, then slate ranges, a
+        slate is never split) or slate ranges split by hand with `slate_base` do not change a bit.  Tree-shaped tries only.
+        Returns {"sequences" int64 [B * S * K, T], "sequences_logprob" fp32 [B * S * K] (log p(item)), "perturbed" fp32 [B, S, K]
+        (descending, <= 0), "token_logprobs" fp32 [B * S * K, T - 1], "item_index" int64 [B, S, K]}.  A user with fewer than K allowed items
+        gets trailing slots with the all-pad sequence, log-probability -inf, perturbed -inf and item_index -1."""
+        if trie is None:
+            raise ValueError("sample_slates() needs the item trie (Trie / CompiledTrie)")
+        trie = self._compiled_trie(trie)
+        if trie.grafted:
+            raise ValueError("sample_slates(): a trie with an appended trie (Trie.append) is a DAG -- an edge reached by two prefixes would share "
+                             "its noise between them; tree-shaped tries only")
+        K, S = int(slate_size), int(num_slates)
+        if K < 1 or K > self.SLATE_MAX_K:
+            raise ValueError(f"sample_slates(slate_size={slate_size}): 1 <= slate_size <= {self.SLATE_MAX_K}")
+        if S < 1:
+            raise ValueError(f"sample_slates(num_slates={num_slates}): at least one slate per user")
+        if K > int(self.wide_max_rows):
+            raise ValueError(f"sample_slates(slate_size={K}): one slate needs {K} decode rows, more than wide_max_rows = {self.wide_max_rows}; a slate "
+                             "cannot be split")
+        if getattr(trie, "item_edges", None) is None:
+            trie.index_items(trie.enumerate_items())
+        excl_np = None
+        if excluded_items is not None:
+            excl_np = self._excluded_items_bitmap(trie, excluded_items, input_ids.shape[0])
+        lib, dev = self._lib, self._be.device
+        q = self._sampling_setup(input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, slate_base, "slate_base")
+        tau, off, tok, nxt, input_ids, whole_word_ids, attention_mask = q.tau, q.off, q.tok, q.nxt, q.input_ids, q.whole_word_ids, q.attention_mask
+        B, L, T, streams_t, slate_base, seed, excl_t, excl_words, ftok, fnode, alive = (q.B, q.L, q.T, q.streams_t, q.base, q.seed, q.excl_t, q.excl_words,
+                                                                                        q.ftok, q.fnode, q.alive)
+        lane = self._cur_lane()
+        engine, sp = lane.engine, self._be.stream_ptr()
+        maxc = max(1, trie.max_children)
+        seq = torch.empty(B, S, K, T, dtype=torch.int32, device=dev)
+        lp = torch.empty(B, S, K, dtype=torch.float32, device=dev)
+        pert = torch.empty(B, S, K, dtype=torch.float32, device=dev)
+        tok_lp = torch.empty(B, S, K, T, dtype=torch.float32, device=dev)
+        ln = torch.empty(B, S, K, dtype=torch.int32, device=dev)
+        nA = int(alive.size)
+        if nA < B:
+            seq.fill_(self.config.pad_token_id)
+            seq[..., 0] = self.config.decoder_start_token_id
+            lp.fill_(-math.inf)
+            pert.fill_(-math.inf)
+            tok_lp.zero_()
+            ln.zero_()
+            alive_t = torch.from_numpy(alive).to(dev)
+        # at most `wide_max_rows` decode rows per engine call: users first, then slate ranges; a slate is never split
+        s_per = max(1, min(S, self.SLATE_MAX_K // K, int(self.wide_max_rows) // K))
+        u_per = max(1, int(self.wide_max_rows) // (s_per * K))
+        calls = 0
+        for s0 in range(0, S, s_per):
+            sc = min(s_per, S - s0)
+            for a in range(0, nA, u_per):
+                b = min(nA, a + u_per)
+                nb = b - a
+                whole = nb == B and sc == S
+                users = slice(a, b) if nA == B else alive_t[a:b]
+                cut = lambda t: None if t is None else (t if nb == B else t[users].contiguous())      # noqa: E731
+                o_seq = seq if whole else torch.empty(nb, sc, K, T, dtype=torch.int32, device=dev)
+                o_lp = lp if whole else torch.empty(nb, sc, K, dtype=torch.float32, device=dev)
+                o_pert = pert if whole else torch.empty(nb, sc, K, dtype=torch.float32, device=dev)
+                o_tok = tok_lp if whole else torch.empty(nb, sc, K, T, dtype=torch.float32, device=dev)
+                o_ln = ln if whole else torch.empty(nb, sc, K, dtype=torch.int32, device=dev)
+                if ftok:
+                    arr = (ctypes.c_int * len(ftok))
+                    self._be.check(lib.p5_generate_set_forced_prefix(engine, arr(*ftok), arr(*fnode), len(ftok)), "p5_generate_set_forced_prefix")
+                ws = self._lane_workspace(lane, lib.p5_sample_slates_workspace_bytes(engine, nb, L, sc, K, T, maxc, excl_words), "slates")
+                ids_c, ww_c, mask_c, ex_c, st_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(excl_t), cut(streams_t)
+                self._be.check(lib.p5_sample_slates(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, sc, K, T, _ptr(off), _ptr(tok), _ptr(nxt),
+                                                    _ptr(ex_c), excl_words, maxc, seed, _ptr(st_c), (slate_base + s0) & 0xFFFFFFFF, tau, _ptr(o_seq),
+                                                    _ptr(o_lp), _ptr(o_pert), _ptr(o_tok), _ptr(o_ln), _ptr(ws), ws.numel(), sp), "p5_sample_slates")
+                if not whole:
+                    seq[users, s0:s0 + sc], lp[users, s0:s0 + sc], pert[users, s0:s0 + sc] = o_seq, o_lp, o_pert
+                    tok_lp[users, s0:s0 + sc], ln[users, s0:s0 + sc] = o_tok, o_ln
+                calls += 1
+        with self._stats_lock:
+            st = self.slate_stats
+            st["calls"] += 1; st["users"] += B; st["engine_calls"] += calls; st["rows_per_call"] = min(nA, u_per) * s_per * K
+            st["forced_prefix_steps"] = len(ftok)
+        self.last_generate_path = "slates"
+        R = B * S * K
+        item_index = self._sampled_item_index(trie, seq.reshape(R, T), ln.reshape(R)).view(B, S, K)
+        return {"sequences": seq.reshape(R, T).to(torch.int64), "sequences_logprob": lp.reshape(R), "perturbed": pert,
+                "token_logprobs": tok_lp.reshape(R, T)[:, 1:].contiguous(), "item_index": item_index}
 
     def _in_user_chunks(self, fn, args):
         """fn(*args) for a search wider than the narrow step, over consecutive chunks of users of at most `wide_max_rows` decode rows each,
