@@ -15,6 +15,10 @@
  *   p5_generate           <- P5_T5.generate(..., prefix_allowed_tokens_fn, num_beams)  (DistributedRunner.py:361-371)
  *   p5_param_table        <- state_dict()/load_state_dict() key layout     (utils/utils.py:119-129)
  *
+ * and, without a counterpart in the reference, what its users build on top of it: exact catalogue ranking and candidate scoring
+ * (p5_rank_items, p5_cand_score, p5_prune_*, p5_bound_*), sampling under the item trie (p5_sample_items, p5_sample_slates) and the
+ * training loss of that sampled distribution (p5_train_set_item_loss: the next p5_forward / p5_forward_loss and its backward normalise
+ * every target position over the allowed children of the label prefix's trie node instead of the vocabulary),
  * plus per-kernel entry points (p5_op_*) used by the parity tests.
  *
  * Conventions: every pointer is a DEVICE pointer owned by the caller (torch's allocator); nothing is allocated,
@@ -104,6 +108,22 @@ int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
                     float* nll_out /* [B*T] */, float* loss_out /* [1] */, void* ws, int64_t ws_bytes, void* stream);
 /* stages: 0 = head + decoder-final, 1..n_dec = decoder layers (top first), then decoder embedding,
  * then encoder-final + encoder layers (top first), last = encoder embedding.  p5_backward runs them all. */
+/* ---- trie-normalised item loss: the training loss of the distribution p5_sample_items / p5_sample_slates draw from (openp5_amd/csrc/p5_trie_ce.h) ----
+ * One-shot: the NEXT p5_forward / p5_forward_loss on this engine, and the backward that follows it, replace the full-vocabulary cross-entropy by
+ *   nll[b, t] = log sum_{allowed children c of node(labels[b, :t])} exp(z_c / temperature) - z_label / temperature,
+ * z = the head's logits.  The trie is that of the samplers (CSR, DEVICE arrays, as p5_generate; the walk starts at the root's child whose
+ * token is the decoder start id); excluded_nodes (DEVICE uint32 [B, excluded_words], excluded_words * 32 >= n_nodes, or NULL) takes the same
+ * children out of the normalisation that the samplers never draw.  With the sampler's temperature and exclusion, nll is -out_tok_logprob of a
+ * draw and the backward its exact score function.  Row states (row_state_out: DEVICE int32 [B * T] or NULL; written by the forward):
+ *   0 scored; 1 past the end (behind </s>, at a node without children, at label -100 and behind it): nll = 0, no gradient;
+ *   2 off the trie (the label is no child of the node, or an excluded one; every later row of the sample too): nll = 0, no gradient.
+ * The forward takes the materialised-logits route (the head GEMM still runs over the whole vocabulary) and reads only the children's
+ * logits; the backward writes the dense dlogits [B * T, Vp] (zeros outside the allowed children), so the tied head's gradients, the staged
+ * backward, accumulation and data-parallel ranges are what they are for the plain loss, at the cost of the "ce_free" 0 route.  The workspace
+ * is p5_train_workspace_bytes, unchanged.  The next forward without a new call is the plain one again, bit for bit.  All arrays must stay
+ * valid until the backward has run. */
+int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes,
+                           const uint32_t* excluded_nodes, int excluded_words, float temperature, int* row_state_out);
 int p5_backward_num_stages(const P5Engine* e);
 int p5_backward_stage(P5Engine* e, const float* dnll, int stage, void* stream);
 int p5_backward(P5Engine* e, const float* dnll, void* stream);
@@ -508,6 +528,19 @@ int p5_op_ce_fwd_t(int dtype, float* nll, float* lse, const float* logits, const
  * grid_y = column slices per row (the engine: 1, 4 or 8 by row count).  g_out [rows] (may be NULL): the same g by p5_ce_gscale_kernel. */
 int p5_op_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const float* dnll, int rows,
                  int V, int ldl, int ldd, const int64_t* out_attn, int T, float gscale, int grid_y, float* g_out, void* stream);
+/* the kernels of the trie-normalised item loss (p5_trie_ce.h; see p5_train_set_item_loss), one by one:
+ * p5_op_trie_walk: labels int64 [B, T] -> node / state int32 [B * T] (node: whose children the row normalises over, -1 behind the end of the walk);
+ * p5_op_trie_ce_fwd: nll / lse fp32 [rows] from fp32 logits [rows, ldl] (rows = B * T; dtype selects the exponential as in p5_op_ce_fwd_t);
+ * p5_op_trie_ce_bwd: dlogits T [rows, ldd], zero outside the allowed children of scored rows, g * (exp(z - lse) - [child == label]) / temperature
+ *   there; g by p5_op_ce_bwd's two rules, 0 for rows that are not scored. */
+int p5_op_trie_walk(int* node, int* state, const int64_t* labels, const int* child_off, const int* child_tok, const int* child_node,
+                    const uint32_t* excluded, int excl_words, int B, int T, int start_id, int eos_id, void* stream);
+int p5_op_trie_ce_fwd(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
+                      const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
+                      int rows, int T, int ldl, void* stream);
+int p5_op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
+                      const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words,
+                      float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream);
 /* loss[0] = mean_b(sum_t nll[b, t] m[b, t] / max(sum_t m[b, t], 1)), m = (out_attn != 0) */
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];

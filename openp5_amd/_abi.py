@@ -46,6 +46,7 @@ PROTOTYPES = {
     "p5_train_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "p5_forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
     "p5_forward_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
+    "p5_train_set_item_loss": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp]),
     "p5_backward_num_stages": (i32, [vp]),
     "p5_backward_stage": (i32, [vp, vp, i32, vp]),
     "p5_backward": (i32, [vp, vp, vp]),
@@ -113,6 +114,9 @@ PROTOTYPES = {
     "p5_op_embed_bwd": (i32, [i32, i32, i32, i32, C.POINTER(P5EmbedBwdSet), vp, vp]),
     "p5_op_ce_fwd_t": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, vp]),
     "p5_op_ce_bwd": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, i32, vp, vp]),
+    "p5_op_trie_walk": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "p5_op_trie_ce_fwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, vp]),
+    "p5_op_trie_ce_bwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, f32, vp]),
     "p5_op_masked_mean": (i32, [vp, vp, vp, i32, i32, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),

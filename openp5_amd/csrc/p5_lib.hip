@@ -28,6 +28,7 @@
 #include "p5_bound.h"
 #include "p5_sample.h"
 #include "p5_sbs.h"
+#include "p5_trie_ce.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -144,6 +145,11 @@ struct P5Engine {
   float *logits = nullptr, *lse_tok = nullptr, *ssq_scratch = nullptr;
   float *ce_part = nullptr, *ce_lab = nullptr, *ce_g = nullptr;      // logit-free cross-entropy: per-row partial (max, sum exp) pairs, label logits, NLL gradients
   bool ce_free_fwd = false;       // the last training forward took the logit-free head (the backward recomputes the logits tile by tile)
+  // trie-normalised item loss (p5_trie_ce.h): il_next = p5_train_set_item_loss, armed for the NEXT forward (one-shot); il = what the last
+  // forward ran under, read by the backward that follows it.  The rows' trie nodes and states live in ce_lab / ce_g (Md x 4 bytes each),
+  // which only the logit-free route uses -- and an item-loss forward never takes it.
+  struct ItemLoss { bool on = false; P5TrieCe tr = {nullptr, nullptr, nullptr, nullptr, 0, 1.f}; int* state_out = nullptr; };
+  ItemLoss il_next, il;
   void* Sf = nullptr;              // folded bf16 weight copy W diag(ln) for q/k/v, wi, cross-attention q (same arena offsets; behind St)
   float *dres_a = nullptr, *dres_b = nullptr, *d_enc = nullptr, *Dvec = nullptr, *dres_cur = nullptr, *rel_partial = nullptr;
   void *dy = nullptr, *dn = nullptr, *dqkv = nullptr, *dO = nullptr, *dh = nullptr, *du = nullptr, *dlogits = nullptr, *dkv = nullptr;
@@ -1087,7 +1093,7 @@ static int decoder_fwd(P5Engine* e, hipStream_t s, float* nll_out = nullptr) {
   // tied head, d^-0.5 rescale folded into alpha (P5_T5.py:352-361)
   const float alpha = 1.0f / sqrtf((float)d);
   e->ce_free_fwd = false;
-  if (nll_out && ce_free<T>(e)) {
+  if (nll_out && !e->il.on && ce_free<T>(e)) {      // (the item loss reads the children's logits: materialised route)
     P5GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = e->dec_hn; g.B = Wc<T>(e, e->off_E); g.M = Md; g.N = c.vocab_size; g.K = d; g.lda = d; g.ldb = d;
@@ -1108,6 +1114,14 @@ static int forward_impl(P5Engine* e, float* nll_out, hipStream_t s) {
   P5_TRY(encoder_fwd<T>(e, s));
   P5_TRY(decoder_fwd<T>(e, s, nll_out));
   if (e->ce_free_fwd) return 0;       // (the head's epilogue + p5_ce_finish_kernel have written nll_out and the rows' log-sum-exp)
+  if (e->il.on) {
+    P5_LAUNCH(p5_trie_walk_kernel, dim3(e->B), dim3(256), 0, s, (int*)e->ce_lab, (int*)e->ce_g, e->il.state_out, e->labels, e->il.tr, e->T, e->c.pad_id,
+              e->c.eos_id);
+    P5_TRY(P5_KCHECK());
+    P5_LAUNCH((p5_trie_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, (const float*)e->logits, e->labels, (const int*)e->ce_lab,
+              (const int*)e->ce_g, e->il.tr, e->T, e->Vp);
+    return P5_KCHECK();
+  }
   P5_LAUNCH((p5_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, (const float*)e->logits, e->labels, e->c.vocab_size, e->Vp);
   return P5_KCHECK();
 }
@@ -1336,6 +1350,10 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       g.epi = P5_EPI_CE_GRAD; g.alpha = alpha; g.drop = no_drop();
       g.ce_labels = e->labels; g.ce_lse = e->lse_tok; g.ce_g = e->ce_g; g.ce_np = (c.vocab_size + 63) / 64;
       P5_TRY(launch_gemm<T>(g, s));
+    } else if (e->il.on) {
+      P5_LAUNCH((p5_trie_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok, e->labels,
+                (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, e->Vp, e->Vp, e->out_attn, e->T, 1.0f / (float)e->B);
+      P5_TRY(P5_KCHECK());
     } else {
       P5_LAUNCH((p5_ce_bwd_kernel<T>), dim3(Md, Md >= 2048 ? 1 : (Md >= 512 ? 4 : 8)), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok,
                 e->labels, dnll, c.vocab_size, e->Vp, e->Vp, e->out_attn, e->T, 1.0f / (float)e->B);
@@ -3566,6 +3584,9 @@ int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_
   e->Vp = (e->c.vocab_size + 63) / 64 * 64;
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = labels; e->out_attn = nullptr;
   if (training && e->c.dropout > 0.f) P5_REQUIRE(e->rng, "training with dropout needs rng_state");
+  e->il = e->il_next;            // one-shot: this forward and the backward behind it
+  e->il_next.on = false;
+  if (e->il.on) P5_REQUIRE(nll_out, "item loss: nll_out");
   return e->c.dtype == 1 ? forward_impl<bf16>(e, nll_out, (hipStream_t)stream) : forward_impl<float>(e, nll_out, (hipStream_t)stream);
 }
 int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
@@ -3576,6 +3597,18 @@ int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
   e->out_attn = output_attention;
   P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, (const float*)nll_out, output_attention, B, T);
   return P5_KCHECK();
+}
+int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes, const uint32_t* excluded_nodes,
+                           int excluded_words, float temperature, int* row_state_out) {
+  e->il_next.on = false;
+  P5_REQUIRE(child_off && child_tok && child_node && n_nodes >= 1, "item loss: trie (child_off / child_tok / child_node, n_nodes >= 1)");
+  P5_REQUIRE(temperature > 0.f && temperature < __builtin_huge_valf(), "item loss: temperature > 0");
+  P5_REQUIRE(excluded_words >= 0 && (excluded_nodes || excluded_words == 0), "item loss: excluded_nodes / excluded_words");
+  P5_REQUIRE(!excluded_nodes || (int64_t)excluded_words * 32 >= n_nodes, "item loss: the excluded-node bitmap is shorter than the trie");
+  e->il_next.tr = P5TrieCe{child_off, child_tok, child_node, excluded_words > 0 ? excluded_nodes : nullptr, excluded_words, temperature};
+  e->il_next.state_out = row_state_out;
+  e->il_next.on = true;
+  return 0;
 }
 int p5_backward_num_stages(const P5Engine* e) { return e->c.n_dec_layers + e->c.n_enc_layers + 4; }
 int p5_backward_stage(P5Engine* e, const float* dnll, int stage, void* stream) {
@@ -4386,6 +4419,44 @@ int p5_op_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse
   }
   if (dtype == 1) P5_LAUNCH((p5_ce_bwd_kernel<bf16>), dim3(rows, grid_y), dim3(256), 0, s, (bf16*)dlogits, logits, lse, labels, dnll, V, ldl, ldd, out_attn, T, gscale);
   else P5_LAUNCH((p5_ce_bwd_kernel<float>), dim3(rows, grid_y), dim3(256), 0, s, (float*)dlogits, logits, lse, labels, dnll, V, ldl, ldd, out_attn, T, gscale);
+  return P5_KCHECK();
+}
+static int trie_ce_args(P5TrieCe* tr, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float tau) {
+  P5_REQUIRE(child_off && child_tok && child_node, "trie_ce: trie");
+  P5_REQUIRE(tau > 0.f && tau < __builtin_huge_valf(), "trie_ce: temperature > 0");
+  P5_REQUIRE(excl_words >= 0 && (excluded || excl_words == 0), "trie_ce: excluded / excl_words");
+  *tr = P5TrieCe{child_off, child_tok, child_node, excl_words > 0 ? excluded : nullptr, excl_words, tau};
+  return 0;
+}
+int p5_op_trie_walk(int* node, int* state, const int64_t* labels, const int* child_off, const int* child_tok, const int* child_node,
+                    const uint32_t* excluded, int excl_words, int B, int T, int start_id, int eos_id, void* stream) {
+  P5_REQUIRE(node && state && labels && B >= 1 && T >= 1, "trie_walk: arguments");
+  P5TrieCe tr;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, 1.f));
+  P5_LAUNCH(p5_trie_walk_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, node, state, (int*)nullptr, labels, tr, T, start_id, eos_id);
+  return P5_KCHECK();
+}
+int p5_op_trie_ce_fwd(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
+                      const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
+                      int rows, int T, int ldl, void* stream) {
+  P5_REQUIRE(nll && lse && logits && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0 && ldl >= 1, "trie_ce_fwd: arguments");
+  P5TrieCe tr;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  if (dtype == 1) P5_LAUNCH((p5_trie_ce_fwd_kernel<bf16>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, node, state, tr, T, ldl);
+  else P5_LAUNCH((p5_trie_ce_fwd_kernel<float>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, node, state, tr, T, ldl);
+  return P5_KCHECK();
+}
+int p5_op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
+                      const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words,
+                      float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(dlogits && logits && lse && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0, "trie_ce_bwd: arguments");
+  P5_REQUIRE(ldl >= 1 && ldd >= 1 && ldd % 8 == 0, "trie_ce_bwd: ldd a multiple of 8");
+  P5_REQUIRE(dnll || out_attn, "trie_ce_bwd: dnll, or out_attn [rows / T, T]");
+  P5TrieCe tr;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  if (dtype == 1) P5_LAUNCH((p5_trie_ce_bwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, (bf16*)dlogits, logits, lse, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
+  else P5_LAUNCH((p5_trie_ce_bwd_kernel<float>), dim3(rows), dim3(256), 0, s, (float*)dlogits, logits, lse, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   return P5_KCHECK();
 }
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream) {

@@ -110,14 +110,15 @@ class _P5LossFn(torch.autograd.Function):
     writing straight into the gradient arena."""
 
     @staticmethod
-    def forward(ctx, anchor, model, input_ids, whole_word_ids, attention_mask, labels):
+    def forward(ctx, anchor, model, input_ids, whole_word_ids, attention_mask, labels, item_loss=None):
         ctx.model = model
-        return model._engine_forward(input_ids, whole_word_ids, attention_mask, labels)
+        ctx.item_loss = item_loss       # (the engine keeps the setting of its last forward for the backward; this keeps the device arrays alive)
+        return model._engine_forward(input_ids, whole_word_ids, attention_mask, labels, item_loss)
 
     @staticmethod
     def backward(ctx, dnll):
         ctx.model._engine_backward(dnll)
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None
 
 
 class _GenLane:
@@ -193,6 +194,7 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
+        self.last_item_loss_state = None    # int32 [B, T] device tensor of the last item-loss forward (forward(trie=...)): 0 scored, 1 past the end, 2 off the trie
         self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("sample": sample_items() / generate(do_sample=True); "slates": sample_slates(); "rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
                            "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0,
@@ -508,7 +510,40 @@ class P5T5Native(nn.Module):
     def _i64(t, device):
         return t.to(device=device, dtype=torch.int64).contiguous()
 
-    def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels):
+    def _item_loss_setup(self, trie, temperature, excluded_items, B):
+        """The checked setting of the trie-normalised item loss (csrc/p5_trie_ce.h) for a batch of B users: the trie on the device, the
+        temperature (the check of `_sampling_setup`) and the excluded-node bitmap (the rule of `sample_items`)."""
+        dev = self._be.device
+        tau = float(temperature)
+        if not (tau > 0.0 and math.isfinite(tau)):
+            raise ValueError(f"temperature={temperature!r}: a finite value > 0")
+        trie = self._compiled_trie(trie)
+        start = int(self.config.decoder_start_token_id)
+        lo, hi = int(trie.child_off[0]), int(trie.child_off[1])
+        if trie.n_nodes < 1 or start not in [int(t) for t in trie.child_tok[lo:hi]]:
+            raise ValueError(f"item loss: the trie has no edge for the decoder start token ({start}) at its root")
+        if trie.child_tok.size and int(trie.child_tok.max()) >= self.config.vocab_size:
+            raise ValueError(f"item loss: the trie holds token {int(trie.child_tok.max())}, the vocabulary has {self.config.vocab_size}")
+        excl_t, excl_words = None, 0
+        if excluded_items is not None:
+            if trie.grafted:
+                raise ValueError("item loss (excluded_items=...): a trie with an appended trie (Trie.append) cannot be indexed")
+            if getattr(trie, "item_edges", None) is None:
+                trie.index_items(trie.enumerate_items())
+            excl_np = self._excluded_items_bitmap(trie, excluded_items, B)
+            excl_words = int(excl_np.shape[1])
+            excl_t = torch.from_numpy(np.ascontiguousarray(excl_np).view(np.int32)).to(dev)
+        off, tok, nxt = trie.device_arrays(dev)
+        return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, n_nodes=int(trie.n_nodes), excl_t=excl_t, excl_words=excl_words)
+
+    def _arm_item_loss(self, q, B, T):
+        """p5_train_set_item_loss for the engine's next forward; the rows' states land in `last_item_loss_state` (no host sync)."""
+        state = torch.empty(B, T, dtype=torch.int32, device=self._be.device)
+        self._be.check(self._lib.p5_train_set_item_loss(self._engine, _ptr(q.off), _ptr(q.tok), _ptr(q.nxt), q.n_nodes, _ptr(q.excl_t), q.excl_words,
+                                                        q.tau, _ptr(state)), "p5_train_set_item_loss")
+        self.last_item_loss_state = state
+
+    def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels, item_loss=None):
         dev = self._be.device
         B, L = input_ids.shape
         T = labels.shape[1]
@@ -519,7 +554,9 @@ class P5T5Native(nn.Module):
         training = 1 if (self.training and self.config.dropout_rate > 0) else 0
         if training:
             self._advance_dropout_step()
-        self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels)   # keep device buffers alive
+        self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, item_loss)   # keep device buffers alive
+        if item_loss is not None:
+            self._arm_item_loss(item_loss, B, T)
         self._be.check(self._lib.p5_forward(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels), B, L, T,
                                             training, _ptr(nll), _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward")
         return nll
@@ -606,11 +643,12 @@ class P5T5Native(nn.Module):
             ev1.record()
             self.ddp_wait_ms.append((ev0, ev1))     # (read by bench.py after a synchronize: main-stream time spent waiting for the buckets)
 
-    def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention):
+    def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
-        none of the ~10 elementwise launches of the generic path.  Returns the loss as a 0-dim tensor; gradients are in `.grad`."""
+        none of the ~10 elementwise launches of the generic path.  Returns the loss as a 0-dim tensor; gradients are in `.grad`.
+        `trie`, `temperature`, `excluded_items`: the trie-normalised item loss, as in `forward` (the masked mean then runs over its NLL)."""
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
         B, L = input_ids.shape
@@ -619,6 +657,7 @@ class P5T5Native(nn.Module):
         labels = self._i64(labels, dev)
         output_attention = self._i64(output_attention, dev)
         T = labels.shape[1]
+        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B)
         self._sync_shadow()
         self._sync_transposed()
         ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
@@ -626,7 +665,9 @@ class P5T5Native(nn.Module):
         training = 1 if (self.training and self.config.dropout_rate > 0) else 0
         if training:
             self._advance_dropout_step()
-        self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, output_attention)
+        self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, output_attention, item_loss)
+        if item_loss is not None:
+            self._arm_item_loss(item_loss, B, T)
         self._be.check(self._lib.p5_forward_loss(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels),
                                                  _ptr(output_attention), B, L, T, training, _ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * B * T),
                                                  _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward_loss")
@@ -637,9 +678,19 @@ class P5T5Native(nn.Module):
         self._rng_cpu[1] = (self._rng_cpu[1] + 1) & 0xFFFFFFFF
         self._rng[1] = self._rng_cpu[1] if self._rng_cpu[1] < 2 ** 31 else self._rng_cpu[1] - 2 ** 32
 
-    def forward(self, input_ids=None, whole_word_ids=None, attention_mask=None, labels=None, alpha=None, return_dict=True, **unused):
+    def forward(self, input_ids=None, whole_word_ids=None, attention_mask=None, labels=None, alpha=None, return_dict=True, trie=None,
+                temperature=1.0, excluded_items=None, **unused):
         """P5_T5.forward (P5_T5.py:275-386): returns {"loss": flat [B*T] per-token NLL}; `alpha` is accepted and ignored
-        exactly as in the reference (P5_T5.py:294)."""
+        exactly as in the reference (P5_T5.py:294).
+        `trie` (Trie / CompiledTrie; None = the full-vocabulary cross-entropy, unchanged): the trie-normalised item loss (csrc/p5_trie_ce.h),
+        the NLL of the distribution `sample_items` / `sample_slates` draw from -- at every position softmax(logits / `temperature`)
+        renormalised over the allowed children of the trie node behind labels[b, :t]; `excluded_items` (per-user lists of item indices, as
+        for `sample_items`; not for a trie with an appended trie) are taken out of the normalisation.  With the sampler's trie, temperature
+        and exclusion, forward(labels=drawn[:, 1:]) returns -token_logprobs of the draw and its backward is the score function of what was
+        drawn.  Positions behind </s>, at label -100 and behind it, and every position from the first label that is not an allowed child
+        on, have NLL 0 and no gradient; `last_item_loss_state` (int32 [B, T] on the device, no host sync) says which: 0 scored, 1 past the
+        end, 2 off the trie.  The head still runs over the whole vocabulary and the logits gradient is dense, so gradient accumulation
+        (`begin_micro_batch`), DDP and the staged backward work as for the plain loss, unchanged."""
         if labels is None:
             raise ValueError("P5T5Native.forward needs labels (the runner always passes them)")
         dev = self._be.device
@@ -651,7 +702,8 @@ class P5T5Native(nn.Module):
             attention_mask = (input_ids != self.config.pad_token_id).long()
         attention_mask = self._i64(attention_mask, dev)
         labels = self._i64(labels, dev)
-        nll = _P5LossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels)
+        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0])
+        nll = _P5LossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels, item_loss)
         out = {"loss": nll}
         return out if return_dict else (nll,)
 

@@ -70,6 +70,11 @@ def parse_runner_args(parser):
     parser.add_argument("--compute_dtype", type=str, default="bf16", help="bf16 (fast) or fp32 (parity) engine arithmetic")
     parser.add_argument("--ddp_bucket_dtype", type=str, default="fp32", help="fp32 | bf16: dtype of the gradient buckets the ranks exchange "
                         "(bf16 halves the bytes on the xGMI links; the sums are identical on every rank either way).")
+    parser.add_argument("--train_item_loss", type=int, default=0, choices=[0, 1], help="1 = train (and validate) on the trie-normalised item loss: "
+                        "at every target position the softmax is renormalised over the continuations that are items (one union trie over the "
+                        "items of all training datasets), the likelihood of the distribution P5T5Native.sample_items / sample_slates draw from.  "
+                        "0 = the full-vocabulary cross-entropy, untouched.")
+    parser.add_argument("--item_loss_temperature", type=float, default=1.0, help="temperature of --train_item_loss 1 (logits / temperature)")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -99,7 +104,7 @@ def masked_mean_loss(nll, output_attention):
     return (loss.sum(dim=1) / m.sum(dim=1).clamp(min=1)).mean()
 
 
-def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1):
+def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=None):
     """One pass of the reference loop body (DistributedRunner.py:63-87): forward, masked-mean loss, backward, clip + AdamW +
     scheduler (fused), zero_grad.  `batch` = (input_ids, whole_word_ids, attention_mask, labels, output_attention) on the
     device.  With the native model the loss and its gradient seed are computed by the engine
@@ -110,16 +115,20 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1):
     to the arena (every gradient kernel accumulates; the arena clear at the start of a backward is skipped), ranks exchange
     gradients on the LAST micro-batch only, and the optimizer steps once per group on the group mean (1/accum folded into the
     AdamW gradient scale).  The reference only divides total_steps by this flag and still steps every batch
-    (SingleRunner.py:182), which drives its schedule to lr = 0 after 1/accum of the run; this is the intended behaviour."""
+    (SingleRunner.py:182), which drives its schedule to lr = 0 after 1/accum of the run; this is the intended behaviour.
+
+    `item_loss` (None = the full-vocabulary cross-entropy): keyword arguments of the native model's trie-normalised item loss --
+    {"trie": ..., "temperature": ...} (`P5T5Native.forward`)."""
+    kw = item_loss or {}
     input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
     fused = getattr(model, "loss_and_backward", None)
     last = micro == accum - 1
     if fused is not None and hasattr(model, "begin_micro_batch"):
         model.begin_micro_batch(first=micro == 0, sync=last)
     if fused is not None:
-        loss = fused(input_ids, whole_ids, attn, output_ids, output_attention)
+        loss = fused(input_ids, whole_ids, attn, output_ids, output_attention, **kw)
     else:
-        out = model(input_ids=input_ids, whole_word_ids=whole_ids, attention_mask=attn, labels=output_ids, alpha=alpha, return_dict=True)
+        out = model(input_ids=input_ids, whole_word_ids=whole_ids, attention_mask=attn, labels=output_ids, alpha=alpha, return_dict=True, **kw)
         loss = masked_mean_loss(out["loss"], output_attention)
         (loss / accum if accum > 1 else loss).backward()
     if last:
@@ -346,7 +355,7 @@ class DistributedRunner:
                 gsize = min(accum, n_total - g0)
                 micro = n_batches - 1 - g0
                 loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
-                                     micro=micro, accum=gsize)
+                                     micro=micro, accum=gsize, item_loss=self._item_loss_kw())
                 losses.append(loss)
                 n_samples += input_ids.shape[0]
                 if resume and save_steps > 0 and micro == gsize - 1 and self.optimizer.t % save_steps == 0:
@@ -394,6 +403,22 @@ class DistributedRunner:
                 logging.info(f"Save the current model to {self.args.model_path}")
         return train_losses
 
+    def _item_loss_kw(self):
+        """--train_item_loss 1: the keyword arguments of the trie-normalised item loss -- ONE union trie over the items of all training
+        datasets (item ids carry their dataset's name, so the union is a tree), built once; None with the flag at 0."""
+        if not int(getattr(self.args, "train_item_loss", 0)):
+            return None
+        kw = self.__dict__.get("_item_loss")
+        if kw is None:
+            loader = self.train_loader if self.train_loader is not None else self.valid_loader
+            seqs, seen = [], set()
+            for ds in loader.dataset.datasets:
+                if ds.dataset not in seen:
+                    seen.add(ds.dataset)
+                    seqs += self._item_sequences(ds, list(ds.all_items))
+            kw = self._item_loss = {"trie": CompiledTrie.from_trie(Trie(seqs)), "temperature": float(getattr(self.args, "item_loss_temperature", 1.0))}
+        return kw
+
     @torch.no_grad()
     def validate(self):
         self.model.eval()
@@ -404,7 +429,7 @@ class DistributedRunner:
         for batch in self.valid_loader:
             input_ids, attn, whole_ids, output_ids, output_attention = self._to_dev(batch)[:5]
             out = self.model(input_ids=input_ids, whole_word_ids=whole_ids, attention_mask=attn, labels=output_ids,
-                             alpha=self.args.alpha, return_dict=True)
+                             alpha=self.args.alpha, return_dict=True, **(self._item_loss_kw() or {}))
             losses.append(masked_mean_loss(out["loss"], output_attention))
         v = torch.stack(losses).mean()
         if self.world > 1:
