@@ -124,6 +124,18 @@ int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
  * valid until the backward has run. */
 int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes,
                            const uint32_t* excluded_nodes, int excluded_words, float temperature, int* row_state_out);
+/* The same under top-k / nucleus truncation (openp5_amd/csrc/p5_trunc.h; the semantics are stated at p5_sample_items_truncated): per
+ * row the normalisation runs over the KEPT children only, nll = lse_kept - z_label / temperature, and the backward writes gradients only
+ * there (the kept set is a constant of the gradient, as under HF's masked_fill).  With the sampler's top_k / top_p, nll is -out_tok_logprob
+ * of a truncated draw.  A label that is allowed but below the row's cut is row state
+ *   3 truncated away: nll = 0 and no gradient FOR THAT ROW ONLY (the walk knows nothing of logits: later rows are scored as usual).
+ * row_cut (DEVICE fp32 [B * T], required): the forward writes every row's cut (min z over the kept set; +inf for rows that are not
+ * scored), the backward reads it; it must stay valid until the backward has run.  top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off); with
+ * both off the plain item-loss kernels run, bit for bit, and row_cut is not written.  One-shot like its sibling; p5_train_workspace_bytes
+ * is unchanged. */
+int p5_train_set_item_loss_truncated(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes,
+                                     const uint32_t* excluded_nodes, int excluded_words, float temperature, int* row_state_out, int top_k,
+                                     float top_p, float* row_cut /* DEVICE [B*T] */);
 int p5_backward_num_stages(const P5Engine* e);
 int p5_backward_stage(P5Engine* e, const float* dnll, int stage, void* stream);
 int p5_backward(P5Engine* e, const float* dnll, void* stream);
@@ -234,6 +246,27 @@ int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
                     int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
                     int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids /* device uint32 [B] */, uint32_t draw_base,
                     float temperature, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream);
+/* ---- p5_sample_items under top-k / nucleus truncation (openp5_amd/csrc/p5_trunc.h) ----
+ * HF's order (processors, temperature, TopKLogitsWarper, TopPLogitsWarper, softmax) restated on the allowed children.  For a row at node n:
+ * A = the children that are not excluded and have a finite logit, z_i = logit_i / temperature.
+ *   top_k >= 1 (0 = off): K1 = { i in A : z_i >= the k-th largest z of A }; ties at the k-th value all stay; |A| <= k: K1 = A.
+ *   0 < top_p <= 1 (1 = off), on softmax over K1: child i stays iff mass{ j in K1 : z_j > z_i } < top_p * mass(K1).  By VALUE: children
+ *     with equal z stay or leave together (HF cuts inside such a group by sort position -- the one deviation), so the result does not
+ *     depend on the order of the children.  The largest value always stays.
+ * The step's distribution is softmax(z) over the kept set { i in A : z_i >= cut }; out_tok_logprob holds log-probabilities under it, exactly
+ * 0 where one child is kept (top_k = 1 is the greedy descent).  The uniform of a child is the function of (seed, stream, draw, step,
+ * child position) p5_sample_items uses: truncation never changes a child's noise, so a draw whose untruncated path stays inside the kept
+ * sets is the same draw.  The cut is a pure function of the row's values (integer radix select for top-k; for top-p a bisection over
+ * sums taken in one fixed order): two calls return the same bits.  Off = top_k in {0, >= max_children} and top_p = 1: the kernels of
+ * p5_sample_items run and every output is its output, bit for bit.
+ * The workspace (exact; -1 outside the limits of p5_sample_items): p5_sample_workspace_bytes plus the step's [B * S, max_children] fp32
+ * scratch (rounded up to 256 bytes). */
+int64_t p5_sample_truncated_workspace_bytes(const P5Engine* e, int B, int L, int S, int max_len, int max_children, int excluded_words);
+int p5_sample_items_truncated(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L,
+                              int S, int max_len, const int* child_off, const int* child_tok, const int* child_node,
+                              const uint32_t* excluded_nodes, int excluded_words, int max_children, uint32_t seed,
+                              const uint32_t* stream_ids /* device uint32 [B] */, uint32_t draw_base, float temperature, int top_k, float top_p,
+                              int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream);
 /* ---- stochastic beam search: S slates of K DISTINCT items per user, a sample without replacement (openp5_amd/csrc/p5_sbs.h) ----
  * The distribution is that of p5_sample_items.  A slate is the K items with the largest G(item) = log p(item) + Gumbel noise, largest first:
  * a sample without replacement in sequential-sampling (Plackett-Luce) order (Kool, van Hoof, Welling 2019), computed top-down over the trie
@@ -541,6 +574,21 @@ int p5_op_trie_ce_fwd(int dtype, float* nll, float* lse, const float* logits, co
 int p5_op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
                       const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words,
                       float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream);
+/* the kernels of the truncated item loss (p5_trunc.h; see p5_train_set_item_loss_truncated), one by one:
+ * p5_op_trunc_cut: fp32 logits [rows, ldl], node int32 [rows] (< 0: no node) -> cut fp32 [rows] (min z over the kept set, +inf where nothing is
+ *   kept) and kept int32 [rows] (size of the kept set); rows_per_user consecutive rows share a row of the excluded bitmap;
+ * p5_op_trunc_ce_fwd: p5_op_trie_ce_fwd over the kept set, plus row_cut fp32 [rows]; state int32 [rows] is read (the walk's) AND written (3
+ *   where the label lies below the cut);
+ * p5_op_trunc_ce_bwd: p5_op_trie_ce_bwd with entries only where z >= row_cut[row]. */
+int p5_op_trunc_cut(float* cut, int* kept, const float* logits, const int* node, const int* child_off, const int* child_tok, const int* child_node,
+                    const uint32_t* excluded, int excl_words, float temperature, int top_k, float top_p, int rows, int rows_per_user, int ldl,
+                    void* stream);
+int p5_op_trunc_ce_fwd(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
+                       const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
+                       int top_k, float top_p, int rows, int T, int ldl, void* stream);
+int p5_op_trunc_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
+                       const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded,
+                       int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream);
 /* loss[0] = mean_b(sum_t nll[b, t] m[b, t] / max(sum_t m[b, t], 1)), m = (out_attn != 0) */
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];

@@ -47,6 +47,7 @@ PROTOTYPES = {
     "p5_forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
     "p5_forward_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
     "p5_train_set_item_loss": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp]),
+    "p5_train_set_item_loss_truncated": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp, i32, f32, vp]),
     "p5_backward_num_stages": (i32, [vp]),
     "p5_backward_stage": (i32, [vp, vp, i32, vp]),
     "p5_backward": (i32, [vp, vp, vp]),
@@ -68,6 +69,9 @@ PROTOTYPES = {
     "p5_generate_set_forced_prefix": (i32, [vp, vp, vp, i32]),
     "p5_sample_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32, i32]),
     "p5_sample_items": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, u32, vp, u32, f32, vp, vp, vp, vp, vp, i64, vp]),
+    "p5_sample_truncated_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32, i32]),
+    "p5_sample_items_truncated": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, u32, vp, u32, f32, i32, f32, vp, vp, vp, vp, vp, i64,
+                                        vp]),
     "p5_sample_slates_workspace_bytes": (i64, [vp, i32, i32, i32, i32, i32, i32, i32]),
     "p5_sample_slates": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, u32, vp, u32, f32, vp, vp, vp, vp, vp, vp, i64, vp]),
     "p5_generate_history_count": (i64, [i32, i32, i32]),
@@ -117,6 +121,9 @@ PROTOTYPES = {
     "p5_op_trie_walk": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "p5_op_trie_ce_fwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, vp]),
     "p5_op_trie_ce_bwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, f32, vp]),
+    "p5_op_trunc_cut": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, f32, i32, i32, i32, vp]),
+    "p5_op_trunc_ce_fwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, f32, i32, i32, i32, vp]),
+    "p5_op_trunc_ce_bwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, f32, vp]),
     "p5_op_masked_mean": (i32, [vp, vp, vp, i32, i32, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),

@@ -29,6 +29,7 @@
 #include "p5_sample.h"
 #include "p5_sbs.h"
 #include "p5_trie_ce.h"
+#include "p5_trunc.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -148,7 +149,12 @@ struct P5Engine {
   // trie-normalised item loss (p5_trie_ce.h): il_next = p5_train_set_item_loss, armed for the NEXT forward (one-shot); il = what the last
   // forward ran under, read by the backward that follows it.  The rows' trie nodes and states live in ce_lab / ce_g (Md x 4 bytes each),
   // which only the logit-free route uses -- and an item-loss forward never takes it.
-  struct ItemLoss { bool on = false; P5TrieCe tr = {nullptr, nullptr, nullptr, nullptr, 0, 1.f}; int* state_out = nullptr; };
+  // trunc: the truncated twins of p5_trunc.h (p5_train_set_item_loss_truncated); row_cut is the caller's [B * T] fp32 device array, written
+  // by the forward and read by the backward
+  struct ItemLoss {
+    bool on = false; P5TrieCe tr = {nullptr, nullptr, nullptr, nullptr, 0, 1.f}; int* state_out = nullptr;
+    bool trunc = false; P5TruncCe tc = {0, 1.f}; float* row_cut = nullptr;
+  };
   ItemLoss il_next, il;
   void* Sf = nullptr;              // folded bf16 weight copy W diag(ln) for q/k/v, wi, cross-attention q (same arena offsets; behind St)
   float *dres_a = nullptr, *dres_b = nullptr, *d_enc = nullptr, *Dvec = nullptr, *dres_cur = nullptr, *rel_partial = nullptr;
@@ -1118,6 +1124,11 @@ static int forward_impl(P5Engine* e, float* nll_out, hipStream_t s) {
     P5_LAUNCH(p5_trie_walk_kernel, dim3(e->B), dim3(256), 0, s, (int*)e->ce_lab, (int*)e->ce_g, e->il.state_out, e->labels, e->il.tr, e->T, e->c.pad_id,
               e->c.eos_id);
     P5_TRY(P5_KCHECK());
+    if (e->il.trunc) {
+      P5_LAUNCH((p5_trunc_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, e->il.row_cut, (int*)e->ce_g, e->il.state_out,
+                (const float*)e->logits, e->labels, (const int*)e->ce_lab, e->il.tr, e->il.tc, e->T, e->Vp);
+      return P5_KCHECK();
+    }
     P5_LAUNCH((p5_trie_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, (const float*)e->logits, e->labels, (const int*)e->ce_lab,
               (const int*)e->ce_g, e->il.tr, e->T, e->Vp);
     return P5_KCHECK();
@@ -1350,6 +1361,11 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       g.epi = P5_EPI_CE_GRAD; g.alpha = alpha; g.drop = no_drop();
       g.ce_labels = e->labels; g.ce_lse = e->lse_tok; g.ce_g = e->ce_g; g.ce_np = (c.vocab_size + 63) / 64;
       P5_TRY(launch_gemm<T>(g, s));
+    } else if (e->il.on && e->il.trunc) {
+      P5_LAUNCH((p5_trunc_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok,
+                (const float*)e->il.row_cut, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, e->Vp, e->Vp, e->out_attn, e->T,
+                1.0f / (float)e->B);
+      P5_TRY(P5_KCHECK());
     } else if (e->il.on) {
       P5_LAUNCH((p5_trie_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok, e->labels,
                 (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, e->Vp, e->Vp, e->out_attn, e->T, 1.0f / (float)e->B);
@@ -2097,12 +2113,14 @@ static int64_t layout_sample(P5Engine* e, char* base, int B, int L, int S, int m
 template <class T>
 static int sample_items_impl(P5Engine* e, int B, int L, int S, int max_len, const int* child_off, const int* child_tok, const int* child_node,
                              const uint32_t* excluded, int excl_words, int max_c, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base,
-                             float tau, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, char* ws, hipStream_t s) {
+                             float tau, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, char* ws, hipStream_t s,
+                             bool trunc = false, int top_k = 0, float top_p = 1.f) {
   const P5Config& c = e->c;
   const int d = c.d_model, R = B * S;
   GenWs w;
   P5SampleState st;
-  layout_sample(e, ws, B, L, S, max_len, &w, &st);
+  // (truncated: the [R, max_c] fp32 scratch of p5_trunc_sample_step_kernel lies behind the sampler's workspace)
+  float* zs = (float*)(ws + layout_sample(e, ws, B, L, S, max_len, &w, &st));
   e->gen.active = false;              // (a search begun on this engine shared the encoder buffers: it cannot be continued)
   e->gen_hist_next = nullptr;
   if (!excluded) excl_words = 0;
@@ -2123,7 +2141,8 @@ static int sample_items_impl(P5Engine* e, int B, int L, int S, int max_len, cons
   for (int cur_len = F + 1; cur_len < max_len; ++cur_len) {
     P5_TRY(decode_step2<T>(e, w, B, L, S, max_len, s, (const int*)(st.steps + cur_len), false));
     a.cur_len = cur_len;
-    P5_LAUNCH((p5_sample_step_kernel<T>), dim3(R), dim3(256), 0, s, st, a);
+    if (trunc) P5_LAUNCH((p5_trunc_sample_step_kernel<T>), dim3(R), dim3(256), 0, s, st, a, zs, top_k, top_p);
+    else P5_LAUNCH((p5_sample_step_kernel<T>), dim3(R), dim3(256), 0, s, st, a);
     P5_TRY(P5_KCHECK());
   }
   P5_LAUNCH(p5_sample_finish_kernel, dim3((R * max_len + 255) / 256), dim3(256), 0, s, out_seq, out_logprob, out_tok_logprob, out_len, st, R, max_len);
@@ -3607,7 +3626,21 @@ int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_t
   P5_REQUIRE(!excluded_nodes || (int64_t)excluded_words * 32 >= n_nodes, "item loss: the excluded-node bitmap is shorter than the trie");
   e->il_next.tr = P5TrieCe{child_off, child_tok, child_node, excluded_words > 0 ? excluded_nodes : nullptr, excluded_words, temperature};
   e->il_next.state_out = row_state_out;
+  e->il_next.trunc = false;
   e->il_next.on = true;
+  return 0;
+}
+int p5_train_set_item_loss_truncated(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes,
+                                     const uint32_t* excluded_nodes, int excluded_words, float temperature, int* row_state_out, int top_k, float top_p,
+                                     float* row_cut) {
+  e->il_next.on = false;
+  P5_REQUIRE(top_k >= 0, "item loss: top_k >= 0 (0 = off)");
+  P5_REQUIRE(top_p > 0.f && top_p <= 1.f, "item loss: 0 < top_p <= 1 (1 = off)");
+  P5_REQUIRE(row_cut, "item loss: row_cut (device, one fp32 per decoder row)");
+  P5_TRY(p5_train_set_item_loss(e, child_off, child_tok, child_node, n_nodes, excluded_nodes, excluded_words, temperature, row_state_out));
+  e->il_next.trunc = top_k > 0 || top_p < 1.f;          // (off: the plain kernels, bit for bit; row_cut is not written then)
+  e->il_next.tc = P5TruncCe{top_k, top_p};
+  e->il_next.row_cut = row_cut;
   return 0;
 }
 int p5_backward_num_stages(const P5Engine* e) { return e->c.n_dec_layers + e->c.n_enc_layers + 4; }
@@ -3890,10 +3923,15 @@ int64_t p5_sample_workspace_bytes(const P5Engine* e, int B, int L, int S, int ma
   P5Engine tmp = *e;
   return layout_sample(&tmp, nullptr, B, L, S, max_len, nullptr, nullptr);
 }
-int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S,
-                    int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
-                    int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base, float temperature,
-                    int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream) {
+// the scratch of the truncated step behind the sampler's workspace: [R, max_children] fp32
+static int64_t trunc_scratch_bytes(int B, int S, int max_children) {
+  return (int64_t)(((size_t)B * S * max_children * 4 + 255) & ~(size_t)255);
+}
+static int sample_items_checked(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S,
+                                int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                                int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base, float temperature,
+                                int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream,
+                                bool truncated, int top_k, float top_p) {
   P5_REQUIRE(e->P, "engine not bound");
   P5_REQUIRE(B >= 1 && S >= 1 && S <= P5_WIDE_MAX_K, "sample_items: 1 <= samples per user <= 4096");
   P5_REQUIRE(max_len >= 2 && max_len <= P5_MAX_LEN, "sample_items: 2 <= max_length <= 128 (P5_MAX_LEN)");
@@ -3904,14 +3942,51 @@ int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
   P5_REQUIRE(excluded_words >= 0 && (excluded_nodes || excluded_words == 0), "excluded_nodes / excluded_words");
   P5_REQUIRE(stream_ids && out_seq && out_logprob && out_tok_logprob && out_len, "sample_items: stream_ids / outputs");
   P5_REQUIRE(e->c.d_model % (8 * (e->c.dtype == 1 ? 8 : 4)) == 0 && e->c.d_model <= 1024, "sample_items: d_model a multiple of 8 x 16 bytes, <= 1024");
-  const int64_t need = layout_sample(e, nullptr, B, L, S, max_len, nullptr, nullptr);
-  P5_REQUIRE(ws_bytes >= need, "sample_items: workspace too small (p5_sample_workspace_bytes)");
+  int64_t need = layout_sample(e, nullptr, B, L, S, max_len, nullptr, nullptr);
+  if (truncated) {
+    P5_REQUIRE(top_k >= 0, "sample_items_truncated: top_k >= 0 (0 = off)");
+    P5_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_items_truncated: 0 < top_p <= 1 (1 = off)");
+    need += trunc_scratch_bytes(B, S, max_children);
+    P5_REQUIRE(ws_bytes >= need, "sample_items_truncated: workspace too small (p5_sample_truncated_workspace_bytes)");
+  } else {
+    P5_REQUIRE(ws_bytes >= need, "sample_items: workspace too small (p5_sample_workspace_bytes)");
+  }
+  // off (top_k 0 or >= the widest node, top_p 1): the untruncated kernels, bit for bit
+  const bool trunc = truncated && ((top_k > 0 && top_k < max_children) || top_p < 1.f);
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
   return e->c.dtype == 1
              ? sample_items_impl<bf16>(e, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed,
-                                       stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream)
+                                       stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream,
+                                       trunc, top_k, top_p)
              : sample_items_impl<float>(e, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes, excluded_words, max_children, seed,
-                                        stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream);
+                                        stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, (char*)ws, (hipStream_t)stream,
+                                        trunc, top_k, top_p);
+}
+int p5_sample_items(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S,
+                    int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                    int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base, float temperature,
+                    int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws, int64_t ws_bytes, void* stream) {
+  return sample_items_checked(e, input_ids, whole_word_ids, attention_mask, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes,
+                              excluded_words, max_children, seed, stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, ws,
+                              ws_bytes, stream, false, 0, 1.f);
+}
+int64_t p5_sample_truncated_workspace_bytes(const P5Engine* e, int B, int L, int S, int max_len, int max_children, int excluded_words) {
+  (void)excluded_words;       // (the exclusion bitmap is read in place)
+  if (B < 1 || S < 1 || S > P5_WIDE_MAX_K || max_len < 2 || max_len > P5_MAX_LEN || L < 1 || L > 512 || max_children < 1) {
+    fail("sample_items_truncated: 1 <= samples per user <= 4096, 2 <= max_length <= 128, 1 <= L <= 512, max_children >= 1");
+    return -1;
+  }
+  P5Engine tmp = *e;
+  return layout_sample(&tmp, nullptr, B, L, S, max_len, nullptr, nullptr) + trunc_scratch_bytes(B, S, max_children);
+}
+int p5_sample_items_truncated(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L, int S,
+                              int max_len, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded_nodes,
+                              int excluded_words, int max_children, uint32_t seed, const uint32_t* stream_ids, uint32_t draw_base, float temperature,
+                              int top_k, float top_p, int* out_seq, float* out_logprob, float* out_tok_logprob, int* out_len, void* ws,
+                              int64_t ws_bytes, void* stream) {
+  return sample_items_checked(e, input_ids, whole_word_ids, attention_mask, B, L, S, max_len, child_off, child_tok, child_node, excluded_nodes,
+                              excluded_words, max_children, seed, stream_ids, draw_base, temperature, out_seq, out_logprob, out_tok_logprob, out_len, ws,
+                              ws_bytes, stream, true, top_k, top_p);
 }
 static int sbs_limits(int B, int S, int K, int max_len) {
   P5_REQUIRE(B >= 1 && K >= 1 && K <= P5_SBS_MAX_K, "sample_slates: 1 <= slate size <= 4096");
@@ -4457,6 +4532,49 @@ int p5_op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float
   P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
   if (dtype == 1) P5_LAUNCH((p5_trie_ce_bwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, (bf16*)dlogits, logits, lse, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   else P5_LAUNCH((p5_trie_ce_bwd_kernel<float>), dim3(rows), dim3(256), 0, s, (float*)dlogits, logits, lse, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
+  return P5_KCHECK();
+}
+static int trunc_ce_args(P5TruncCe* tc, int top_k, float top_p) {
+  P5_REQUIRE(top_k >= 0, "trunc: top_k >= 0 (0 = off)");
+  P5_REQUIRE(top_p > 0.f && top_p <= 1.f, "trunc: 0 < top_p <= 1 (1 = off)");
+  *tc = P5TruncCe{top_k, top_p};
+  return 0;
+}
+int p5_op_trunc_cut(float* cut, int* kept, const float* logits, const int* node, const int* child_off, const int* child_tok, const int* child_node,
+                    const uint32_t* excluded, int excl_words, float temperature, int top_k, float top_p, int rows, int rows_per_user, int ldl,
+                    void* stream) {
+  P5_REQUIRE(cut && kept && logits && node && rows >= 1 && rows_per_user >= 1 && rows % rows_per_user == 0 && ldl >= 1, "trunc_cut: arguments");
+  P5TrieCe tr;
+  P5TruncCe tc;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  P5_TRY(trunc_ce_args(&tc, top_k, top_p));
+  P5_LAUNCH(p5_trunc_cut_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, cut, kept, logits, node, tr, tc, rows_per_user, ldl);
+  return P5_KCHECK();
+}
+int p5_op_trunc_ce_fwd(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
+                       const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
+                       int top_k, float top_p, int rows, int T, int ldl, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(nll && lse && row_cut && state && logits && labels && node && rows >= 1 && T >= 1 && rows % T == 0 && ldl >= 1, "trunc_ce_fwd: arguments");
+  P5TrieCe tr;
+  P5TruncCe tc;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  P5_TRY(trunc_ce_args(&tc, top_k, top_p));
+  if (dtype == 1) P5_LAUNCH((p5_trunc_ce_fwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, nll, lse, row_cut, state, (int*)nullptr, logits, labels, node, tr, tc, T, ldl);
+  else P5_LAUNCH((p5_trunc_ce_fwd_kernel<float>), dim3(rows), dim3(256), 0, s, nll, lse, row_cut, state, (int*)nullptr, logits, labels, node, tr, tc, T, ldl);
+  return P5_KCHECK();
+}
+int p5_op_trunc_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
+                       const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded,
+                       int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(dlogits && logits && lse && row_cut && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0, "trunc_ce_bwd: arguments");
+  P5_REQUIRE(ldl >= 1 && ldd >= 1 && ldd % 8 == 0, "trunc_ce_bwd: ldd a multiple of 8");
+  P5_REQUIRE(dnll || out_attn, "trunc_ce_bwd: dnll, or out_attn [rows / T, T]");
+  P5TrieCe tr;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  if (dtype == 1) P5_LAUNCH((p5_trunc_ce_bwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, (bf16*)dlogits, logits, lse, row_cut, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
+  else P5_LAUNCH((p5_trunc_ce_bwd_kernel<float>), dim3(rows), dim3(256), 0, s, (float*)dlogits, logits, lse, row_cut, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   return P5_KCHECK();
 }
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream) {

@@ -194,7 +194,7 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
-        self.last_item_loss_state = None    # int32 [B, T] device tensor of the last item-loss forward (forward(trie=...)): 0 scored, 1 past the end, 2 off the trie
+        self.last_item_loss_state = None    # int32 [B, T] device tensor of the last item-loss forward (forward(trie=...)): 0 scored, 1 past the end, 2 off the trie, 3 truncated away
         self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("sample": sample_items() / generate(do_sample=True); "slates": sample_slates(); "rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
                            "pruned_calls": 0, "certified_users": 0, "fallback_users": 0, "declined_users": 0, "kept_rows_per_user": 0,
@@ -510,10 +510,25 @@ class P5T5Native(nn.Module):
     def _i64(t, device):
         return t.to(device=device, dtype=torch.int64).contiguous()
 
-    def _item_loss_setup(self, trie, temperature, excluded_items, B):
+    @staticmethod
+    def _truncation(top_k, top_p):
+        """checked (top_k, top_p) of `sample_items` / the item loss: top_k an integer >= 0 (0 = off), 0 < top_p <= 1 (1 = off)"""
+        if top_k is None:
+            top_k = 0
+        if top_p is None:
+            top_p = 1.0
+        if isinstance(top_k, bool) or int(top_k) != top_k or int(top_k) < 0:
+            raise ValueError(f"top_k={top_k!r}: an integer >= 0 (0 = no top-k truncation)")
+        p = float(top_p)
+        if not (0.0 < p <= 1.0):
+            raise ValueError(f"top_p={top_p!r}: 0 < top_p <= 1 (1 = no nucleus truncation)")
+        return min(int(top_k), 2 ** 31 - 1), p
+
+    def _item_loss_setup(self, trie, temperature, excluded_items, B, top_k=0, top_p=1.0):
         """The checked setting of the trie-normalised item loss (csrc/p5_trie_ce.h) for a batch of B users: the trie on the device, the
-        temperature (the check of `_sampling_setup`) and the excluded-node bitmap (the rule of `sample_items`)."""
+        temperature (the check of `_sampling_setup`), the excluded-node bitmap (the rule of `sample_items`) and the truncation."""
         dev = self._be.device
+        top_k, top_p = self._truncation(top_k, top_p)
         tau = float(temperature)
         if not (tau > 0.0 and math.isfinite(tau)):
             raise ValueError(f"temperature={temperature!r}: a finite value > 0")
@@ -534,13 +549,21 @@ class P5T5Native(nn.Module):
             excl_words = int(excl_np.shape[1])
             excl_t = torch.from_numpy(np.ascontiguousarray(excl_np).view(np.int32)).to(dev)
         off, tok, nxt = trie.device_arrays(dev)
-        return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, n_nodes=int(trie.n_nodes), excl_t=excl_t, excl_words=excl_words)
+        return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, n_nodes=int(trie.n_nodes), excl_t=excl_t, excl_words=excl_words, top_k=top_k,
+                                     top_p=top_p, row_cut=None)
 
     def _arm_item_loss(self, q, B, T):
-        """p5_train_set_item_loss for the engine's next forward; the rows' states land in `last_item_loss_state` (no host sync)."""
+        """p5_train_set_item_loss (or its truncated sibling) for the engine's next forward; the rows' states land in `last_item_loss_state`
+        (no host sync).  Truncated: the rows' cuts live in q.row_cut, which the saved inputs keep alive until the backward has run."""
         state = torch.empty(B, T, dtype=torch.int32, device=self._be.device)
-        self._be.check(self._lib.p5_train_set_item_loss(self._engine, _ptr(q.off), _ptr(q.tok), _ptr(q.nxt), q.n_nodes, _ptr(q.excl_t), q.excl_words,
-                                                        q.tau, _ptr(state)), "p5_train_set_item_loss")
+        if q.top_k > 0 or q.top_p < 1.0:
+            q.row_cut = torch.empty(B, T, dtype=torch.float32, device=self._be.device)
+            self._be.check(self._lib.p5_train_set_item_loss_truncated(self._engine, _ptr(q.off), _ptr(q.tok), _ptr(q.nxt), q.n_nodes, _ptr(q.excl_t),
+                                                                      q.excl_words, q.tau, _ptr(state), q.top_k, q.top_p, _ptr(q.row_cut)),
+                           "p5_train_set_item_loss_truncated")
+        else:
+            self._be.check(self._lib.p5_train_set_item_loss(self._engine, _ptr(q.off), _ptr(q.tok), _ptr(q.nxt), q.n_nodes, _ptr(q.excl_t), q.excl_words,
+                                                            q.tau, _ptr(state)), "p5_train_set_item_loss")
         self.last_item_loss_state = state
 
     def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels, item_loss=None):
@@ -643,12 +666,14 @@ class P5T5Native(nn.Module):
             ev1.record()
             self.ddp_wait_ms.append((ev0, ev1))     # (read by bench.py after a synchronize: main-stream time spent waiting for the buckets)
 
-    def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None):
+    def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None,
+                          top_k=0, top_p=1.0):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
         none of the ~10 elementwise launches of the generic path.  Returns the loss as a 0-dim tensor; gradients are in `.grad`.
-        `trie`, `temperature`, `excluded_items`: the trie-normalised item loss, as in `forward` (the masked mean then runs over its NLL)."""
+        `trie`, `temperature`, `excluded_items`, `top_k`, `top_p`: the trie-normalised item loss, as in `forward` (the masked mean then runs
+        over its NLL)."""
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
         B, L = input_ids.shape
@@ -657,7 +682,7 @@ class P5T5Native(nn.Module):
         labels = self._i64(labels, dev)
         output_attention = self._i64(output_attention, dev)
         T = labels.shape[1]
-        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B)
+        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p)
         self._sync_shadow()
         self._sync_transposed()
         ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
@@ -679,7 +704,7 @@ class P5T5Native(nn.Module):
         self._rng[1] = self._rng_cpu[1] if self._rng_cpu[1] < 2 ** 31 else self._rng_cpu[1] - 2 ** 32
 
     def forward(self, input_ids=None, whole_word_ids=None, attention_mask=None, labels=None, alpha=None, return_dict=True, trie=None,
-                temperature=1.0, excluded_items=None, **unused):
+                temperature=1.0, excluded_items=None, top_k=0, top_p=1.0, **unused):
         """P5_T5.forward (P5_T5.py:275-386): returns {"loss": flat [B*T] per-token NLL}; `alpha` is accepted and ignored
         exactly as in the reference (P5_T5.py:294).
         `trie` (Trie / CompiledTrie; None = the full-vocabulary cross-entropy, unchanged): the trie-normalised item loss (csrc/p5_trie_ce.h),
@@ -689,7 +714,11 @@ class P5T5Native(nn.Module):
         and exclusion, forward(labels=drawn[:, 1:]) returns -token_logprobs of the draw and its backward is the score function of what was
         drawn.  Positions behind </s>, at label -100 and behind it, and every position from the first label that is not an allowed child
         on, have NLL 0 and no gradient; `last_item_loss_state` (int32 [B, T] on the device, no host sync) says which: 0 scored, 1 past the
-        end, 2 off the trie.  The head still runs over the whole vocabulary and the logits gradient is dense, so gradient accumulation
+        end, 2 off the trie.
+        `top_k` (0 = off) / `top_p` (1 = off): the loss of the TRUNCATED distribution `sample_items(top_k=, top_p=)` draws from
+        (csrc/p5_trunc.h) -- the normalisation runs over the kept children only and the kept set is a constant of the gradient (HF's
+        masked_fill under autograd); a label that is allowed but below the row's cut has NLL 0, no gradient and state 3 (truncated away),
+        for that row only.  The head still runs over the whole vocabulary and the logits gradient is dense, so gradient accumulation
         (`begin_micro_batch`), DDP and the staged backward work as for the plain loss, unchanged."""
         if labels is None:
             raise ValueError("P5T5Native.forward needs labels (the runner always passes them)")
@@ -702,7 +731,7 @@ class P5T5Native(nn.Module):
             attention_mask = (input_ids != self.config.pad_token_id).long()
         attention_mask = self._i64(attention_mask, dev)
         labels = self._i64(labels, dev)
-        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0])
+        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], top_k, top_p)
         nll = _P5LossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels, item_loss)
         out = {"loss": nll}
         return out if return_dict else (nll,)
@@ -1364,9 +1393,11 @@ class P5T5Native(nn.Module):
         if int(num_beams) != 1:
             raise ValueError(f"generate(do_sample=True, num_beams={num_beams}): beam sampling is not built; {supported}")
         if kw.get("top_k") not in (None, 0):
-            raise ValueError(f"generate(do_sample=True, top_k={kw.get('top_k')}): top-k truncation is not built; {supported}")
+            raise ValueError(f"generate(do_sample=True, top_k={kw.get('top_k')}): truncation is not wired into generate(), call "
+                             f"sample_items(top_k=, top_p=); {supported}")
         if kw.get("top_p") not in (None, 1, 1.0):
-            raise ValueError(f"generate(do_sample=True, top_p={kw.get('top_p')}): nucleus truncation is not built; {supported}")
+            raise ValueError(f"generate(do_sample=True, top_p={kw.get('top_p')}): truncation is not wired into generate(), call "
+                             f"sample_items(top_k=, top_p=); {supported}")
         if roots is not None:
             raise ValueError(f"generate(do_sample=True, roots=...): per-user roots are not built; {supported}")
         if trie is None and prefix_allowed_tokens_fn is not None:
@@ -1390,7 +1421,7 @@ class P5T5Native(nn.Module):
 
     @torch.no_grad()
     def sample_items(self, input_ids=None, attention_mask=None, whole_word_ids=None, trie=None, num_samples: int = 1, temperature: float = 1.0,
-                     excluded_items=None, seed: Optional[int] = None, streams=None, draw_base: int = 0):
+                     excluded_items=None, seed: Optional[int] = None, streams=None, draw_base: int = 0, top_k: int = 0, top_p: float = 1.0):
         """Draw `num_samples` items per user from the model's distribution over the catalogue (on-policy samples for preference / policy-
         gradient fine-tuning, exploration, Monte-Carlo estimates).  What HF's sampling path computes under the item trie: at every step
         softmax(logits / temperature) renormalised over the allowed children of the prefix, one child drawn (Gumbel-max on the device,
@@ -1403,6 +1434,12 @@ class P5T5Native(nn.Module):
         draw) are the coordinates of the counter-based uniforms (csrc/p5_rng.h): a draw is a pure function of (weights, the user's input,
         seed, stream, draw index), so user chunks (at most `wide_max_rows` decode rows per engine call) and draw ranges (`num_samples` >
         4096, or split by hand with `draw_base`) do not change a bit of the result.
+        `top_k` (0 = off) / `top_p` (1 = off): HF's TopKLogitsWarper then TopPLogitsWarper on the allowed children, behind the temperature
+        (csrc/p5_trunc.h): the k largest stay (ties at the k-th value all stay), then child i stays iff the probability mass strictly above
+        it is < top_p -- by value, so equal logits stay or leave together (HF cuts inside such a group by sort position).  The returned
+        log-probabilities are those of the truncated distribution (exactly 0 where one child is kept: top_k=1 is the greedy descent); a
+        child's noise does not depend on the truncation, so a draw whose untruncated path stays inside the kept sets is the same draw.
+        With both off the untruncated kernels run.  `forward(trie=, top_k=, top_p=)` is the loss of this distribution.
         Returns {"sequences" int64 [B * S, T] (decoder start first, pad-filled; T = depth of the trie), "sequences_logprob" fp32 [B * S]
         (-inf for a user with nothing to draw), "token_logprobs" fp32 [B * S, T - 1] (0 at forced-prefix positions and behind </s>),
         "item_index" int64 [B, S] (-1 for a user with nothing to draw; None for a trie with an appended trie, which cannot be indexed)}."""
@@ -1419,7 +1456,9 @@ class P5T5Native(nn.Module):
             if trie.grafted:
                 raise ValueError("sample_items(excluded_items=...): a trie with an appended trie (Trie.append) cannot be indexed")
             excl_np = self._excluded_items_bitmap(trie, excluded_items, input_ids.shape[0])
-        seq, lp, tok_lp, ln = self._sample(input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base)
+        top_k, top_p = self._truncation(top_k, top_p)
+        seq, lp, tok_lp, ln = self._sample(input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, top_k=top_k,
+                                           top_p=top_p)
         B, _, T = seq.shape
         item_index = None
         if not trie.grafted:
@@ -1533,7 +1572,8 @@ class P5T5Native(nn.Module):
                                      B=B, L=L, T=T, streams_t=streams_t, base=base, seed=seed, excl_t=excl_t, excl_words=excl_words, ftok=ftok, fnode=fnode,
                                      alive=alive)
 
-    def _sample(self, input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, max_length=None):
+    def _sample(self, input_ids, attention_mask, whole_word_ids, trie, S, temperature, excl_np, seed, streams, draw_base, max_length=None, top_k=0,
+                top_p=1.0):
         """The engine calls of sample_items / generate(do_sample=True): (sequences int32 [B, S, T], log-probability [B, S], per-position
         log-probabilities [B, S, T], generated tokens [B, S]).  `excl_np`: uint32 [B, words] excluded-node bitmap or None."""
         lib, dev = self._lib, self._be.device
@@ -1544,6 +1584,7 @@ class P5T5Native(nn.Module):
         lane = self._cur_lane()
         engine, sp = lane.engine, self._be.stream_ptr()
         maxc = max(1, trie.max_children)
+        truncated = (0 < top_k < maxc) or top_p < 1.0        # (off: the untruncated entry point, the same bits)
         seq = torch.empty(B, S, T, dtype=torch.int32, device=dev)
         lp = torch.empty(B, S, dtype=torch.float32, device=dev)
         tok_lp = torch.empty(B, S, T, dtype=torch.float32, device=dev)
@@ -1575,11 +1616,20 @@ class P5T5Native(nn.Module):
                 if ftok:
                     arr = (ctypes.c_int * len(ftok))
                     self._be.check(lib.p5_generate_set_forced_prefix(engine, arr(*ftok), arr(*fnode), len(ftok)), "p5_generate_set_forced_prefix")
-                ws = self._lane_workspace(lane, lib.p5_sample_workspace_bytes(engine, nb, L, sc, T, maxc, excl_words), "sample")
+                need = (lib.p5_sample_truncated_workspace_bytes if truncated else lib.p5_sample_workspace_bytes)(engine, nb, L, sc, T, maxc, excl_words)
+                if need < 0:
+                    self._be.check(-1, "p5_sample_truncated_workspace_bytes")
+                ws = self._lane_workspace(lane, need, "sample")
                 ids_c, ww_c, mask_c, ex_c, st_c = cut(input_ids), cut(whole_word_ids), cut(attention_mask), cut(excl_t), cut(streams_t)
-                self._be.check(lib.p5_sample_items(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, sc, T, _ptr(off), _ptr(tok), _ptr(nxt), _ptr(ex_c),
-                                                   excl_words, maxc, seed, _ptr(st_c), (draw_base + s0) & 0xFFFFFFFF, tau, _ptr(o_seq), _ptr(o_lp),
-                                                   _ptr(o_tok), _ptr(o_ln), _ptr(ws), ws.numel(), sp), "p5_sample_items")
+                if truncated:
+                    self._be.check(lib.p5_sample_items_truncated(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, sc, T, _ptr(off), _ptr(tok), _ptr(nxt),
+                                                                 _ptr(ex_c), excl_words, maxc, seed, _ptr(st_c), (draw_base + s0) & 0xFFFFFFFF, tau, top_k,
+                                                                 top_p, _ptr(o_seq), _ptr(o_lp), _ptr(o_tok), _ptr(o_ln), _ptr(ws), ws.numel(), sp),
+                                   "p5_sample_items_truncated")
+                else:
+                    self._be.check(lib.p5_sample_items(engine, _ptr(ids_c), _ptr(ww_c), _ptr(mask_c), nb, L, sc, T, _ptr(off), _ptr(tok), _ptr(nxt), _ptr(ex_c),
+                                                       excl_words, maxc, seed, _ptr(st_c), (draw_base + s0) & 0xFFFFFFFF, tau, _ptr(o_seq), _ptr(o_lp),
+                                                       _ptr(o_tok), _ptr(o_ln), _ptr(ws), ws.numel(), sp), "p5_sample_items")
                 if not whole:
                     seq[users, s0:s0 + sc], lp[users, s0:s0 + sc], tok_lp[users, s0:s0 + sc], ln[users, s0:s0 + sc] = o_seq, o_lp, o_tok, o_ln
                 calls += 1

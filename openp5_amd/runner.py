@@ -75,6 +75,10 @@ def parse_runner_args(parser):
                         "items of all training datasets), the likelihood of the distribution P5T5Native.sample_items / sample_slates draw from.  "
                         "0 = the full-vocabulary cross-entropy, untouched.")
     parser.add_argument("--item_loss_temperature", type=float, default=1.0, help="temperature of --train_item_loss 1 (logits / temperature)")
+    parser.add_argument("--item_loss_top_k", type=int, default=0, help="top-k truncation of --train_item_loss 1: the loss of the distribution "
+                        "sample_items(top_k=...) draws from (0 = off)")
+    parser.add_argument("--item_loss_top_p", type=float, default=1.0, help="nucleus truncation of --train_item_loss 1 (sample_items(top_p=...)); "
+                        "1.0 = off")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -118,7 +122,7 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
     (SingleRunner.py:182), which drives its schedule to lr = 0 after 1/accum of the run; this is the intended behaviour.
 
     `item_loss` (None = the full-vocabulary cross-entropy): keyword arguments of the native model's trie-normalised item loss --
-    {"trie": ..., "temperature": ...} (`P5T5Native.forward`)."""
+    {"trie": ..., "temperature": ...[, "top_k": ..., "top_p": ...]} (`P5T5Native.forward`)."""
     kw = item_loss or {}
     input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
     fused = getattr(model, "loss_and_backward", None)
@@ -417,6 +421,9 @@ class DistributedRunner:
                     seen.add(ds.dataset)
                     seqs += self._item_sequences(ds, list(ds.all_items))
             kw = self._item_loss = {"trie": CompiledTrie.from_trie(Trie(seqs)), "temperature": float(getattr(self.args, "item_loss_temperature", 1.0))}
+            top_k, top_p = int(getattr(self.args, "item_loss_top_k", 0)), float(getattr(self.args, "item_loss_top_p", 1.0))
+            if top_k != 0 or top_p != 1.0:          # (off: the keyword arguments of the untruncated loss, as before)
+                kw.update(top_k=top_k, top_p=top_p)
         return kw
 
     @torch.no_grad()

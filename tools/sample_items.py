@@ -5,7 +5,10 @@ lands on both; one JSON line per configuration:
   ms per call (median and spread over the rounds), the draft search's ms from the same run, their ratio, the decode steps either runs,
   and the device ms of one sampling call split by phase (in-run profiler, p5_profile_begin / end: each launch's time includes its
   dispatch gap).
-python tools/sample_items.py [--rows 10,64] [--users 20] [--dtype bf16] [--rounds 7] [--min_seconds 0.5] [--tag NAME] [--out FILE]"""
+With --top_k / --top_p (csrc/p5_trunc.h) the truncated call is timed instead of the search, alternating with the untruncated call at the same
+shape: "what": "sample_items_truncated", the two medians and their ratio.
+python tools/sample_items.py [--rows 10,64] [--users 20] [--dtype bf16] [--rounds 7] [--min_seconds 0.5] [--top_k K] [--top_p P] [--tag NAME]
+                             [--out FILE]"""
 import argparse
 import ctypes
 import json
@@ -21,6 +24,8 @@ ap.add_argument("--users", type=int, default=20)
 ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--min_seconds", type=float, default=0.5)
+ap.add_argument("--top_k", type=int, default=0)
+ap.add_argument("--top_p", type=float, default=1.0)
 ap.add_argument("--tag", default="this")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--out", default=None)
@@ -35,7 +40,7 @@ from openp5_amd.model import P5ModelConfig, P5T5Native  # noqa: E402
 from openp5_amd.trie import CompiledTrie  # noqa: E402
 
 # phase <- kernel name prefixes
-PARTS = (("selection", ("p5_sample_",)), ("step_attention", ("p5_dec_self_attn", "p5_dec_cross_attn")), ("step_gemm", ("p5_skinny",)),
+PARTS = (("selection", ("p5_sample_", "p5_trunc_sample_")), ("step_attention", ("p5_dec_self_attn", "p5_dec_cross_attn")), ("step_gemm", ("p5_skinny",)),
          ("step_norm_gelu", ("p5_rmsnorm_f32in", "p5_gated_gelu")), ("encoder_and_prefix_attention", ("p5_attn_fwd",)),
          ("encoder_and_prefix_gemm", ("p5_gemm", "p5_g4", "p5_g5")))
 
@@ -85,6 +90,24 @@ def main(a):
     lines = []
     for R in (int(x) for x in a.rows.split(",")):
         draw = lambda: model.sample_items(trie=ct, num_samples=R, seed=1, **kw)      # noqa: E731
+        if a.top_k != 0 or a.top_p != 1.0:
+            trunc = lambda: model.sample_items(trie=ct, num_samples=R, seed=1, top_k=a.top_k, top_p=a.top_p, **kw)      # noqa: E731
+            for fn in (draw, trunc, draw, trunc):
+                fn()
+            torch.cuda.synchronize()
+            t_draw, t_trunc = [], []
+            for _ in range(a.rounds):
+                t_draw.append(window(draw, a.min_seconds) * 1e3)
+                t_trunc.append(window(trunc, a.min_seconds) * 1e3)
+            md, mt = statistics.median(t_draw), statistics.median(t_trunc)
+            line = {"tag": a.tag, "what": "sample_items_truncated", "dtype": a.dtype, "n_items": 3416, "max_children": int(ct.max_children), "B": B, "L": L,
+                    "rows_per_user": R, "rounds": a.rounds, "top_k": a.top_k, "top_p": a.top_p, "sample_ms": round(md, 4),
+                    "sample_ms_min_max": [round(min(t_draw), 4), round(max(t_draw), 4)], "truncated_ms": round(mt, 4),
+                    "truncated_ms_min_max": [round(min(t_trunc), 4), round(max(t_trunc), 4)], "truncated_over_untruncated": round(mt / md, 4),
+                    "truncated_ms_by_phase": profile_split(model._lib, lambda: (trunc(), torch.cuda.synchronize()))}
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+            continue
         search = lambda: model.generate(trie=ct, max_length=depth, num_beams=R, num_return_sequences=R, **kw)      # noqa: E731
         for fn in (draw, search, draw, search):          # warm-up: workspaces, code objects, the search's decode-step graph
             fn()
