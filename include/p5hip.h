@@ -136,6 +136,20 @@ int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_t
 int p5_train_set_item_loss_truncated(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes,
                                      const uint32_t* excluded_nodes, int excluded_words, float temperature, int* row_state_out, int top_k,
                                      float top_p, float* row_cut /* DEVICE [B*T] */);
+/* The item loss on a head RESTRICTED to the trie's tokens (openp5_amd/csrc/p5_item_head.h), opt-in.  U = the distinct tokens on the trie's edges,
+ * ascending; Nu = |U|, Nup = Nu rounded up to 64.  The forward gathers the rows U of the head weight into E_U [Nup, d], the head GEMM writes
+ * logits_U [B*T, Nup] instead of [B*T, Vp], the cross-entropy kernels read a child's logit at child_col[edge] (one int per CSR edge: the index of
+ * child_tok[edge] in head_tokens), and the backward writes dlogits_U, takes dhn over K = Nup (the same ordered split-K partial sums) and
+ * dE_U [Nup, d] with one un-split GEMM, which one kernel scatters into shared.weight's gradient: all V rows on a storing first micro-batch
+ * (zeros outside U), the rows U added otherwise.  No [B*T, Vp] array is written or read.  The loss, the row states and row_cut are those of
+ * the dense route on equal logits; the two heads' logits differ by the GEMMs' rounding only.
+ * Call it BEHIND p5_train_set_item_loss[_truncated] and in front of the forward; one-shot like them (a new p5_train_set_item_loss disarms it).
+ * ws: DEVICE, 256-byte aligned, at least p5_item_head_workspace_bytes(e, B, T, n_tokens) bytes for the batch of the forward (the forward
+ * checks it); it holds E_U, logits_U, dlogits_U and dE_U and must stay valid, like head_tokens and child_col, until the backward has run.
+ * p5_train_workspace_bytes is unchanged.  Errors: no item loss armed, n_tokens outside [1, vocab_size], null arguments, ws too small. */
+size_t p5_item_head_workspace_bytes(const P5Engine* e, int B, int T, int n_tokens);
+int p5_train_set_item_head(P5Engine* e, const int* head_tokens /* DEVICE [n_tokens], ascending, distinct */, int n_tokens,
+                           const int* child_col /* DEVICE [n_edges] */, void* ws, size_t ws_bytes);
 int p5_backward_num_stages(const P5Engine* e);
 int p5_backward_stage(P5Engine* e, const float* dnll, int stage, void* stream);
 int p5_backward(P5Engine* e, const float* dnll, void* stream);
@@ -589,6 +603,29 @@ int p5_op_trunc_ce_fwd(int dtype, float* nll, float* lse, float* row_cut, int* s
 int p5_op_trunc_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
                        const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded,
                        int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream);
+/* the kernels of the restricted item head (p5_item_head.h; see p5_train_set_item_head), one by one:
+ * p5_op_item_gather: EU T [Nup, d] = rows `tokens` of E T [*, d], rows [n_tokens, Nup) zeros (Nup = n_tokens rounded up to 64; d a multiple of 16 bytes);
+ * p5_op_item_scatter: dEU fp32 [Nup, d] into dE fp32 [V, d].  store != 0: every row v < V is written, dEU[index of v in tokens] or zeros;
+ *   store == 0: dE[tokens[r]] += dEU[r] for r < n_tokens, every other row untouched.  tokens ascending and distinct, all < V;
+ * p5_op_*_cols: the four cross-entropy entries above on a COMPACT row -- child_col int32 [n_edges] gives the column of an edge's token in
+ *   logits [rows, ldl] and dlogits [rows, ldd]; labels, nodes, states and the bitmap stay on tokens and nodes.  The arithmetic per child and
+ *   the order of reduction are those of the dense entries: on equal logits nll, lse, row_cut and the entries of dlogits are equal bit for bit. */
+int p5_op_item_gather(int dtype, void* EU, const void* E, const int* tokens, int n_tokens, int d, void* stream);
+int p5_op_item_scatter(float* dE, const float* dEU, const int* tokens, int n_tokens, int V, int d, int store, void* stream);
+int p5_op_trie_ce_fwd_cols(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
+                           const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded, int excl_words,
+                           float temperature, int rows, int T, int ldl, void* stream);
+int p5_op_trie_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
+                           const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                           const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
+                           float gscale, void* stream);
+int p5_op_trunc_ce_fwd_cols(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
+                            const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded,
+                            int excl_words, float temperature, int top_k, float top_p, int rows, int T, int ldl, void* stream);
+int p5_op_trunc_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
+                            const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                            const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
+                            float gscale, void* stream);
 /* loss[0] = mean_b(sum_t nll[b, t] m[b, t] / max(sum_t m[b, t], 1)), m = (out_attn != 0) */
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];

@@ -29,6 +29,7 @@
 #include "p5_sample.h"
 #include "p5_sbs.h"
 #include "p5_trie_ce.h"
+#include "p5_item_head.h"
 #include "p5_trunc.h"
 #include "../../include/p5hip.h"
 
@@ -154,6 +155,12 @@ struct P5Engine {
   struct ItemLoss {
     bool on = false; P5TrieCe tr = {nullptr, nullptr, nullptr, nullptr, 0, 1.f}; int* state_out = nullptr;
     bool trunc = false; P5TruncCe tc = {0, 1.f}; float* row_cut = nullptr;
+    // head: the head restricted to the trie's tokens (p5_item_head.h, p5_train_set_item_head) -- tr.col is set, the caller's workspace holds
+    // E_U [Nup, d] T | logits_U [Md, Nup] fp32 | dlogits_U [Md, Nup] T | dE_U [Nup, d] fp32, laid out by the forward, which knows Md
+    // (item_head_layout)
+    bool head = false; const int* head_tok = nullptr; int Nu = 0, Nup = 0;
+    void* head_ws = nullptr; size_t head_ws_bytes = 0;
+    void *EU = nullptr, *dlogitsU = nullptr; float *logitsU = nullptr, *dEU = nullptr;
   };
   ItemLoss il_next, il;
   void* Sf = nullptr;              // folded bf16 weight copy W diag(ln) for q/k/v, wi, cross-attention q (same arena offsets; behind St)
@@ -826,6 +833,23 @@ static int zero_small_grads(P5Engine* e, hipStream_t s) {
   return P5_KCHECK();
 }
 
+// the caller's workspace of the restricted item head (p5_item_head.h): E_U | logits_U | dlogits_U | dE_U.  The split-K partial products of
+// its input gradient are [Md, d] slices like the dense head's and live in dres_b.
+static size_t item_head_layout(const P5Engine* e, char* base, size_t Md, size_t Nup, P5Engine::ItemLoss* h) {
+  const size_t sz = e->c.dtype == 1 ? 2 : 4, d = (size_t)e->c.d_model;
+  Bump b{base, 0};
+  void* EU = b.take(Nup * d * sz);
+  float* lg = (float*)b.take(Md * Nup * 4);
+  void* dl = b.take(Md * Nup * sz);
+  float* dEU = (float*)b.take(Nup * d * 4);
+  if (h) { h->EU = EU; h->logitsU = lg; h->dlogitsU = dl; h->dEU = dEU; }
+  return b.off;
+}
+static unsigned item_head_blocks(long long pieces) {
+  const long long b = (pieces + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
 static int64_t layout_ws(P5Engine* e, char* base, int B, int L, int T, bool with_bwd) {
   const P5Config& c = e->c;
   const size_t sz = c.dtype == 1 ? 2 : 4;
@@ -1111,6 +1135,17 @@ static int decoder_fwd(P5Engine* e, hipStream_t s, float* nll_out = nullptr) {
     e->ce_free_fwd = true;
     return 0;
   }
+  if (e->il.on && e->il.head) {
+    // the head over the trie's tokens only: E_U = the rows U of the head weight, logits_U [Md, Nup] = alpha hn E_U^T
+    P5Engine::ItemLoss& h = e->il;
+    P5_REQUIRE(d % TT<T>::EPF == 0, "item head: d_model must be a multiple of 16 bytes");
+    const size_t need = item_head_layout(e, (char*)h.head_ws, Md, h.Nup, &h);
+    P5_REQUIRE(h.head_ws_bytes >= need, "item head: workspace too small for this batch (p5_item_head_workspace_bytes)");
+    P5_LAUNCH((p5_item_gather_kernel<T>), dim3(item_head_blocks((long long)h.Nup * (d / TT<T>::EPF))), dim3(256), 0, s, (T*)h.EU, Wc<T>(e, e->off_E), h.head_tok,
+              h.Nu, h.Nup, d);
+    P5_TRY(P5_KCHECK());
+    return linear_fwd<T>(s, e->dec_hn, d, (const T*)h.EU, h.logitsU, h.Nup, Md, h.Nup, d, P5_EPI_STORE, nullptr, 0, alpha, 1);
+  }
   P5_TRY(linear_fwd<T>(s, e->dec_hn, d, Wc<T>(e, e->off_E), e->logits, e->Vp, Md, c.vocab_size, d, P5_EPI_STORE, nullptr, 0, alpha, 1));
   return 0;
 }
@@ -1124,13 +1159,16 @@ static int forward_impl(P5Engine* e, float* nll_out, hipStream_t s) {
     P5_LAUNCH(p5_trie_walk_kernel, dim3(e->B), dim3(256), 0, s, (int*)e->ce_lab, (int*)e->ce_g, e->il.state_out, e->labels, e->il.tr, e->T, e->c.pad_id,
               e->c.eos_id);
     P5_TRY(P5_KCHECK());
+    // (restricted head: the compact row, columns through il.tr.col)
+    const float* lg = e->il.head ? (const float*)e->il.logitsU : (const float*)e->logits;
+    const int ldl = e->il.head ? e->il.Nup : e->Vp;
     if (e->il.trunc) {
       P5_LAUNCH((p5_trunc_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, e->il.row_cut, (int*)e->ce_g, e->il.state_out,
-                (const float*)e->logits, e->labels, (const int*)e->ce_lab, e->il.tr, e->il.tc, e->T, e->Vp);
+                lg, e->labels, (const int*)e->ce_lab, e->il.tr, e->il.tc, e->T, ldl);
       return P5_KCHECK();
     }
-    P5_LAUNCH((p5_trie_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, (const float*)e->logits, e->labels, (const int*)e->ce_lab,
-              (const int*)e->ce_g, e->il.tr, e->T, e->Vp);
+    P5_LAUNCH((p5_trie_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, lg, e->labels, (const int*)e->ce_lab,
+              (const int*)e->ce_g, e->il.tr, e->T, ldl);
     return P5_KCHECK();
   }
   P5_LAUNCH((p5_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, (const float*)e->logits, e->labels, e->c.vocab_size, e->Vp);
@@ -1351,6 +1389,12 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     e->zg_pending = false;
     if (!dnll) P5_REQUIRE(e->out_attn, "backward without dnll needs p5_forward_loss (output_attention mask)");
     const float alpha = 1.0f / sqrtf((float)d);
+    // the head's logits, their gradient and their leading dimension: the vocabulary's, or -- item loss on the restricted head
+    // (p5_item_head.h) -- the compact arrays of the caller's workspace
+    const bool hd = e->il.on && e->il.head;
+    const float* hd_lg = hd ? (const float*)e->il.logitsU : (const float*)e->logits;
+    void* hd_dl = hd ? e->il.dlogitsU : e->dlogits;
+    const int hd_ld = hd ? e->il.Nup : e->Vp;
     if (e->ce_free_fwd) {
       // dlogits = (softmax - onehot) * g straight out of the recomputed head GEMM (same operands, same accumulation order: the same logits)
       P5_LAUNCH(p5_ce_gscale_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->ce_g, e->labels, dnll, e->out_attn, e->T, 1.0f / (float)e->B, Md);
@@ -1362,13 +1406,13 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       g.ce_labels = e->labels; g.ce_lse = e->lse_tok; g.ce_g = e->ce_g; g.ce_np = (c.vocab_size + 63) / 64;
       P5_TRY(launch_gemm<T>(g, s));
     } else if (e->il.on && e->il.trunc) {
-      P5_LAUNCH((p5_trunc_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok,
-                (const float*)e->il.row_cut, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, e->Vp, e->Vp, e->out_attn, e->T,
+      P5_LAUNCH((p5_trunc_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, (const float*)e->lse_tok,
+                (const float*)e->il.row_cut, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, hd_ld, hd_ld, e->out_attn, e->T,
                 1.0f / (float)e->B);
       P5_TRY(P5_KCHECK());
     } else if (e->il.on) {
-      P5_LAUNCH((p5_trie_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok, e->labels,
-                (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, e->Vp, e->Vp, e->out_attn, e->T, 1.0f / (float)e->B);
+      P5_LAUNCH((p5_trie_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, (const float*)e->lse_tok, e->labels,
+                (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, hd_ld, hd_ld, e->out_attn, e->T, 1.0f / (float)e->B);
       P5_TRY(P5_KCHECK());
     } else {
       P5_LAUNCH((p5_ce_bwd_kernel<T>), dim3(Md, Md >= 2048 ? 1 : (Md >= 512 ? 4 : 8)), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok,
@@ -1376,8 +1420,19 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       P5_TRY(P5_KCHECK());
     }
     // dE += alpha * dlogits^T hn ;  dhn = alpha * dlogits E
-    P5_TRY(linear_wgrad<T>(e, s, e->dlogits, e->Vp, e->dec_hn, d, e->G + e->off_E, Md, c.vocab_size, d, alpha));
-    P5_TRY(wgrad_flush(e, s, true, (g_opt_wgrad_side & 1) != 0));
+    if (hd) {
+      // dE_U = alpha dlogits_U^T hn: ONE un-split GEMM that stores (one writer per element), then the scatter into shared.weight's gradient on
+      // this stream -- ahead of the embedding sums of the last stage, which add into the same rows.  Nothing is queued: the weight-gradient
+      // plan runs without head entries.  A storing backward writes ALL V rows (the arena was not cleared), the others add at the rows U.
+      P5_TRY(gemm<T>(s, hd_dl, hd_ld, 1, e->dec_hn, d, 1, e->il.dEU, d, e->il.Nup, d, Md, P5_EPI_STORE, nullptr, 0, alpha, 1, no_drop()));
+      const int store = e->wg_epi == P5_EPI_STORE ? 1 : 0;
+      P5_LAUNCH(p5_item_scatter_kernel, dim3(item_head_blocks((long long)(store ? c.vocab_size : e->il.Nu) * (d / 4))), dim3(256), 0, s, e->G + e->off_E,
+                (const float*)e->il.dEU, e->il.head_tok, e->il.Nu, c.vocab_size, d, store);
+      P5_TRY(P5_KCHECK());
+    } else {
+      P5_TRY(linear_wgrad<T>(e, s, e->dlogits, e->Vp, e->dec_hn, d, e->G + e->off_E, Md, c.vocab_size, d, alpha));
+      P5_TRY(wgrad_flush(e, s, true, (g_opt_wgrad_side & 1) != 0));
+    }
     {
       // K = vocab is long and M*N small: split-K.  The splits STORE their partial products side by side and one pass sums them in index
       // order and casts -- not fp32 atomics into a cleared buffer: the order atomics land in changes from run to run, the bf16 rounding
@@ -1386,7 +1441,9 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       // in their last bits).
       // (bf16: reduce over the padded vocabulary Vp = multiple of 64 so that both operands qualify for direct-to-LDS copies;
       //  dlogits columns V..Vp are exact zeros and the rows "E[V..Vp)" are the finite first rows of the next tensor in the arena)
-      const int Kv = sizeof(T) == 2 ? e->Vp : c.vocab_size;
+      // (restricted head: the same block over K = Nup -- the rows [Nu, Nup) of E_U and the columns [Nu, Nup) of dlogits_U are exact zeros)
+      const int Kv = hd ? e->il.Nup : sizeof(T) == 2 ? e->Vp : c.vocab_size;
+      const void* hd_B = hd ? (const void*)e->il.EU : (const void*)Wc<T>(e, e->off_E);
       const bool big = Kv >= 16384 || (long)((Md + 127) / 128) * ((d + 127) / 128) >= 512;      // (launch_gemm's tile choice for this problem)
       const long tiles = big ? (long)((Md + 127) / 128) * ((d + 127) / 128) : (long)((Md + 63) / 64) * ((d + 63) / 64);
       const int nst = (Kv + 2 * TT<T>::KCH - 1) / (2 * TT<T>::KCH);         // K-steps of the 128x128 / 64x64 kernels (two K-chunks each)
@@ -1397,7 +1454,7 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       {
         P5GemmArgs g;
         memset(&g, 0, sizeof(g));
-        g.A = e->dlogits; g.B = Wc<T>(e, e->off_E); g.C = e->dres_b; g.M = Md; g.N = d; g.K = Kv; g.lda = e->Vp; g.ldb = d; g.ldc = d;
+        g.A = hd_dl; g.B = hd_B; g.C = e->dres_b; g.M = Md; g.N = d; g.K = Kv; g.lda = hd_ld; g.ldb = d; g.ldc = d;
         g.a_ks = 0; g.b_ks = 1; g.epi = P5_EPI_ATOMIC; g.c_f32 = 1; g.splitk = want; g.alpha = alpha; g.drop = no_drop();
         g.rowss_invd = 1.0f / (float)Kv; g.c_split_stride = (long long)Md * d;
         P5_TRY(launch_gemm<T>(g, s));
@@ -3620,6 +3677,7 @@ int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_
 int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes, const uint32_t* excluded_nodes,
                            int excluded_words, float temperature, int* row_state_out) {
   e->il_next.on = false;
+  e->il_next.head = false;        // (the restricted head is armed behind this call, every time: p5_train_set_item_head)
   P5_REQUIRE(child_off && child_tok && child_node && n_nodes >= 1, "item loss: trie (child_off / child_tok / child_node, n_nodes >= 1)");
   P5_REQUIRE(temperature > 0.f && temperature < __builtin_huge_valf(), "item loss: temperature > 0");
   P5_REQUIRE(excluded_words >= 0 && (excluded_nodes || excluded_words == 0), "item loss: excluded_nodes / excluded_words");
@@ -3641,6 +3699,26 @@ int p5_train_set_item_loss_truncated(P5Engine* e, const int* child_off, const in
   e->il_next.trunc = top_k > 0 || top_p < 1.f;          // (off: the plain kernels, bit for bit; row_cut is not written then)
   e->il_next.tc = P5TruncCe{top_k, top_p};
   e->il_next.row_cut = row_cut;
+  return 0;
+}
+size_t p5_item_head_workspace_bytes(const P5Engine* e, int B, int T, int n_tokens) {
+  if (B < 1 || T < 1 || n_tokens < 1) return 0;
+  return item_head_layout(e, nullptr, (size_t)B * T, ((size_t)n_tokens + 63) / 64 * 64, nullptr);
+}
+int p5_train_set_item_head(P5Engine* e, const int* head_tokens, int n_tokens, const int* child_col, void* ws, size_t ws_bytes) {
+  e->il_next.head = false;
+  e->il_next.tr.col = nullptr;
+  P5_REQUIRE(e->il_next.on, "item head: no item loss is armed (call p5_train_set_item_loss / _truncated first)");
+  P5_REQUIRE(n_tokens >= 1 && n_tokens <= e->c.vocab_size, "item head: n_tokens must lie in [1, vocab_size]");
+  P5_REQUIRE(head_tokens && child_col && ws, "item head: head_tokens / child_col / ws");
+  P5_REQUIRE(((uintptr_t)ws % 256) == 0, "item head: workspace must be 256-byte aligned");
+  // (the forward knows the batch and checks the exact size; this is the part that does not depend on it)
+  P5_REQUIRE(ws_bytes >= p5_item_head_workspace_bytes(e, 1, 1, n_tokens), "item head: workspace too small (p5_item_head_workspace_bytes)");
+  P5Engine::ItemLoss& h = e->il_next;
+  h.head_tok = head_tokens; h.Nu = n_tokens; h.Nup = (n_tokens + 63) / 64 * 64;
+  h.head_ws = ws; h.head_ws_bytes = ws_bytes;
+  h.tr.col = child_col;
+  h.head = true;
   return 0;
 }
 int p5_backward_num_stages(const P5Engine* e) { return e->c.n_dec_layers + e->c.n_enc_layers + 4; }
@@ -4511,28 +4589,44 @@ int p5_op_trie_walk(int* node, int* state, const int64_t* labels, const int* chi
   P5_LAUNCH(p5_trie_walk_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, node, state, (int*)nullptr, labels, tr, T, start_id, eos_id);
   return P5_KCHECK();
 }
-int p5_op_trie_ce_fwd(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
-                      const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
-                      int rows, int T, int ldl, void* stream) {
+// (child_col: the compact row of the restricted item head, p5_op_*_cols below; nullptr = the dense row, column = token)
+static int op_trie_ce_fwd(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
+                          const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded, int excl_words,
+                          float temperature, int rows, int T, int ldl, void* stream) {
   P5_REQUIRE(nll && lse && logits && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0 && ldl >= 1, "trie_ce_fwd: arguments");
   P5TrieCe tr;
   P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  tr.col = child_col;
   if (dtype == 1) P5_LAUNCH((p5_trie_ce_fwd_kernel<bf16>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, node, state, tr, T, ldl);
   else P5_LAUNCH((p5_trie_ce_fwd_kernel<float>), dim3(rows), dim3(256), 0, (hipStream_t)stream, nll, lse, logits, labels, node, state, tr, T, ldl);
   return P5_KCHECK();
 }
-int p5_op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
-                      const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words,
-                      float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream) {
+int p5_op_trie_ce_fwd(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
+                      const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
+                      int rows, int T, int ldl, void* stream) {
+  return op_trie_ce_fwd(dtype, nll, lse, logits, labels, node, state, child_off, child_tok, child_node, nullptr, excluded, excl_words, temperature, rows, T,
+                        ldl, stream);
+}
+static int op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
+                          const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                          const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
+                          float gscale, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   P5_REQUIRE(dlogits && logits && lse && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0, "trie_ce_bwd: arguments");
   P5_REQUIRE(ldl >= 1 && ldd >= 1 && ldd % 8 == 0, "trie_ce_bwd: ldd a multiple of 8");
   P5_REQUIRE(dnll || out_attn, "trie_ce_bwd: dnll, or out_attn [rows / T, T]");
   P5TrieCe tr;
   P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  tr.col = child_col;
   if (dtype == 1) P5_LAUNCH((p5_trie_ce_bwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, (bf16*)dlogits, logits, lse, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   else P5_LAUNCH((p5_trie_ce_bwd_kernel<float>), dim3(rows), dim3(256), 0, s, (float*)dlogits, logits, lse, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   return P5_KCHECK();
+}
+int p5_op_trie_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
+                      const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words,
+                      float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream) {
+  return op_trie_ce_bwd(dtype, dlogits, logits, lse, labels, node, state, dnll, child_off, child_tok, child_node, nullptr, excluded, excl_words, temperature,
+                        rows, T, ldl, ldd, out_attn, gscale, stream);
 }
 static int trunc_ce_args(P5TruncCe* tc, int top_k, float top_p) {
   P5_REQUIRE(top_k >= 0, "trunc: top_k >= 0 (0 = off)");
@@ -4551,31 +4645,92 @@ int p5_op_trunc_cut(float* cut, int* kept, const float* logits, const int* node,
   P5_LAUNCH(p5_trunc_cut_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, cut, kept, logits, node, tr, tc, rows_per_user, ldl);
   return P5_KCHECK();
 }
-int p5_op_trunc_ce_fwd(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
-                       const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
-                       int top_k, float top_p, int rows, int T, int ldl, void* stream) {
+static int op_trunc_ce_fwd(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
+                           const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded,
+                           int excl_words, float temperature, int top_k, float top_p, int rows, int T, int ldl, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   P5_REQUIRE(nll && lse && row_cut && state && logits && labels && node && rows >= 1 && T >= 1 && rows % T == 0 && ldl >= 1, "trunc_ce_fwd: arguments");
   P5TrieCe tr;
   P5TruncCe tc;
   P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  tr.col = child_col;
   P5_TRY(trunc_ce_args(&tc, top_k, top_p));
   if (dtype == 1) P5_LAUNCH((p5_trunc_ce_fwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, nll, lse, row_cut, state, (int*)nullptr, logits, labels, node, tr, tc, T, ldl);
   else P5_LAUNCH((p5_trunc_ce_fwd_kernel<float>), dim3(rows), dim3(256), 0, s, nll, lse, row_cut, state, (int*)nullptr, logits, labels, node, tr, tc, T, ldl);
   return P5_KCHECK();
 }
-int p5_op_trunc_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
-                       const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded,
-                       int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream) {
+int p5_op_trunc_ce_fwd(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
+                       const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded, int excl_words, float temperature,
+                       int top_k, float top_p, int rows, int T, int ldl, void* stream) {
+  return op_trunc_ce_fwd(dtype, nll, lse, row_cut, state, logits, labels, node, child_off, child_tok, child_node, nullptr, excluded, excl_words, temperature,
+                         top_k, top_p, rows, T, ldl, stream);
+}
+static int op_trunc_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
+                           const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                           const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
+                           float gscale, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   P5_REQUIRE(dlogits && logits && lse && row_cut && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0, "trunc_ce_bwd: arguments");
   P5_REQUIRE(ldl >= 1 && ldd >= 1 && ldd % 8 == 0, "trunc_ce_bwd: ldd a multiple of 8");
   P5_REQUIRE(dnll || out_attn, "trunc_ce_bwd: dnll, or out_attn [rows / T, T]");
   P5TrieCe tr;
   P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  tr.col = child_col;
   if (dtype == 1) P5_LAUNCH((p5_trunc_ce_bwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, (bf16*)dlogits, logits, lse, row_cut, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   else P5_LAUNCH((p5_trunc_ce_bwd_kernel<float>), dim3(rows), dim3(256), 0, s, (float*)dlogits, logits, lse, row_cut, labels, node, state, dnll, tr, ldl, ldd, out_attn, T, gscale);
   return P5_KCHECK();
+}
+int p5_op_trunc_ce_bwd(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
+                       const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const uint32_t* excluded,
+                       int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn, float gscale, void* stream) {
+  return op_trunc_ce_bwd(dtype, dlogits, logits, lse, row_cut, labels, node, state, dnll, child_off, child_tok, child_node, nullptr, excluded, excl_words,
+                         temperature, rows, T, ldl, ldd, out_attn, gscale, stream);
+}
+// ---- the restricted item head (p5_item_head.h), kernel by kernel ----
+int p5_op_item_gather(int dtype, void* EU, const void* E, const int* tokens, int n_tokens, int d, void* stream) {
+  P5_REQUIRE(EU && E && tokens && n_tokens >= 1 && d >= 1, "item_gather: arguments");
+  P5_REQUIRE(d % (dtype == 1 ? 8 : 4) == 0 && ((uintptr_t)EU % 16) == 0 && ((uintptr_t)E % 16) == 0, "item_gather: rows of whole 16-byte pieces, 16-byte aligned");
+  const int Nup = (n_tokens + 63) / 64 * 64;
+  if (dtype == 1) P5_LAUNCH((p5_item_gather_kernel<bf16>), dim3(item_head_blocks((long long)Nup * (d / 8))), dim3(256), 0, (hipStream_t)stream, (bf16*)EU, (const bf16*)E, tokens, n_tokens, Nup, d);
+  else P5_LAUNCH((p5_item_gather_kernel<float>), dim3(item_head_blocks((long long)Nup * (d / 4))), dim3(256), 0, (hipStream_t)stream, (float*)EU, (const float*)E, tokens, n_tokens, Nup, d);
+  return P5_KCHECK();
+}
+int p5_op_item_scatter(float* dE, const float* dEU, const int* tokens, int n_tokens, int V, int d, int store, void* stream) {
+  P5_REQUIRE(dE && dEU && tokens && n_tokens >= 1 && n_tokens <= V && d >= 1, "item_scatter: arguments");
+  P5_REQUIRE(d % 4 == 0 && ((uintptr_t)dE % 16) == 0 && ((uintptr_t)dEU % 16) == 0, "item_scatter: rows of whole 16-byte pieces, 16-byte aligned");
+  P5_LAUNCH(p5_item_scatter_kernel, dim3(item_head_blocks((long long)(store ? V : n_tokens) * (d / 4))), dim3(256), 0, (hipStream_t)stream, dE, dEU, tokens, n_tokens,
+            V, d, store ? 1 : 0);
+  return P5_KCHECK();
+}
+int p5_op_trie_ce_fwd_cols(int dtype, float* nll, float* lse, const float* logits, const int64_t* labels, const int* node, const int* state,
+                           const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded, int excl_words,
+                           float temperature, int rows, int T, int ldl, void* stream) {
+  P5_REQUIRE(child_col, "trie_ce_fwd_cols: child_col");
+  return op_trie_ce_fwd(dtype, nll, lse, logits, labels, node, state, child_off, child_tok, child_node, child_col, excluded, excl_words, temperature, rows, T,
+                        ldl, stream);
+}
+int p5_op_trie_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const float* lse, const int64_t* labels, const int* node, const int* state,
+                           const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                           const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
+                           float gscale, void* stream) {
+  P5_REQUIRE(child_col, "trie_ce_bwd_cols: child_col");
+  return op_trie_ce_bwd(dtype, dlogits, logits, lse, labels, node, state, dnll, child_off, child_tok, child_node, child_col, excluded, excl_words, temperature,
+                        rows, T, ldl, ldd, out_attn, gscale, stream);
+}
+int p5_op_trunc_ce_fwd_cols(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
+                            const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded,
+                            int excl_words, float temperature, int top_k, float top_p, int rows, int T, int ldl, void* stream) {
+  P5_REQUIRE(child_col, "trunc_ce_fwd_cols: child_col");
+  return op_trunc_ce_fwd(dtype, nll, lse, row_cut, state, logits, labels, node, child_off, child_tok, child_node, child_col, excluded, excl_words, temperature,
+                         top_k, top_p, rows, T, ldl, stream);
+}
+int p5_op_trunc_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const float* lse, const float* row_cut, const int64_t* labels, const int* node,
+                            const int* state, const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                            const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
+                            float gscale, void* stream) {
+  P5_REQUIRE(child_col, "trunc_ce_bwd_cols: child_col");
+  return op_trunc_ce_bwd(dtype, dlogits, logits, lse, row_cut, labels, node, state, dnll, child_off, child_tok, child_node, child_col, excluded, excl_words,
+                         temperature, rows, T, ldl, ldd, out_attn, gscale, stream);
 }
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream) {
   P5_REQUIRE(loss && nll && out_attn && B >= 1 && T >= 1, "masked_mean: arguments");

@@ -12,6 +12,11 @@
 //   p5_trie_ce_bwd_kernel   the DENSE dlogits row: zero everywhere except g * (exp(z - lse) - [child == label]) / tau at the allowed children, so
 //                           that the tied head's weight gradient and its split-K input gradient run unchanged behind it
 // Every value has one writer and every reduction a fixed order: no atomics, two runs return the same bits.
+// P5TrieCe::col (optional, one int per CSR edge): the head restricted to the trie's tokens (p5_item_head.h).  The logits row and the dlogits row
+// are then COMPACT -- [rows, Nup] over the sorted distinct tokens of the trie -- and a child's logit / gradient sits at column col[edge] instead of
+// column child_tok[edge].  Nothing else changes: labels, the walk and the exclusion bitmap stay on tokens and nodes, the arithmetic per child
+// and the order of reduction are the same, so on equal logits nll, lse and the entries of dlogits are equal bit for bit.  nullptr = the dense row.
+// Not there, either way: per-user roots; exclusion on a grafted trie (the Python layer raises).
 #pragma once
 #include "p5_elem.h"
 
@@ -23,6 +28,7 @@ struct P5TrieCe {
   const int* child_off; const int* child_tok; const int* child_node;
   const uint32_t* excluded; int excl_words;      // [B, excl_words] bitmap over trie nodes, or nullptr
   float tau;
+  const int* col;      // [n_edges] column of an edge's token in a compact logits row (p5_item_head.h), or nullptr: column = token
 };
 
 // one workgroup per sample: the positions are walked in order, the 256 threads look the label up among the node's children.
@@ -105,7 +111,7 @@ __global__ __launch_bounds__(256) void p5_trie_ce_fwd_kernel(float* __restrict__
       if ((ex[cn >> 5] >> (cn & 31)) & 1u) continue;
     }
     const int tok = tr.child_tok[c0 + i];
-    const float z = lr[tok] / tr.tau;
+    const float z = lr[tr.col ? tr.col[c0 + i] : tok] / tr.tau;
     if ((int64_t)tok == lab) s_zl = z;      // (the walk found the label among the allowed children: exactly one thread)
     if (z == P5_NEG_INF) continue;          // a masked logit adds nothing; while m is still -inf, exp(-inf - m) would be NaN and stay in s
     if (z > m) { s *= p5_exp<T>(m - z); m = z; }
@@ -163,7 +169,8 @@ __global__ __launch_bounds__(256) void p5_trie_ce_bwd_kernel(T* __restrict__ dlo
       if ((ex[cn >> 5] >> (cn & 31)) & 1u) continue;
     }
     const int tok = tr.child_tok[c0 + i];
-    const float z = lr[tok] / tr.tau;
-    dr[tok] = from_f<T>(g * (p5_exp<T>(z - l) - ((int64_t)tok == lab ? 1.f : 0.f)) / tr.tau);
+    const int col = tr.col ? tr.col[c0 + i] : tok;
+    const float z = lr[col] / tr.tau;
+    dr[col] = from_f<T>(g * (p5_exp<T>(z - l) - ((int64_t)tok == lab ? 1.f : 0.f)) / tr.tau);
   }
 }

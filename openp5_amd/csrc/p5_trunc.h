@@ -252,12 +252,13 @@ struct P5TruncCe { int top_k; float top_p; };
 // the z of child i of a row of the materialised logits: -inf for an excluded child
 struct P5TruncGather {
   const float* lr; const int* tok; const int* cnode; const uint32_t* ex; float tau;
+  const int* col;      // P5TrieCe::col at the node's first edge, or nullptr: column = token
   __device__ __forceinline__ float operator()(int i) const {
     if (ex) {
       const int cn = cnode[i];
       if ((ex[cn >> 5] >> (cn & 31)) & 1u) return P5_NEG_INF;
     }
-    return lr[tok[i]] / tau;
+    return lr[col ? col[i] : tok[i]] / tau;
   }
 };
 
@@ -284,7 +285,8 @@ __global__ __launch_bounds__(256) void p5_trunc_cut_kernel(float* __restrict__ c
   }
   const int c0 = tr.child_off[nd], nc = tr.child_off[nd + 1] - c0;
   const P5TruncGather g{logits + (size_t)row * ldl, tr.child_tok + c0, tr.child_node + c0,
-                        tr.excluded ? tr.excluded + (size_t)(row / rows_per_user) * tr.excl_words : nullptr, tr.tau};
+                        tr.excluded ? tr.excluded + (size_t)(row / rows_per_user) * tr.excl_words : nullptr, tr.tau,
+                        tr.col ? tr.col + c0 : nullptr};
   int n = 0;
   const float c = p5_trunc_row_cut(g, nc, tc.top_k, tc.top_p, L, &n);
   if (threadIdx.x == 0) { cut[row] = c; kept[row] = n; }
@@ -308,7 +310,8 @@ __global__ __launch_bounds__(256) void p5_trunc_ce_fwd_kernel(float* __restrict_
   const int nd = node[row];
   const int c0 = tr.child_off[nd], nc = tr.child_off[nd + 1] - c0;
   const P5TruncGather g{logits + (size_t)row * ldl, tr.child_tok + c0, tr.child_node + c0,
-                        tr.excluded ? tr.excluded + (size_t)(row / Tlen) * tr.excl_words : nullptr, tr.tau};
+                        tr.excluded ? tr.excluded + (size_t)(row / Tlen) * tr.excl_words : nullptr, tr.tau,
+                        tr.col ? tr.col + c0 : nullptr};
   const float cut = p5_trunc_row_cut(g, nc, tc.top_k, tc.top_p, L, nullptr);
   const bool staged = nc <= P5_TRUNC_STAGE;
   const int64_t lab = labels[row];
@@ -378,8 +381,9 @@ __global__ __launch_bounds__(256) void p5_trunc_ce_bwd_kernel(T* __restrict__ dl
       if ((ex[cn >> 5] >> (cn & 31)) & 1u) continue;
     }
     const int tok = tr.child_tok[c0 + i];
-    const float z = lr[tok] / tr.tau;
+    const int col = tr.col ? tr.col[c0 + i] : tok;
+    const float z = lr[col] / tr.tau;
     if (z == P5_NEG_INF || !(z >= cut)) continue;
-    dr[tok] = from_f<T>(g * (p5_exp<T>(z - l) - ((int64_t)tok == lab ? 1.f : 0.f)) / tr.tau);
+    dr[col] = from_f<T>(g * (p5_exp<T>(z - l) - ((int64_t)tok == lab ? 1.f : 0.f)) / tr.tau);
   }
 }

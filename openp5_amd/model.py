@@ -158,6 +158,9 @@ class P5T5Native(nn.Module):
     wide_max_rows = 4096          # a wide search (K > 64) runs over at most this many decode rows (users x beams) per call: larger batches go in user
                                   # chunks (the step KV cache alone is n_dec_layers x max_len x rows x 2 x inner x sizeof(T): ~3 GiB for fp32
                                   # T5-small at max_len 30)
+    # head of the trie-normalised item loss (forward(trie=...)): "dense" = over the whole vocabulary; "trie" = over the distinct tokens of the
+    # trie's edges only (csrc/p5_item_head.h: no [B*T, V] logits, the tied head's three GEMMs shrink to the trie's token set)
+    item_head = "dense"
 
     def __init__(self, config, dtype: str = "bf16", device=None, backend=None, seed: int = 2023):
         super().__init__()
@@ -524,9 +527,19 @@ class P5T5Native(nn.Module):
             raise ValueError(f"top_p={top_p!r}: 0 < top_p <= 1 (1 = no nucleus truncation)")
         return min(int(top_k), 2 ** 31 - 1), p
 
-    def _item_loss_setup(self, trie, temperature, excluded_items, B, top_k=0, top_p=1.0):
+    def _item_head_mode(self, item_head, trie):
+        """`item_head` of forward / loss_and_backward: None = the model's `item_head` attribute (which a call without a trie ignores)."""
+        if item_head is not None and trie is None and item_head == "trie":
+            raise ValueError('item_head="trie" needs trie=...: the restricted head belongs to the trie-normalised item loss')
+        mode = self.item_head if item_head is None else item_head
+        if mode not in ("dense", "trie"):
+            raise ValueError(f'item_head={mode!r}: "dense" (the head over the vocabulary) or "trie" (over the tokens of the trie)')
+        return mode
+
+    def _item_loss_setup(self, trie, temperature, excluded_items, B, top_k=0, top_p=1.0, item_head="dense"):
         """The checked setting of the trie-normalised item loss (csrc/p5_trie_ce.h) for a batch of B users: the trie on the device, the
-        temperature (the check of `_sampling_setup`), the excluded-node bitmap (the rule of `sample_items`) and the truncation."""
+        temperature (the check of `_sampling_setup`), the excluded-node bitmap (the rule of `sample_items`), the truncation and the head
+        ("trie": the sorted token set of the trie and every edge's column in it, csrc/p5_item_head.h)."""
         dev = self._be.device
         top_k, top_p = self._truncation(top_k, top_p)
         tau = float(temperature)
@@ -549,8 +562,9 @@ class P5T5Native(nn.Module):
             excl_words = int(excl_np.shape[1])
             excl_t = torch.from_numpy(np.ascontiguousarray(excl_np).view(np.int32)).to(dev)
         off, tok, nxt = trie.device_arrays(dev)
+        head_tok, head_col = trie.head_columns_device(dev) if item_head == "trie" else (None, None)
         return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, n_nodes=int(trie.n_nodes), excl_t=excl_t, excl_words=excl_words, top_k=top_k,
-                                     top_p=top_p, row_cut=None)
+                                     top_p=top_p, row_cut=None, head_tok=head_tok, head_col=head_col, head_ws=None)
 
     def _arm_item_loss(self, q, B, T):
         """p5_train_set_item_loss (or its truncated sibling) for the engine's next forward; the rows' states land in `last_item_loss_state`
@@ -564,6 +578,17 @@ class P5T5Native(nn.Module):
         else:
             self._be.check(self._lib.p5_train_set_item_loss(self._engine, _ptr(q.off), _ptr(q.tok), _ptr(q.nxt), q.n_nodes, _ptr(q.excl_t), q.excl_words,
                                                             q.tau, _ptr(state)), "p5_train_set_item_loss")
+        if q.head_tok is not None:
+            # the restricted head's compact buffers: the caller's, like row_cut -- the saved inputs keep them alive until the backward has run
+            n_tok = int(q.head_tok.numel())
+            need = int(self._lib.p5_item_head_workspace_bytes(self._engine, B, T, n_tok))
+            raw = self.__dict__.get("_item_head_raw")       # (one buffer per model, grown on demand: the engine holds one forward at a time)
+            if raw is None or raw.numel() < need + 256:
+                raw = self.__dict__["_item_head_raw"] = torch.empty(need + 256, dtype=torch.uint8, device=self._be.device)
+            skew = (-raw.data_ptr()) % 256
+            q.head_ws = raw[skew:skew + need]
+            self._be.check(self._lib.p5_train_set_item_head(self._engine, _ptr(q.head_tok), n_tok, _ptr(q.head_col), _ptr(q.head_ws), need),
+                           "p5_train_set_item_head")
         self.last_item_loss_state = state
 
     def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels, item_loss=None):
@@ -667,13 +692,14 @@ class P5T5Native(nn.Module):
             self.ddp_wait_ms.append((ev0, ev1))     # (read by bench.py after a synchronize: main-stream time spent waiting for the buckets)
 
     def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None,
-                          top_k=0, top_p=1.0):
+                          top_k=0, top_p=1.0, item_head=None):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
         none of the ~10 elementwise launches of the generic path.  Returns the loss as a 0-dim tensor; gradients are in `.grad`.
         `trie`, `temperature`, `excluded_items`, `top_k`, `top_p`: the trie-normalised item loss, as in `forward` (the masked mean then runs
-        over its NLL)."""
+        over its NLL); `item_head`: "dense" | "trie" | None = `self.item_head`, as in `forward`."""
+        item_head = self._item_head_mode(item_head, trie)
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
         B, L = input_ids.shape
@@ -682,7 +708,7 @@ class P5T5Native(nn.Module):
         labels = self._i64(labels, dev)
         output_attention = self._i64(output_attention, dev)
         T = labels.shape[1]
-        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p)
+        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p, item_head)
         self._sync_shadow()
         self._sync_transposed()
         ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
@@ -704,7 +730,7 @@ class P5T5Native(nn.Module):
         self._rng[1] = self._rng_cpu[1] if self._rng_cpu[1] < 2 ** 31 else self._rng_cpu[1] - 2 ** 32
 
     def forward(self, input_ids=None, whole_word_ids=None, attention_mask=None, labels=None, alpha=None, return_dict=True, trie=None,
-                temperature=1.0, excluded_items=None, top_k=0, top_p=1.0, **unused):
+                temperature=1.0, excluded_items=None, top_k=0, top_p=1.0, item_head=None, **unused):
         """P5_T5.forward (P5_T5.py:275-386): returns {"loss": flat [B*T] per-token NLL}; `alpha` is accepted and ignored
         exactly as in the reference (P5_T5.py:294).
         `trie` (Trie / CompiledTrie; None = the full-vocabulary cross-entropy, unchanged): the trie-normalised item loss (csrc/p5_trie_ce.h),
@@ -718,10 +744,15 @@ class P5T5Native(nn.Module):
         `top_k` (0 = off) / `top_p` (1 = off): the loss of the TRUNCATED distribution `sample_items(top_k=, top_p=)` draws from
         (csrc/p5_trunc.h) -- the normalisation runs over the kept children only and the kept set is a constant of the gradient (HF's
         masked_fill under autograd); a label that is allowed but below the row's cut has NLL 0, no gradient and state 3 (truncated away),
-        for that row only.  The head still runs over the whole vocabulary and the logits gradient is dense, so gradient accumulation
-        (`begin_micro_batch`), DDP and the staged backward work as for the plain loss, unchanged."""
+        for that row only.
+        `item_head` ("dense" | "trie"; None = `self.item_head`, "dense" unless changed): "dense" runs the tied head over the whole vocabulary
+        and writes a dense logits gradient; "trie" (csrc/p5_item_head.h) runs it over the distinct tokens of the trie's edges only -- no
+        [B*T, V] array is written or read, the loss is the same function of the logits, and rows of shared.weight's gradient whose token is
+        neither on the trie nor looked up by the batch are exact zeros.  Gradient accumulation (`begin_micro_batch`), DDP and the staged
+        backward work with either head as for the plain loss."""
         if labels is None:
             raise ValueError("P5T5Native.forward needs labels (the runner always passes them)")
+        item_head = self._item_head_mode(item_head, trie)
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
         if whole_word_ids is None:
@@ -731,7 +762,7 @@ class P5T5Native(nn.Module):
             attention_mask = (input_ids != self.config.pad_token_id).long()
         attention_mask = self._i64(attention_mask, dev)
         labels = self._i64(labels, dev)
-        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], top_k, top_p)
+        item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], top_k, top_p, item_head)
         nll = _P5LossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels, item_loss)
         out = {"loss": nll}
         return out if return_dict else (nll,)

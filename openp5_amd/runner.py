@@ -79,6 +79,9 @@ def parse_runner_args(parser):
                         "sample_items(top_k=...) draws from (0 = off)")
     parser.add_argument("--item_loss_top_p", type=float, default=1.0, help="nucleus truncation of --train_item_loss 1 (sample_items(top_p=...)); "
                         "1.0 = off")
+    parser.add_argument("--item_loss_head", type=str, default="dense", choices=["dense", "trie"], help="head of --train_item_loss 1: dense = the "
+                        "tied head over the whole vocabulary; trie = over the distinct tokens of the item trie only (the same loss, no [B*T, V] "
+                        "logits; P5T5Native.forward(item_head=...))")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -424,6 +427,8 @@ class DistributedRunner:
             top_k, top_p = int(getattr(self.args, "item_loss_top_k", 0)), float(getattr(self.args, "item_loss_top_p", 1.0))
             if top_k != 0 or top_p != 1.0:          # (off: the keyword arguments of the untruncated loss, as before)
                 kw.update(top_k=top_k, top_p=top_p)
+            if str(getattr(self.args, "item_loss_head", "dense")) == "trie":      # (dense: the keyword arguments of the run without the flag)
+                kw["item_head"] = "trie"
         return kw
 
     @torch.no_grad()

@@ -404,6 +404,23 @@ class CompiledTrie:
             self._dev[key] = tuple(torch.from_numpy(a).to(device) for a in (self.child_off, self.child_tok, self.child_node))
         return self._dev[key]
 
+    def head_columns(self):
+        """(tokens int32 [Nu], child_col int32 [n_edges]): the distinct tokens on the trie's edges in ascending order, and for every CSR edge
+        the index of its token in that list -- the columns of a head restricted to the trie's tokens (csrc/p5_item_head.h).  Cached."""
+        hc = self.__dict__.get("_head_cols")
+        if hc is None:
+            tokens, col = np.unique(self.child_tok, return_inverse=True)
+            hc = self._head_cols = (np.ascontiguousarray(tokens, dtype=np.int32), np.ascontiguousarray(col.reshape(-1), dtype=np.int32))
+        return hc
+
+    def head_columns_device(self, device):
+        """`head_columns()` on `device`, cached per device next to `device_arrays`."""
+        import torch
+        key = ("head", str(device))
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(a).to(device) for a in self.head_columns())
+        return self._dev[key]
+
 
 def find_trie(fn):
     """Recover the Trie behind a prefix_allowed_tokens_fn: ours (`.candidate_trie`) or the reference's closure

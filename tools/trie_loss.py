@@ -3,12 +3,15 @@ items of the benchmark's 3,416-item trie) three ways in one process --
   plain          the default step: full-vocabulary cross-entropy on the logit-free head
   plain_ce_free0 the same loss with option "ce_free" 0: materialised fp32 logits, p5_ce_fwd_kernel / p5_ce_bwd_kernel
   item_loss      training_step(..., item_loss={"trie": ...}): materialised logits, p5_trie_walk / p5_trie_ce_fwd / p5_trie_ce_bwd
+  item_loss_trie_head   (with --item_head trie or both) the same loss on the head restricted to the trie's tokens (csrc/p5_item_head.h): the
+                 rows U of the head weight gathered, logits_U [B*T, Nup], one scatter of dE_U into shared.weight's gradient
 alternated window by window, so that a drift of the machine lands on all three; one JSON line per variant: ms per step (median and spread
 over the rounds), its ratio to the plain step of the same run, and the device ms of one step by kernel family (in-run profiler,
 p5_profile_begin / end: each launch's time includes its dispatch gap).
-Nothing is gated on the item-loss step.  The expectation, stated as such: it lands at the ce_free 0 time -- the same route with a cheaper
-forward reduction.
-python tools/trie_loss.py [--batch 64] [--dtype bf16] [--rounds 7] [--min_seconds 0.5] [--temperature 1.0] [--tag NAME] [--out profiles/trie_loss.jsonl]"""
+Nothing is gated on the item-loss step.  The yardstick of the restricted head is the dense item-loss step of the same call
+(`over_item_loss`, with that step's own spread in `step_ms_min_max`).
+python tools/trie_loss.py [--batch 64] [--dtype bf16] [--rounds 7] [--min_seconds 0.5] [--temperature 1.0] [--item_head dense|trie|both] [--tag NAME]
+                          [--out profiles/trie_loss.jsonl]"""
 import argparse
 import ctypes
 import json
@@ -24,6 +27,7 @@ ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--min_seconds", type=float, default=0.5)
 ap.add_argument("--temperature", type=float, default=1.0)
+ap.add_argument("--item_head", default="both", choices=["dense", "trie", "both"], help="which item-loss steps run beside the plain ones")
 ap.add_argument("--tag", default="this")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--out", default=None)
@@ -38,7 +42,7 @@ from openp5_amd.runner import training_step  # noqa: E402
 from openp5_amd.trie import CompiledTrie  # noqa: E402
 
 # family <- kernel name prefixes
-PARTS = (("loss", ("p5_trie_", "p5_ce_", "p5_masked_mean")), ("attention", ("p5_attn",)), ("gemm", ("p5_gemm", "p5_g4", "p5_g5")),
+PARTS = (("loss", ("p5_trie_", "p5_ce_", "p5_masked_mean", "p5_item_")), ("attention", ("p5_attn",)), ("gemm", ("p5_gemm", "p5_g4", "p5_g5")),
          ("optimizer", ("p5_adamw", "p5_sumsq")), ("embedding", ("p5_embed",)))
 
 
@@ -105,7 +109,11 @@ def main(a):
             finally:
                 lib.p5_set_option(b"ce_free", 1)
         return step
-    steps = {"plain": variant(1, None), "plain_ce_free0": variant(0, None), "item_loss": variant(1, kw)}
+    steps = {"plain": variant(1, None), "plain_ce_free0": variant(0, None)}
+    if a.item_head in ("dense", "both"):
+        steps["item_loss"] = variant(1, {**kw, "item_head": "dense"})
+    if a.item_head in ("trie", "both"):
+        steps["item_loss_trie_head"] = variant(1, {**kw, "item_head": "trie"})
     for _ in range(5):          # warm-up: workspaces, code objects, the trie on the device
         for fn in steps.values():
             fn()
@@ -121,9 +129,10 @@ def main(a):
     lines = []
     for k, fn in steps.items():
         line = {"tag": a.tag, "what": "trie_loss", "variant": k, "dtype": a.dtype, "backbone": "t5-small", "B": B, "L": L, "T": T, "dropout": 0.1,
-                "n_items": 3416, "temperature": a.temperature if k == "item_loss" else None, "rounds": a.rounds, "loss": round(loss[k], 5),
+                "n_items": 3416, "temperature": a.temperature if k.startswith("item_loss") else None,
+                "item_head": {"item_loss": "dense", "item_loss_trie_head": "trie"}.get(k), "head_columns": len(ct.head_columns()[0]) if k == "item_loss_trie_head" else None, "rounds": a.rounds, "loss": round(loss[k], 5),
                 "step_ms": round(med[k], 4), "step_ms_min_max": [round(min(t[k]), 4), round(max(t[k]), 4)],
-                "over_plain": round(med[k] / med["plain"], 4), "step_ms_by_family": profile_split(lib, lambda: (fn(), torch.cuda.synchronize()))}
+                "over_plain": round(med[k] / med["plain"], 4), "over_item_loss": round(med[k] / med["item_loss"], 4) if "item_loss" in med else None, "step_ms_by_family": profile_split(lib, lambda: (fn(), torch.cuda.synchronize()))}
         lines.append(line)
         print(json.dumps(line), flush=True)
     if a.out:
