@@ -106,6 +106,28 @@ int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_
 int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask,
                     const int64_t* labels, const int64_t* output_attention /* [B,T] */, int B, int L, int T, int training,
                     float* nll_out /* [B*T] */, float* loss_out /* [1] */, void* ws, int64_t ws_bytes, void* stream);
+/* ---- several targets per user with ONE encoder pass ----
+ * labels [B, G, T] (flat [B*G*T], (b, g, t) order): what the three calls above compute for the replicated batch -- user b's inputs repeated G
+ * times, sample b*G + g carrying labels[b, g] -- but the encoder and the projection of its output to every decoder layer's cross-attention K/V
+ * run once per user; the decoder is a batch of B*G sequences, cross-attention runs a user's G*T queries against that user's keys, and the
+ * gradients into the encoder output, the encoder and the K/V weights are the sums over a user's G targets.  nll_out: fp32 [B*G*T].  With dropout
+ * on, the masks follow the engine's site / flat-index rule on the tensors actually formed (encoder: batch B; decoder rows: [B*G*T, .]; self
+ * attention: [B*G, H, T, T]; cross attention: [B, H, G*T, L]).  G = 1 is the plain call, bit for bit (the plain calls ARE these with G = 1 and
+ * NULL weights).  Limits: G >= 1; for G > 1, G*T <= 512 (the attention kernels' query limit) and B*G*T <= 65536 (the norm-backward
+ * epilogue's partial table: 1024 blocks of 64 rows) and B*G*n_heads <= 65535 (the y extent of the self-attention launch grids).  p5_backward / p5_backward_stage / p5_backward_staged follow as usual.
+ * The one-shot item-loss calls compose as with the plain calls: excluded_nodes stays [B, excluded_words] (per USER, applied to all G targets),
+ * row_state_out / row_cut are [B*G*T], and p5_item_head_workspace_bytes(e, B, T, n) is called with B*G in the place of B.
+ * p5_forward_loss_targets: output_attention [B, G, T]; target_weights DEVICE fp32 [B*G] or NULL (= all ones; may be negative or zero);
+ *   loss_out[0] = sum_{b,g} w[b,g] * (sum_t nll*m / max(sum_t m, 1)) / (B*G),
+ * and the backward with dnll == NULL is seeded with its gradient.  target_weights must stay valid until the backward has run. */
+int64_t p5_train_workspace_bytes_targets(const P5Engine* e, int B, int L, int T, int G);
+int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask,
+                       const int64_t* labels /* [B,G,T] */, int B, int L, int T, int G, int training, float* nll_out /* [B*G*T] */, void* ws,
+                       int64_t ws_bytes, void* stream);
+int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask,
+                            const int64_t* labels /* [B,G,T] */, const int64_t* output_attention /* [B,G,T] */, int B, int L, int T, int G,
+                            const float* target_weights /* DEVICE [B*G] or NULL */, int training, float* nll_out /* [B*G*T] */,
+                            float* loss_out /* [1] */, void* ws, int64_t ws_bytes, void* stream);
 /* stages: 0 = head + decoder-final, 1..n_dec = decoder layers (top first), then decoder embedding,
  * then encoder-final + encoder layers (top first), last = encoder embedding.  p5_backward runs them all. */
 /* ---- trie-normalised item loss: the training loss of the distribution p5_sample_items / p5_sample_slates draw from (openp5_amd/csrc/p5_trie_ce.h) ----

@@ -46,6 +46,9 @@ PROTOTYPES = {
     "p5_train_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "p5_forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
     "p5_forward_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
+    "p5_train_workspace_bytes_targets": (i64, [vp, i32, i32, i32, i32]),
+    "p5_forward_targets": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "p5_forward_loss_targets": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp]),
     "p5_train_set_item_loss": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp]),
     "p5_train_set_item_loss_truncated": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp, i32, f32, vp]),
     "p5_item_head_workspace_bytes": (C.c_size_t, [vp, i32, i32, i32]),

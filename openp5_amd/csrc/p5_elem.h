@@ -488,8 +488,10 @@ __global__ __launch_bounds__(256) void p5_ce_finish_kernel(float* __restrict__ n
   }
 }
 // g[row] = gradient of the row's NLL: dnll[row] (autograd), or the runner's masked-mean loss (p5_ce_bwd_kernel's rule), 0 for ignored labels
+// tw: optional weight per sample (row / Tlen) of the seeded loss -- several targets per user (p5_forward_loss_targets) -- or nullptr = 1
 __global__ __launch_bounds__(256) void p5_ce_gscale_kernel(float* __restrict__ g_out, const int64_t* __restrict__ labels, const float* __restrict__ dnll,
-                                                          const int64_t* __restrict__ out_attn, int Tlen, float gscale, int rows) {
+                                                          const int64_t* __restrict__ out_attn, int Tlen, float gscale, int rows,
+                                                          const float* __restrict__ tw = nullptr) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
   float g;
@@ -500,6 +502,7 @@ __global__ __launch_bounds__(256) void p5_ce_gscale_kernel(float* __restrict__ g
     float cnt = 0.f;
     for (int t = 0; t < Tlen; ++t) cnt += out_attn[(size_t)b * Tlen + t] != 0 ? 1.f : 0.f;
     g = out_attn[row] != 0 ? gscale / fmaxf(cnt, 1.f) : 0.f;
+    if (tw) g *= tw[b];
   }
   if (labels[row] == -100) g = 0.f;
   g_out[row] = g;
@@ -508,8 +511,10 @@ __global__ __launch_bounds__(256) void p5_ce_gscale_kernel(float* __restrict__ g
 // Runner loss behind the CE kernel (DistributedRunner.py:72-77):
 //   loss = mean_b( sum_t nll[b,t] * m[b,t] / max(sum_t m[b,t], 1) ),  m = (output_attention != 0)
 // one workgroup, fixed summation order (deterministic): thread i owns batch rows i, i+256, ...
+// tw: optional weight per batch row (the B x G targets of p5_forward_loss_targets: mean_b(w[b] * ...)), or nullptr = 1
 __global__ __launch_bounds__(256) void p5_masked_mean_kernel(float* __restrict__ loss, const float* __restrict__ nll,
-                                                            const int64_t* __restrict__ out_attn, int B, int T) {
+                                                            const int64_t* __restrict__ out_attn, int B, int T,
+                                                            const float* __restrict__ tw = nullptr) {
   __shared__ float sred[4];
   float s = 0.f;
   for (int b = threadIdx.x; b < B; b += 256) {
@@ -519,7 +524,9 @@ __global__ __launch_bounds__(256) void p5_masked_mean_kernel(float* __restrict__
       num += nll[(size_t)b * T + t] * m;
       cnt += m;
     }
-    s += num / fmaxf(cnt, 1.f);
+    float r = num / fmaxf(cnt, 1.f);
+    if (tw) r *= tw[b];
+    s += r;
   }
   s = block_reduce(s, false, sred);
   if (threadIdx.x == 0) loss[0] = s / (float)B;
@@ -532,7 +539,8 @@ template <class T>
 __global__ __launch_bounds__(256) void p5_ce_bwd_kernel(T* __restrict__ dlogits, const float* __restrict__ logits,
                                                        const float* __restrict__ lse, const int64_t* __restrict__ labels,
                                                        const float* __restrict__ dnll, int V, int ldl, int ldd,
-                                                       const int64_t* __restrict__ out_attn, int Tlen, float gscale) {
+                                                       const int64_t* __restrict__ out_attn, int Tlen, float gscale,
+                                                       const float* __restrict__ tw = nullptr) {
   // grid (rows, column slices); one 16-byte store per lane (ldl, ldd are multiples of 64: the lm_head GEMM pads V)
   constexpr int EPF = TT<T>::EPF;
   const int row = blockIdx.x;
@@ -546,6 +554,7 @@ __global__ __launch_bounds__(256) void p5_ce_bwd_kernel(T* __restrict__ dlogits,
     float cnt = 0.f;
     for (int t = 0; t < Tlen; ++t) cnt += out_attn[(size_t)b * Tlen + t] != 0 ? 1.f : 0.f;
     g = out_attn[row] != 0 ? gscale / fmaxf(cnt, 1.f) : 0.f;
+    if (tw) g *= tw[b];      // (p5_forward_loss_targets: the weight of the row's target)
   }
   if (lab == -100) g = 0.f;
   const float l = lse[row];

@@ -140,6 +140,10 @@ struct P5Engine {
   uint32_t* rng = nullptr;
   // ---- saved state of the last forward ----
   int B = 0, L = 0, T = 0, training = 0, M = 0, Md = 0, Vp = 0;
+  // several targets per user (p5_forward_targets): labels [B, G, T] -- the decoder is a batch of Bd = B * G sequences (Md = Bd * T rows), the encoder
+  // and the cross-attention K/V a batch of B; cross-attention runs G * T queries of a user against that user's keys
+  int Gt = 1, Bd = 0;                  // Gt: targets per user (G of the C ABI; `G` is the gradient arena)
+  const float* tgt_w = nullptr;        // p5_forward_loss_targets: weight per target [Bd] of the seeded loss, or nullptr = 1
   const int64_t *ids = nullptr, *ww = nullptr, *mask = nullptr, *labels = nullptr, *out_attn = nullptr;
   std::vector<LayerSave> es, ds;
   void *enc_x0 = nullptr, *enc_xf = nullptr, *enc_out = nullptr; float* enc_rstd_f = nullptr;
@@ -850,11 +854,11 @@ static unsigned item_head_blocks(long long pieces) {
   return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-static int64_t layout_ws(P5Engine* e, char* base, int B, int L, int T, bool with_bwd) {
+static int64_t layout_ws(P5Engine* e, char* base, int B, int L, int T, bool with_bwd, int G = 1) {
   const P5Config& c = e->c;
   const size_t sz = c.dtype == 1 ? 2 : 4;
   const int d = c.d_model, in = e->inner, F = c.d_ff, H = c.n_heads;
-  const size_t M = (size_t)B * L, Md = (size_t)B * T;
+  const size_t M = (size_t)B * L, Bd = (size_t)B * G, Md = Bd * T;      // (G targets per user: the decoder's batch is B * G)
   const int Vp = (c.vocab_size + 63) / 64 * 64;
   Bump b{base, 0};
   e->es.assign(c.n_enc_layers, LayerSave());
@@ -886,12 +890,12 @@ static int64_t layout_ws(P5Engine* e, char* base, int B, int L, int T, bool with
       l.x_sa = xprev;
       l.n_sa = b.take(Md * d * sz); l.rstd_sa = (float*)b.take(Md * 4);
       l.ssq_sa = (float*)b.take(Md * (d / 64) * 4); l.ssq_ca = (float*)b.take(Md * (d / 64) * 4); l.ssq_ff = (float*)b.take(Md * (d / 64) * 4);
-      l.qkv = b.take(Md * 3 * in * sz); l.o_sa = b.take(Md * in * sz); l.lse_sa = (float*)b.take((size_t)B * H * T * 4);
+      l.qkv = b.take(Md * 3 * in * sz); l.o_sa = b.take(Md * in * sz); l.lse_sa = (float*)b.take(Bd * H * T * 4);
       l.keep_sa = nullptr;
       l.x_ca = b.take(Md * d * sz);
       l.n_ca = b.take(Md * d * sz); l.rstd_ca = (float*)b.take(Md * 4);
       l.q_ca = b.take(Md * in * sz); l.o_ca = b.take(Md * in * sz);
-      l.lse_ca = (float*)b.take((size_t)B * H * T * 4);
+      l.lse_ca = (float*)b.take(Bd * H * T * 4);      // [B, H, G * T]
       l.x_ff = b.take(Md * d * sz);
       l.n_ff = b.take(Md * d * sz); l.rstd_ff = (float*)b.take(Md * 4);
       l.u_ff = c.gated_gelu ? b.take(Md * 2 * F * sz) : nullptr;
@@ -918,8 +922,8 @@ static int64_t layout_ws(P5Engine* e, char* base, int B, int L, int T, bool with
       e->dres_b = (float*)b.take(need > Mx * d * 4 ? need : Mx * d * 4);
     }
     e->d_enc = (float*)b.take(M * d * 4);
-    e->Dvec = (float*)b.take((size_t)B * H * (L > T ? L : T) * 4);
-    e->rel_partial = (float*)b.take(((size_t)c.n_enc_layers * rel_slots(B, L) + (size_t)c.n_dec_layers * rel_slots(B, T > 0 ? T : 1)) * c.rel_buckets * H * 4);
+    e->Dvec = (float*)b.take((size_t)H * ((size_t)B * L > Bd * T ? (size_t)B * L : Bd * T) * 4);
+    e->rel_partial = (float*)b.take(((size_t)c.n_enc_layers * rel_slots(B, L) + (size_t)c.n_dec_layers * rel_slots((int)Bd, T > 0 ? T : 1)) * c.rel_buckets * H * 4);
     e->dw_scratch = (float*)b.take((size_t)(2 * c.n_enc_layers + 3 * c.n_dec_layers + 2) * 1024 * d * 4);
     e->nb_dotbuf = (float*)b.take(Mx * (size_t)((F / 64 > H ? F / 64 : H) + 4) * 4);
     {
@@ -1072,7 +1076,7 @@ static int decoder_fwd(P5Engine* e, hipStream_t s, float* nll_out = nullptr) {
 #endif
     }
   }
-  P5_LAUNCH(p5_shift_right_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->dec_ids, e->labels, e->B, e->T, (int64_t)c.pad_id);
+  P5_LAUNCH(p5_shift_right_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->dec_ids, e->labels, e->Bd, e->T, (int64_t)c.pad_id);
   P5_TRY(P5_KCHECK());
   const bool nf = norm_fused<T>(e);
   P5_LAUNCH((p5_embed_fwd_kernel<T>), dim3((Md + 3) / 4), dim3(256), 0, s, (T*)e->dec_x0, Wc<T>(e, e->off_E), (const T*)nullptr,
@@ -1094,7 +1098,7 @@ static int decoder_fwd(P5Engine* e, hipStream_t s, float* nll_out = nullptr) {
     memset(&a, 0, sizeof(a));
     a.Q = l.qkv; a.K = (const T*)l.qkv + in; a.V = (const T*)l.qkv + 2 * in; a.O = l.o_sa; a.lse = l.lse_sa;
     a.rel_table = e->P + e->off_dec_rel; a.bucket_lut = e->lut_dec; a.lut_half = e->lut_half; a.kmask = nullptr;
-    a.B = e->B; a.H = H; a.Lq = e->T; a.Lk = e->T; a.ldq = a.ldk = a.ldv = 3 * in; a.ldo = in; a.causal = 1;
+    a.B = e->Bd; a.H = H; a.Lq = e->T; a.Lk = e->T; a.ldq = a.ldk = a.ldv = 3 * in; a.ldo = in; a.causal = 1;
     a.drop = mk_drop(e, 1, i, 1);
     P5_TRY(launch_attn_fwd<T>(a, s));
     if (nf) {
@@ -1112,7 +1116,7 @@ static int decoder_fwd(P5Engine* e, hipStream_t s, float* nll_out = nullptr) {
     memset(&a, 0, sizeof(a));
     a.Q = l.q_ca; a.K = l.kv_ca; a.V = (const T*)l.kv_ca + in; a.O = l.o_ca; a.lse = l.lse_ca;
     a.rel_table = nullptr; a.bucket_lut = nullptr; a.kmask = e->mask;
-    a.B = e->B; a.H = H; a.Lq = e->T; a.Lk = e->L; a.ldq = in; a.ldk = a.ldv = ldkv; a.ldo = in; a.causal = 0;
+    a.B = e->B; a.H = H; a.Lq = e->Gt * e->T; a.Lk = e->L; a.ldq = in; a.ldk = a.ldv = ldkv; a.ldo = in; a.causal = 0;      // a user's G * T queries
     a.drop = mk_drop(e, 1, i, 3);
     P5_TRY(launch_attn_fwd<T>(a, s));
     if (nf) P5_TRY(gemm_nf<T>(s, l.o_ca, in, Wc<T>(e, lo.ca.o), in, l.x_ff, d, Md, d, in, P5_EPI_RESID_DROP, l.x_ca, d, mk_drop(e, 1, i, 4), nullptr, 0.f, l.ssq_ff, d));
@@ -1156,7 +1160,7 @@ static int forward_impl(P5Engine* e, float* nll_out, hipStream_t s) {
   P5_TRY(decoder_fwd<T>(e, s, nll_out));
   if (e->ce_free_fwd) return 0;       // (the head's epilogue + p5_ce_finish_kernel have written nll_out and the rows' log-sum-exp)
   if (e->il.on) {
-    P5_LAUNCH(p5_trie_walk_kernel, dim3(e->B), dim3(256), 0, s, (int*)e->ce_lab, (int*)e->ce_g, e->il.state_out, e->labels, e->il.tr, e->T, e->c.pad_id,
+    P5_LAUNCH(p5_trie_walk_kernel, dim3(e->Bd), dim3(256), 0, s, (int*)e->ce_lab, (int*)e->ce_g, e->il.state_out, e->labels, e->il.tr, e->T, e->c.pad_id,
               e->c.eos_id);
     P5_TRY(P5_KCHECK());
     // (restricted head: the compact row, columns through il.tr.col)
@@ -1320,11 +1324,11 @@ static int self_attn_bwd(P5Engine* e, hipStream_t s, const LayerOff& lo, LayerSa
   a.rel_copies = c.rel_buckets;
   // every layer's launch stores into its own block of slots (encoder layers first, then decoder layers): nothing to clear, nothing to add to
   // (blocks of exactly as many slots as the launch writes -- p5l_attn_bwd_slots -- so that a stack's blocks are contiguous rows for the reducer)
-  const int sl_enc = p5l_attn_bwd_slots(sizeof(T) == 2, e->B, e->L, e->L), sl_dec = p5l_attn_bwd_slots(sizeof(T) == 2, e->B, e->T, e->T);
+  const int sl_enc = p5l_attn_bwd_slots(sizeof(T) == 2, e->B, e->L, e->L), sl_dec = p5l_attn_bwd_slots(sizeof(T) == 2, e->Bd, e->T, e->T);
   a.d_rel_table = e->rel_partial + (is_dec ? ((size_t)c.n_enc_layers * rel_slots(e->B, e->L) + (size_t)li * sl_dec) * a.rel_stride
                                            : (size_t)li * sl_enc * a.rel_stride);
   a.bucket_lut = is_dec ? e->lut_dec : e->lut_enc; a.lut_half = e->lut_half; a.kmask = is_dec ? nullptr : e->mask;
-  a.B = e->B; a.H = H; a.Lq = Lq; a.Lk = Lq; a.ldq = a.ldk = a.ldv = 3 * in; a.ldo = in; a.lddo = in;
+  a.B = is_dec ? e->Bd : e->B; a.H = H; a.Lq = Lq; a.Lk = Lq; a.ldq = a.ldk = a.ldv = 3 * in; a.ldo = in; a.lddo = in;
   a.lddq = a.lddk = a.lddv = 3 * in; a.causal = is_dec ? 1 : 0;
   a.drop = mk_drop(e, is_dec ? 1 : 0, li, 1);
   a.keep_bits = (!is_dec && g_opt_attn_fwd_head && g_opt_attn_bwd_head && g_opt_attn_keep_bits) ? l.keep_sa : nullptr;
@@ -1397,7 +1401,7 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     const int hd_ld = hd ? e->il.Nup : e->Vp;
     if (e->ce_free_fwd) {
       // dlogits = (softmax - onehot) * g straight out of the recomputed head GEMM (same operands, same accumulation order: the same logits)
-      P5_LAUNCH(p5_ce_gscale_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->ce_g, e->labels, dnll, e->out_attn, e->T, 1.0f / (float)e->B, Md);
+      P5_LAUNCH(p5_ce_gscale_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->ce_g, e->labels, dnll, e->out_attn, e->T, 1.0f / (float)e->Bd, Md, e->tgt_w);
       P5_TRY(P5_KCHECK());
       P5GemmArgs g;
       memset(&g, 0, sizeof(g));
@@ -1408,15 +1412,15 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     } else if (e->il.on && e->il.trunc) {
       P5_LAUNCH((p5_trunc_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, (const float*)e->lse_tok,
                 (const float*)e->il.row_cut, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, hd_ld, hd_ld, e->out_attn, e->T,
-                1.0f / (float)e->B);
+                1.0f / (float)e->Bd);
       P5_TRY(P5_KCHECK());
     } else if (e->il.on) {
       P5_LAUNCH((p5_trie_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, (const float*)e->lse_tok, e->labels,
-                (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, hd_ld, hd_ld, e->out_attn, e->T, 1.0f / (float)e->B);
+                (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, hd_ld, hd_ld, e->out_attn, e->T, 1.0f / (float)e->Bd);
       P5_TRY(P5_KCHECK());
     } else {
       P5_LAUNCH((p5_ce_bwd_kernel<T>), dim3(Md, Md >= 2048 ? 1 : (Md >= 512 ? 4 : 8)), dim3(256), 0, s, (T*)e->dlogits, (const float*)e->logits, (const float*)e->lse_tok,
-                e->labels, dnll, c.vocab_size, e->Vp, e->Vp, e->out_attn, e->T, 1.0f / (float)e->B);
+                e->labels, dnll, c.vocab_size, e->Vp, e->Vp, e->out_attn, e->T, 1.0f / (float)e->Bd, e->tgt_w);
       P5_TRY(P5_KCHECK());
     }
     // dE += alpha * dlogits^T hn ;  dhn = alpha * dlogits E
@@ -1487,7 +1491,7 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     const int ldkv = nd * 2 * in;
     T* dkv_i = (T*)e->dkv_all + (size_t)i * 2 * in;      // this layer's columns of d(K/V); consumed once, after the last layer
     a.dQ = e->dqkv; a.dK = dkv_i; a.dV = dkv_i + in; a.Dvec = e->Dvec;
-    a.kmask = e->mask; a.B = e->B; a.H = H; a.Lq = e->T; a.Lk = e->L; a.ldq = in; a.ldk = a.ldv = ldkv; a.ldo = in; a.lddo = in;
+    a.kmask = e->mask; a.B = e->B; a.H = H; a.Lq = e->Gt * e->T; a.Lk = e->L; a.ldq = in; a.ldk = a.ldv = ldkv; a.ldo = in; a.lddo = in;      // (dK / dV: summed over a user's G targets)
     a.lddq = in; a.lddk = a.lddv = ldkv; a.causal = 0; a.drop = mk_drop(e, 1, i, 3);
     P5_TRY(launch_attn_bwd<T>(a, s));
     P5_TRY(linear_wgrad<T>(e, s, e->dqkv, in, l.n_ca, d, e->G + lo.ca.q, Md, in, d));
@@ -1517,7 +1521,7 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     }
     P5_LAUNCH(p5_reduce_rows_kernel, dim3((c.rel_buckets * H + 15) / 16), dim3(256), 0, s, e->G + e->off_dec_rel,
               (const float*)(e->rel_partial + (size_t)c.n_enc_layers * rel_slots(e->B, e->L) * c.rel_buckets * H),
-              c.n_dec_layers * p5l_attn_bwd_slots(sizeof(T) == 2, e->B, e->T, e->T), c.rel_buckets * H);
+              c.n_dec_layers * p5l_attn_bwd_slots(sizeof(T) == 2, e->Bd, e->T, e->T), c.rel_buckets * H);
     P5_TRY(P5_KCHECK());
 #ifndef P5_EMU
     // shared.weight's gradient: the tied head's weight gradient adds with plain read-modify-writes (side stream, stage 0); the
@@ -1936,7 +1940,7 @@ template <class T>
 static int gen_prepare(P5Engine* e, GenWs& w, int B, int L, int K, int max_len, const int* roots, hipStream_t s, P5Forced* ff_out) {
   const P5Config& c = e->c;
   const int d = c.d_model, in = e->inner, R = B * K;
-  e->B = B; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
+  e->B = B; e->Gt = 1; e->Bd = B; e->tgt_w = nullptr; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
   if (e->enc_ext_next) {
     // the encoder output of the verification pass (fp32, same weights), rounded once to this engine's dtype: one encoder pass per batch
     // instead of two, and a draft that starts from the better numbers
@@ -2400,7 +2404,7 @@ static int verify_encode_impl(P5Engine* e, const int64_t* input_ids, const int64
   const P5Config& c = e->c;
   SplitScope split(sizeof(T) == 4 ? g_opt_verify_split : 0);
   layout_ws(e, v.ws, v.B, v.L, 0, false);          // (the encoder's buffers: the head of the verification workspace)
-  e->B = v.B; e->L = v.L; e->T = 0; e->M = v.B * v.L; e->Md = 0; e->training = 0;
+  e->B = v.B; e->Gt = 1; e->Bd = v.B; e->tgt_w = nullptr; e->L = v.L; e->T = 0; e->M = v.B * v.L; e->Md = 0; e->training = 0;
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
   P5_TRY(encoder_fwd<T>(e, s));
   P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), v.w.kv_all, c.n_dec_layers * 2 * e->inner, v.B * v.L, c.n_dec_layers * 2 * e->inner, c.d_model));
@@ -2698,7 +2702,7 @@ static int rank_items_impl(P5Engine* e, RankArgs& r, hipStream_t s) {
   const int R = B * w.CQ * w.nchunk;
   // encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl)
   layout_ws(e, r.ws, B, r.L, 0, false);
-  e->B = B; e->L = r.L; e->T = 0; e->M = B * r.L; e->Md = 0; e->training = 0;
+  e->B = B; e->Gt = 1; e->Bd = B; e->tgt_w = nullptr; e->L = r.L; e->T = 0; e->M = B * r.L; e->Md = 0; e->training = 0;
   e->ids = r.input_ids; e->ww = r.whole_word_ids; e->mask = r.attention_mask; e->labels = nullptr;
   P5_TRY(encoder_fwd<T>(e, s));
   P5_TRY(linear_fwd<T>(s, e->enc_out, c.d_model, Wc<T>(e, e->dec[0].ca.k), w.kv_all, c.n_dec_layers * 2 * in, B * r.L, c.n_dec_layers * 2 * in, c.d_model));
@@ -2825,7 +2829,7 @@ static int cand_plan_impl(P5Engine* e, const int* cand, int B, int C, const int*
 // while the second runs again with more rows (bound_round_impl).
 static void sel_pass_bind(P5Engine* e, char* pass, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, int B, int L) {
   layout_ws(e, pass, B, L, 0, false);
-  e->B = B; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
+  e->B = B; e->Gt = 1; e->Bd = B; e->tgt_w = nullptr; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = nullptr;
 }
 // first part: encoder + the cross-attention K/V of every decoder layer (as verify_encode_impl)
@@ -3644,35 +3648,61 @@ int p5_refresh_shadow(P5Engine* e, void* stream) {
   return P5_KCHECK();
 }
 
-int64_t p5_train_workspace_bytes(const P5Engine* e, int B, int L, int T) {
+// ---- several targets per user: labels [B, G, T] against ONE encoder pass per user (p5_forward_targets, include/p5hip.h) ----
+// the row limit of the decoder side: the norm-backward epilogue's partial table (dw_scratch) holds 1024 blocks of 64 rows per norm
+static constexpr int64_t P5_MAX_DEC_ROWS = 1024 * 64;
+int64_t p5_train_workspace_bytes_targets(const P5Engine* e, int B, int L, int T, int G) {
+  if (G < 1) return 0;
   P5Engine tmp = *e;
-  return layout_ws(&tmp, nullptr, B, L, T, true);
+  return layout_ws(&tmp, nullptr, B, L, T, true, G);
 }
+int64_t p5_train_workspace_bytes(const P5Engine* e, int B, int L, int T) { return p5_train_workspace_bytes_targets(e, B, L, T, 1); }
 
-int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
-               int B, int L, int T, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream) {
+int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
+                       int B, int L, int T, int G, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream) {
   P5_REQUIRE(e->P, "engine not bound");
   P5_REQUIRE(B >= 1 && L >= 1 && L <= 512 && T >= 1 && T <= 512, "shape limits: 1 <= L,T <= 512");
-  const int64_t need = layout_ws(e, (char*)ws, B, L, T, true);
+  P5_REQUIRE(G >= 1, "targets per user: G >= 1");
+  if (G > 1) {
+    P5_REQUIRE((int64_t)G * T <= 512, "targets per user: G * T <= 512 (the cross-attention kernels' query limit)");
+    P5_REQUIRE((int64_t)B * G * T <= P5_MAX_DEC_ROWS, "targets per user: B * G * T <= 65536 decoder rows");
+    // (decoder self-attention launches put one entry per (sequence, head) in gridDim.y: p5_attn_tu.hip)
+    P5_REQUIRE((int64_t)B * G * e->c.n_heads <= 65535, "targets per user: B * G * n_heads <= 65535 (a launch grid's y extent)");
+  }
+  const int64_t need = layout_ws(e, (char*)ws, B, L, T, true, G);
   P5_REQUIRE(ws_bytes >= need, "workspace too small");
   P5_REQUIRE(((uintptr_t)ws % 256) == 0, "workspace must be 256-byte aligned");
-  e->B = B; e->L = L; e->T = T; e->M = B * L; e->Md = B * T; e->training = training;
+  e->B = B; e->Gt = G; e->Bd = B * G; e->L = L; e->T = T; e->M = B * L; e->Md = B * G * T; e->training = training;
   e->Vp = (e->c.vocab_size + 63) / 64 * 64;
-  e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = labels; e->out_attn = nullptr;
+  e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = labels; e->out_attn = nullptr; e->tgt_w = nullptr;
   if (training && e->c.dropout > 0.f) P5_REQUIRE(e->rng, "training with dropout needs rng_state");
   e->il = e->il_next;            // one-shot: this forward and the backward behind it
   e->il_next.on = false;
+  e->il.tr.group = G;            // (the excluded-node bitmap is per USER: sample b * G + g reads row b)
+  e->il.tr.tw = nullptr;
   if (e->il.on) P5_REQUIRE(nll_out, "item loss: nll_out");
   return e->c.dtype == 1 ? forward_impl<bf16>(e, nll_out, (hipStream_t)stream) : forward_impl<float>(e, nll_out, (hipStream_t)stream);
+}
+int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
+               int B, int L, int T, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream) {
+  return p5_forward_targets(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, 1, training, nll_out, ws, ws_bytes, stream);
+}
+int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
+                            const int64_t* output_attention, int B, int L, int T, int G, const float* target_weights, int training, float* nll_out,
+                            float* loss_out, void* ws, int64_t ws_bytes, void* stream) {
+  P5_REQUIRE(output_attention && loss_out, "null argument");
+  P5_TRY(p5_forward_targets(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, G, training, nll_out, ws, ws_bytes, stream));
+  e->out_attn = output_attention;
+  e->tgt_w = target_weights;
+  e->il.tr.tw = target_weights;
+  P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, (const float*)nll_out, output_attention, B * G, T, target_weights);
+  return P5_KCHECK();
 }
 int p5_forward_loss(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
                     const int64_t* output_attention, int B, int L, int T, int training, float* nll_out, float* loss_out, void* ws, int64_t ws_bytes,
                     void* stream) {
-  P5_REQUIRE(output_attention && loss_out, "null argument");
-  P5_TRY(p5_forward(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, training, nll_out, ws, ws_bytes, stream));
-  e->out_attn = output_attention;
-  P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, (const float*)nll_out, output_attention, B, T);
-  return P5_KCHECK();
+  return p5_forward_loss_targets(e, input_ids, whole_word_ids, attention_mask, labels, output_attention, B, L, T, 1, nullptr, training, nll_out, loss_out,
+                                 ws, ws_bytes, stream);
 }
 int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_tok, const int* child_node, int n_nodes, const uint32_t* excluded_nodes,
                            int excluded_words, float temperature, int* row_state_out) {
@@ -4333,7 +4363,7 @@ int p5_encode(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_i
   P5_REQUIRE(e->P, "engine not bound");
   const int64_t need = layout_ws(e, (char*)ws, B, L, 0, false);
   P5_REQUIRE(ws_bytes >= need, "workspace too small");
-  e->B = B; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
+  e->B = B; e->Gt = 1; e->Bd = B; e->tgt_w = nullptr; e->L = L; e->T = 0; e->M = B * L; e->Md = 0; e->training = 0;
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask;
   P5_TRY(e->c.dtype == 1 ? encoder_fwd<bf16>(e, (hipStream_t)stream) : encoder_fwd<float>(e, (hipStream_t)stream));
   const size_t bytes = (size_t)B * L * e->c.d_model * (e->c.dtype == 1 ? 2 : 4);

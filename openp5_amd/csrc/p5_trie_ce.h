@@ -29,7 +29,14 @@ struct P5TrieCe {
   const uint32_t* excluded; int excl_words;      // [B, excl_words] bitmap over trie nodes, or nullptr
   float tau;
   const int* col;      // [n_edges] column of an edge's token in a compact logits row (p5_item_head.h), or nullptr: column = token
+  int group;           // samples per user (several targets per user: p5_forward_targets); the bitmap row of sample s is s / group.  0 = 1
+  const float* tw;     // [samples] weight of a sample in the seeded masked-mean loss (p5_forward_loss_targets), or nullptr = 1
 };
+// the excluded-node bitmap row of a sample
+__device__ __forceinline__ const uint32_t* p5_trie_excl_row(const P5TrieCe& tr, int sample) {
+  if (!tr.excluded) return nullptr;
+  return tr.excluded + (size_t)(tr.group > 1 ? sample / tr.group : sample) * tr.excl_words;
+}
 
 // one workgroup per sample: the positions are walked in order, the 256 threads look the label up among the node's children.
 // node[b * T + t]: the node whose children row (b, t) normalises over; -1 behind </s> and behind the row that ended the walk.
@@ -38,7 +45,7 @@ __global__ __launch_bounds__(256) void p5_trie_walk_kernel(int* __restrict__ nod
                                                           const int64_t* __restrict__ labels, P5TrieCe tr, int T, int start_id, int eos_id) {
   __shared__ int s_hit[2];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const uint32_t* ex = tr.excluded ? tr.excluded + (size_t)b * tr.excl_words : nullptr;
+  const uint32_t* ex = p5_trie_excl_row(tr, b);
   int nd = -1;
   for (int c = tr.child_off[0]; c < tr.child_off[1]; ++c)      // p5_sample_init_kernel's start node
     if (tr.child_tok[c] == start_id) nd = tr.child_node[c];
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(256) void p5_trie_ce_fwd_kernel(float* __restrict__
   }
   const int nd = node[row];
   const int c0 = tr.child_off[nd], nc = tr.child_off[nd + 1] - c0;
-  const uint32_t* ex = tr.excluded ? tr.excluded + (size_t)(row / Tlen) * tr.excl_words : nullptr;
+  const uint32_t* ex = p5_trie_excl_row(tr, row / Tlen);
   const float* lr = logits + (size_t)row * ldl;
   const int64_t lab = labels[row];
   float m = P5_NEG_INF, s = 0.f;
@@ -154,12 +161,13 @@ __global__ __launch_bounds__(256) void p5_trie_ce_bwd_kernel(T* __restrict__ dlo
     float cnt = 0.f;
     for (int t = 0; t < Tlen; ++t) cnt += out_attn[(size_t)b * Tlen + t] != 0 ? 1.f : 0.f;
     g = out_attn[row] != 0 ? gscale / fmaxf(cnt, 1.f) : 0.f;
+    if (tr.tw) g *= tr.tw[b];
   }
   P5_WAIT_VM(0);      // this wave's zero stores are acknowledged before anybody's child store leaves
   __syncthreads();
   const int nd = node[row];
   const int c0 = tr.child_off[nd], nc = tr.child_off[nd + 1] - c0;
-  const uint32_t* ex = tr.excluded ? tr.excluded + (size_t)(row / Tlen) * tr.excl_words : nullptr;
+  const uint32_t* ex = p5_trie_excl_row(tr, row / Tlen);
   const float* lr = logits + (size_t)row * ldl;
   const int64_t lab = labels[row];
   const float l = lse[row];

@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void p5_trunc_ce_fwd_kernel(float* __restrict_
   const int nd = node[row];
   const int c0 = tr.child_off[nd], nc = tr.child_off[nd + 1] - c0;
   const P5TruncGather g{logits + (size_t)row * ldl, tr.child_tok + c0, tr.child_node + c0,
-                        tr.excluded ? tr.excluded + (size_t)(row / Tlen) * tr.excl_words : nullptr, tr.tau,
+                        p5_trie_excl_row(tr, row / Tlen), tr.tau,
                         tr.col ? tr.col + c0 : nullptr};
   const float cut = p5_trunc_row_cut(g, nc, tc.top_k, tc.top_p, L, nullptr);
   const bool staged = nc <= P5_TRUNC_STAGE;
@@ -366,12 +366,13 @@ __global__ __launch_bounds__(256) void p5_trunc_ce_bwd_kernel(T* __restrict__ dl
     float cnt = 0.f;
     for (int t = 0; t < Tlen; ++t) cnt += out_attn[(size_t)b * Tlen + t] != 0 ? 1.f : 0.f;
     g = out_attn[row] != 0 ? gscale / fmaxf(cnt, 1.f) : 0.f;
+    if (tr.tw) g *= tr.tw[b];
   }
   P5_WAIT_VM(0);      // this wave's zero stores are acknowledged before anybody's child store leaves
   __syncthreads();
   const int nd = node[row];
   const int c0 = tr.child_off[nd], nc = tr.child_off[nd + 1] - c0;
-  const uint32_t* ex = tr.excluded ? tr.excluded + (size_t)(row / Tlen) * tr.excl_words : nullptr;
+  const uint32_t* ex = p5_trie_excl_row(tr, row / Tlen);
   const float* lr = logits + (size_t)row * ldl;
   const int64_t lab = labels[row];
   const float l = lse[row], cut = row_cut[row];

@@ -566,9 +566,10 @@ class P5T5Native(nn.Module):
         return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, n_nodes=int(trie.n_nodes), excl_t=excl_t, excl_words=excl_words, top_k=top_k,
                                      top_p=top_p, row_cut=None, head_tok=head_tok, head_col=head_col, head_ws=None)
 
-    def _arm_item_loss(self, q, B, T):
+    def _arm_item_loss(self, q, B, T, G=None):
         """p5_train_set_item_loss (or its truncated sibling) for the engine's next forward; the rows' states land in `last_item_loss_state`
-        (no host sync).  Truncated: the rows' cuts live in q.row_cut, which the saved inputs keep alive until the backward has run."""
+        (no host sync).  Truncated: the rows' cuts live in q.row_cut, which the saved inputs keep alive until the backward has run.
+        B: the decoder's batch (users x targets per user, G); the states are [users, G, T] then."""
         state = torch.empty(B, T, dtype=torch.int32, device=self._be.device)
         if q.top_k > 0 or q.top_p < 1.0:
             q.row_cut = torch.empty(B, T, dtype=torch.float32, device=self._be.device)
@@ -589,24 +590,68 @@ class P5T5Native(nn.Module):
             q.head_ws = raw[skew:skew + need]
             self._be.check(self._lib.p5_train_set_item_head(self._engine, _ptr(q.head_tok), n_tok, _ptr(q.head_col), _ptr(q.head_ws), need),
                            "p5_train_set_item_head")
-        self.last_item_loss_state = state
+        self.last_item_loss_state = state if G is None else state.view(B // G, G, T)
+
+    MAX_TARGET_QUERIES = 512        # G * T: the training attention kernels' query limit (cross-attention runs a user's G * T queries)
+    MAX_DECODER_ROWS = 1024 * 64    # B * G * T: the norm-backward epilogue's partial table holds 1024 blocks of 64 rows
+    MAX_GRID_Y = 65535              # B * G * num_heads: decoder self-attention launches one grid-y entry per (sequence, head)
+
+    def _check_targets(self, B, labels, output_attention=None, target_weights=None, fused=False):
+        """The limits of a call with several targets per user (labels [B, G, T]), checked before the engine is called; returns G, or None
+        for the plain labels [B, T]."""
+        if labels.dim() == 2:
+            if fused and output_attention.dim() != 2:
+                raise ValueError(f"output_attention {tuple(output_attention.shape)} must match labels {tuple(labels.shape)}")
+            if target_weights is not None:
+                raise ValueError("target_weights needs labels [B, G, T] (one weight per target); labels [B, T] has none")
+            return None
+        if labels.dim() != 3:
+            raise ValueError(f"labels {tuple(labels.shape)}: [B, T], or [B, G, T] for G targets per user")
+        Bl, G, T = labels.shape
+        if Bl != B:
+            raise ValueError(f"labels {tuple(labels.shape)}: the first dimension must be the batch of input_ids ({B})")
+        if G < 1 or T < 1:
+            raise ValueError(f"labels {tuple(labels.shape)}: G >= 1 targets per user of T >= 1 tokens")
+        if G * T > self.MAX_TARGET_QUERIES:
+            raise ValueError(f"labels {tuple(labels.shape)}: G * T = {G * T} exceeds the limit G * T <= {self.MAX_TARGET_QUERIES} "
+                             "(the attention kernels' query limit; split the targets over several calls)")
+        if B * G * T > self.MAX_DECODER_ROWS:
+            raise ValueError(f"labels {tuple(labels.shape)}: B * G * T = {B * G * T} decoder rows exceed the limit B * G * T <= {self.MAX_DECODER_ROWS} "
+                             "(the engine's row limit: 1024 blocks of 64 rows in the norm backward's partial table)")
+        if G > 1 and B * G * self.config.num_heads > self.MAX_GRID_Y:
+            raise ValueError(f"labels {tuple(labels.shape)}: B * G * num_heads = {B * G * self.config.num_heads} exceeds the limit "
+                             f"B * G * num_heads <= {self.MAX_GRID_Y} (the y extent of the self-attention launch grids)")
+        if fused and tuple(output_attention.shape) != tuple(labels.shape):
+            raise ValueError(f"output_attention {tuple(output_attention.shape)} must match labels {tuple(labels.shape)} ([B, G, T])")
+        if target_weights is not None and tuple(target_weights.shape) != (B, G):
+            raise ValueError(f"target_weights {tuple(target_weights.shape)} must have shape [B, G] = {(B, G)}")
+        return int(G)
 
     def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels, item_loss=None):
         dev = self._be.device
         B, L = input_ids.shape
-        T = labels.shape[1]
+        G = int(labels.shape[1]) if labels.dim() == 3 else None      # several targets per user (checked by the caller: _check_targets)
+        T = labels.shape[-1]
+        Bd = B * (G or 1)
         self._sync_shadow()
         self._sync_transposed()     # (no-op unless the parameters changed; a backward may follow this forward)
-        ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
-        nll = torch.empty(B * T, dtype=torch.float32, device=dev)
+        if G is None:
+            ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
+        else:
+            ws = self._workspace(self._lib.p5_train_workspace_bytes_targets(self._engine, B, L, T, G))
+        nll = torch.empty(Bd * T, dtype=torch.float32, device=dev)
         training = 1 if (self.training and self.config.dropout_rate > 0) else 0
         if training:
             self._advance_dropout_step()
         self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, item_loss)   # keep device buffers alive
         if item_loss is not None:
-            self._arm_item_loss(item_loss, B, T)
-        self._be.check(self._lib.p5_forward(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels), B, L, T,
-                                            training, _ptr(nll), _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward")
+            self._arm_item_loss(item_loss, Bd, T, G)
+        if G is None:
+            self._be.check(self._lib.p5_forward(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels), B, L, T,
+                                                training, _ptr(nll), _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward")
+        else:
+            self._be.check(self._lib.p5_forward_targets(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels), B, L, T,
+                                                        G, training, _ptr(nll), _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward_targets")
         return nll
 
     def _engine_backward(self, dnll):
@@ -692,13 +737,17 @@ class P5T5Native(nn.Module):
             self.ddp_wait_ms.append((ev0, ev1))     # (read by bench.py after a synchronize: main-stream time spent waiting for the buckets)
 
     def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None,
-                          top_k=0, top_p=1.0, item_head=None):
+                          top_k=0, top_p=1.0, item_head=None, target_weights=None):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
         none of the ~10 elementwise launches of the generic path.  Returns the loss as a 0-dim tensor; gradients are in `.grad`.
         `trie`, `temperature`, `excluded_items`, `top_k`, `top_p`: the trie-normalised item loss, as in `forward` (the masked mean then runs
-        over its NLL); `item_head`: "dense" | "trie" | None = `self.item_head`, as in `forward`."""
+        over its NLL); `item_head`: "dense" | "trie" | None = `self.item_head`, as in `forward`.
+        Several targets per user: `labels` and `output_attention` [B, G, T] (see `forward`: one encoder pass per user) and optionally
+        `target_weights` [B, G] (float; None = ones; may be negative or zero, as advantages are) -- the loss is
+        sum_{b,g} w[b,g] * (sum_t nll*m / max(sum_t m, 1)) / (B*G), the runner's masked mean over the replicated batch when w = 1; a target
+        with weight 0 or an all-zero mask contributes exactly nothing to the loss and the gradients."""
         item_head = self._item_head_mode(item_head, trie)
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
@@ -707,23 +756,36 @@ class P5T5Native(nn.Module):
         attention_mask = self._i64(attention_mask if attention_mask is not None else (input_ids != self.config.pad_token_id).long(), dev)
         labels = self._i64(labels, dev)
         output_attention = self._i64(output_attention, dev)
-        T = labels.shape[1]
+        if target_weights is not None:
+            target_weights = torch.as_tensor(target_weights).to(device=dev, dtype=torch.float32).contiguous()
+        G = self._check_targets(B, labels, output_attention, target_weights, fused=True)
+        T = labels.shape[-1]
+        Bd = B * (G or 1)
         item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p, item_head)
         self._sync_shadow()
         self._sync_transposed()
-        ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
-        out = torch.empty(B * T + 1, dtype=torch.float32, device=dev)
+        if G is None:
+            ws = self._workspace(self._lib.p5_train_workspace_bytes(self._engine, B, L, T))
+        else:
+            ws = self._workspace(self._lib.p5_train_workspace_bytes_targets(self._engine, B, L, T, G))
+        out = torch.empty(Bd * T + 1, dtype=torch.float32, device=dev)
         training = 1 if (self.training and self.config.dropout_rate > 0) else 0
         if training:
             self._advance_dropout_step()
-        self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, output_attention, item_loss)
+        self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, output_attention, item_loss, target_weights)
         if item_loss is not None:
-            self._arm_item_loss(item_loss, B, T)
-        self._be.check(self._lib.p5_forward_loss(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels),
-                                                 _ptr(output_attention), B, L, T, training, _ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * B * T),
-                                                 _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward_loss")
+            self._arm_item_loss(item_loss, Bd, T, G)
+        if G is None:
+            self._be.check(self._lib.p5_forward_loss(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels),
+                                                     _ptr(output_attention), B, L, T, training, _ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * B * T),
+                                                     _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward_loss")
+        else:
+            self._be.check(self._lib.p5_forward_loss_targets(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels),
+                                                             _ptr(output_attention), B, L, T, G, _ptr(target_weights), training, _ptr(out),
+                                                             ctypes.c_void_p(out.data_ptr() + 4 * Bd * T), _ptr(ws), ws.numel(),
+                                                             self._be.stream_ptr()), "p5_forward_loss_targets")
         self._engine_backward(None)
-        return out[B * T]
+        return out[Bd * T]
 
     def _advance_dropout_step(self):
         self._rng_cpu[1] = (self._rng_cpu[1] + 1) & 0xFFFFFFFF
@@ -749,7 +811,14 @@ class P5T5Native(nn.Module):
         and writes a dense logits gradient; "trie" (csrc/p5_item_head.h) runs it over the distinct tokens of the trie's edges only -- no
         [B*T, V] array is written or read, the loss is the same function of the logits, and rows of shared.weight's gradient whose token is
         neither on the trie nor looked up by the batch are exact zeros.  Gradient accumulation (`begin_micro_batch`), DDP and the staged
-        backward work with either head as for the plain loss."""
+        backward work with either head as for the plain loss.
+        Several targets per user: `labels` [B, G, T] returns the flat [B*G*T] NLL, in (b, g, t) order, of the replicated batch (user b's
+        inputs repeated G times, sample b*G + g carrying labels[b, g]) -- but the encoder and the cross-attention K/V projections run ONCE per
+        user, and the gradients into them are the sums over the user's G targets.  G * T <= 512, B * G * T <= 65536, B * G * num_heads <= 65535.  Every keyword
+        keeps its meaning; `excluded_items` stays per USER and applies to all G targets, `last_item_loss_state` is [B, G, T].
+        `sample_items(...)["sequences"].view(B, S, -1)[:, :, 1:]` and the [B, S*K, .] view of a slate are valid `labels` as they are.
+        With dropout on, the masks are those of the tensors the engine forms (decoder rows [B*G*T, .], self-attention [B*G, H, T, T],
+        cross-attention [B, H, G*T, L]), not those of the replicated batch.  labels[:, None, :] (G = 1) returns the bits of the 2-D call."""
         if labels is None:
             raise ValueError("P5T5Native.forward needs labels (the runner always passes them)")
         item_head = self._item_head_mode(item_head, trie)
@@ -762,6 +831,7 @@ class P5T5Native(nn.Module):
             attention_mask = (input_ids != self.config.pad_token_id).long()
         attention_mask = self._i64(attention_mask, dev)
         labels = self._i64(labels, dev)
+        self._check_targets(input_ids.shape[0], labels)
         item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], top_k, top_p, item_head)
         nll = _P5LossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels, item_loss)
         out = {"loss": nll}
