@@ -172,6 +172,33 @@ int p5_train_set_item_loss_truncated(P5Engine* e, const int* child_off, const in
 size_t p5_item_head_workspace_bytes(const P5Engine* e, int B, int T, int n_tokens);
 int p5_train_set_item_head(P5Engine* e, const int* head_tokens /* DEVICE [n_tokens], ascending, distinct */, int n_tokens,
                            const int* child_col /* DEVICE [n_edges] */, void* ws, size_t ws_bytes);
+/* Two exact per-row regularisers of the item loss (openp5_amd/csrc/p5_trie_reg.h), opt-in: the ENTROPY H of a scored row's distribution over
+ * the allowed children of its node, and its divergence KL(policy || reference) from the distribution that ref_logits give over the SAME
+ * children at the same temperature.  Rows that are not scored and rows with one allowed child have H = KL = 0 exactly.
+ * Call it BEHIND p5_train_set_item_loss and, if used, p5_train_set_item_head, in front of the forward; one-shot like them (a new
+ * p5_train_set_item_loss disarms it).  The forward then runs the regularised twin of the item-loss kernel (nll and lse keep their bits) and the
+ * backward the twin that adds the two terms' gradients to the same dlogits row in one pass.
+ * ref_logits: DEVICE fp32 [rows, ld_ref] in the column layout of the call's own head -- token columns (ld_ref >= vocab_size) for the dense head,
+ *   child_col columns (ld_ref >= n_tokens) for the restricted head -- or NULL: entropy only, KL is 0 and has no gradient.  It must be finite at
+ *   the allowed children (not checked: a -inf there gives KL = +inf) and is a constant of the gradient.
+ * row_terms: DEVICE fp32 [3 * rows], caller-owned like row_cut: H | KL | lse_ref, rows = B * G * T values each (the last two only with
+ *   ref_logits); written by the forward, read by the backward.
+ * The backward's seeds: called with dnll, it reads the per-row gradients of H and KL handed over by p5_backward_set_item_grads (zeros without
+ *   that call).  Called without (behind p5_forward_loss / p5_forward_loss_targets) the loss is
+ *     loss = L_nll + kl_coef * R_KL - entropy_coef * R_H,   R_X = sum_{b,g} (sum_t X * m / max(sum_t m, 1)) / (B * G),  m = output_attention != 0,
+ *   L_nll what it is without this call (target_weights included); R_H and R_KL are NOT weighted by target_weights.  loss_out receives the loss
+ *   and terms_out (DEVICE fp32 [3], or NULL) the parts (L_nll, R_H, R_KL).
+ * Errors: no item loss armed, the truncated item loss armed (not built), ld_ref smaller than the head's columns, row_terms NULL, a
+ * coefficient that is not finite. */
+int p5_train_set_item_regularizers(P5Engine* e, const float* ref_logits, int ld_ref, float* row_terms, float entropy_coef, float kl_coef,
+                                   float* terms_out);
+/* One-shot, in front of p5_backward / p5_backward_stage (stage 0) / p5_backward_staged called WITH dnll: DEVICE fp32 [rows] gradients of the
+ * rows' H and KL of the last forward (NULL = zeros).  Error: the last forward ran without p5_train_set_item_regularizers. */
+int p5_backward_set_item_grads(P5Engine* e, const float* d_entropy, const float* d_kl);
+/* The materialised fp32 logits of the last item-loss forward, for a frozen reference model: *ptr DEVICE [*rows, *ld], of which the first *cols
+ * columns are logits (dense head: ld = vocab_size rounded up to 64, cols = vocab_size; restricted head: logits_U, ld = Nup, cols = n_tokens).
+ * Valid until the engine's next forward.  Error: the last forward ran without an item loss. */
+int p5_train_last_item_logits(const P5Engine* e, const float** ptr, int* rows, int* ld, int* cols);
 int p5_backward_num_stages(const P5Engine* e);
 int p5_backward_stage(P5Engine* e, const float* dnll, int stage, void* stream);
 int p5_backward(P5Engine* e, const float* dnll, void* stream);
@@ -641,6 +668,21 @@ int p5_op_trie_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const 
                            const float* dnll, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
                            const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ldd, const int64_t* out_attn,
                            float gscale, void* stream);
+/* the kernels of the regularised item loss (p5_trie_reg.h; see p5_train_set_item_regularizers), one by one; child_col NULL = the dense row:
+ * p5_op_trie_reg_fwd: p5_op_trie_ce_fwd[_cols] (the same bits in nll / lse) plus entropy fp32 [rows] and, with ref_logits fp32 [rows, ld_ref],
+ *   kl and lse_ref fp32 [rows] (all three may be NULL together);
+ * p5_op_trie_reg_bwd: p5_op_trie_ce_bwd[_cols]'s row with the two regularisers' gradients added in the same store; entropy / kl / lse_ref as the
+ *   forward wrote them; seeds dnll / d_entropy / d_kl fp32 [rows] (the last two may be NULL = zeros), or -- dnll NULL -- from out_attn:
+ *   base = [out_attn != 0] gscale / max(count, 1), g_nll = base, g_H = -entropy_coef * base, g_KL = kl_coef * base. */
+int p5_op_trie_reg_fwd(int dtype, float* nll, float* lse, float* entropy, float* kl, float* lse_ref, const float* logits, const float* ref_logits,
+                       const int64_t* labels, const int* node, const int* state, const int* child_off, const int* child_tok, const int* child_node,
+                       const int* child_col, const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ld_ref,
+                       void* stream);
+int p5_op_trie_reg_bwd(int dtype, void* dlogits, const float* logits, const float* ref_logits, const float* lse, const float* entropy, const float* kl,
+                       const float* lse_ref, const int64_t* labels, const int* node, const int* state, const float* dnll, const float* d_entropy,
+                       const float* d_kl, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                       const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ld_ref, int ldd,
+                       const int64_t* out_attn, float gscale, float entropy_coef, float kl_coef, void* stream);
 int p5_op_trunc_ce_fwd_cols(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
                             const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded,
                             int excl_words, float temperature, int top_k, float top_p, int rows, int T, int ldl, void* stream);

@@ -53,6 +53,9 @@ PROTOTYPES = {
     "p5_train_set_item_loss_truncated": (i32, [vp, vp, vp, vp, i32, vp, i32, f32, vp, i32, f32, vp]),
     "p5_item_head_workspace_bytes": (C.c_size_t, [vp, i32, i32, i32]),
     "p5_train_set_item_head": (i32, [vp, vp, i32, vp, vp, C.c_size_t]),
+    "p5_train_set_item_regularizers": (i32, [vp, vp, i32, vp, f32, f32, vp]),
+    "p5_backward_set_item_grads": (i32, [vp, vp, vp]),
+    "p5_train_last_item_logits": (i32, [vp, vp, vp, vp, vp]),
     "p5_backward_num_stages": (i32, [vp]),
     "p5_backward_stage": (i32, [vp, vp, i32, vp]),
     "p5_backward": (i32, [vp, vp, vp]),
@@ -133,6 +136,9 @@ PROTOTYPES = {
     "p5_op_item_scatter": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_trie_ce_fwd_cols": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, vp]),
     "p5_op_trie_ce_bwd_cols": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, f32, vp]),
+    "p5_op_trie_reg_fwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp]),
+    "p5_op_trie_reg_bwd": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, i32, vp, f32,
+                                 f32, f32, vp]),
     "p5_op_trunc_ce_fwd_cols": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, f32, i32, i32, i32, vp]),
     "p5_op_trunc_ce_bwd_cols": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, f32, vp]),
     "p5_op_masked_mean": (i32, [vp, vp, vp, i32, i32, vp]),

@@ -29,6 +29,7 @@
 #include "p5_sample.h"
 #include "p5_sbs.h"
 #include "p5_trie_ce.h"
+#include "p5_trie_reg.h"
 #include "p5_item_head.h"
 #include "p5_trunc.h"
 #include "../../include/p5hip.h"
@@ -165,8 +166,13 @@ struct P5Engine {
     bool head = false; const int* head_tok = nullptr; int Nu = 0, Nup = 0;
     void* head_ws = nullptr; size_t head_ws_bytes = 0;
     void *EU = nullptr, *dlogitsU = nullptr; float *logitsU = nullptr, *dEU = nullptr;
+    // reg: the regularised twins of p5_trie_reg.h (p5_train_set_item_regularizers) -- per-row entropy and, with reference logits, KL to the
+    // reference.  row_terms is the caller's [3 * Md] fp32 device array (H | KL | lse_ref), written by the forward and read by the backward
+    bool reg = false; const float* ref = nullptr; int ld_ref = 0; float* row_terms = nullptr; float ent_coef = 0.f, kl_coef = 0.f;
+    float* terms_out = nullptr;
   };
   ItemLoss il_next, il;
+  const float *bw_dH = nullptr, *bw_dKL = nullptr;      // p5_backward_set_item_grads: per-row gradients of H / KL for the NEXT backward (one-shot)
   void* Sf = nullptr;              // folded bf16 weight copy W diag(ln) for q/k/v, wi, cross-attention q (same arena offsets; behind St)
   float *dres_a = nullptr, *dres_b = nullptr, *d_enc = nullptr, *Dvec = nullptr, *dres_cur = nullptr, *rel_partial = nullptr;
   void *dy = nullptr, *dn = nullptr, *dqkv = nullptr, *dO = nullptr, *dh = nullptr, *du = nullptr, *dlogits = nullptr, *dkv = nullptr;
@@ -1171,6 +1177,13 @@ static int forward_impl(P5Engine* e, float* nll_out, hipStream_t s) {
                 lg, e->labels, (const int*)e->ce_lab, e->il.tr, e->il.tc, e->T, ldl);
       return P5_KCHECK();
     }
+    if (e->il.reg) {
+      float* rt = e->il.row_terms;
+      P5_LAUNCH((p5_trie_reg_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, rt, e->il.ref ? rt + e->Md : (float*)nullptr,
+                e->il.ref ? rt + 2 * (size_t)e->Md : (float*)nullptr, lg, e->il.ref, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, e->il.tr,
+                e->T, ldl, e->il.ld_ref);
+      return P5_KCHECK();
+    }
     P5_LAUNCH((p5_trie_ce_fwd_kernel<T>), dim3(e->Md), dim3(256), 0, s, nll_out, e->lse_tok, lg, e->labels, (const int*)e->ce_lab,
               (const int*)e->ce_g, e->il.tr, e->T, ldl);
     return P5_KCHECK();
@@ -1392,6 +1405,7 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
 #endif
     e->zg_pending = false;
     if (!dnll) P5_REQUIRE(e->out_attn, "backward without dnll needs p5_forward_loss (output_attention mask)");
+    struct ItemGradsOnce { P5Engine* e; ~ItemGradsOnce() { e->bw_dH = e->bw_dKL = nullptr; } } item_grads_once{e};      // one-shot, whatever stage 0 returns
     const float alpha = 1.0f / sqrtf((float)d);
     // the head's logits, their gradient and their leading dimension: the vocabulary's, or -- item loss on the restricted head
     // (p5_item_head.h) -- the compact arrays of the caller's workspace
@@ -1413,6 +1427,12 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       P5_LAUNCH((p5_trunc_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, (const float*)e->lse_tok,
                 (const float*)e->il.row_cut, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->il.tr, hd_ld, hd_ld, e->out_attn, e->T,
                 1.0f / (float)e->Bd);
+      P5_TRY(P5_KCHECK());
+    } else if (e->il.on && e->il.reg) {
+      const float* rt = e->il.row_terms;
+      P5_LAUNCH((p5_trie_reg_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, e->il.ref, (const float*)e->lse_tok, rt, rt + Md,
+                rt + 2 * (size_t)Md, e->labels, (const int*)e->ce_lab, (const int*)e->ce_g, dnll, e->bw_dH, e->bw_dKL, e->il.tr, hd_ld, e->il.ld_ref,
+                hd_ld, e->out_attn, e->T, 1.0f / (float)e->Bd, e->il.ent_coef, e->il.kl_coef);
       P5_TRY(P5_KCHECK());
     } else if (e->il.on) {
       P5_LAUNCH((p5_trie_ce_bwd_kernel<T>), dim3(Md), dim3(256), 0, s, (T*)hd_dl, hd_lg, (const float*)e->lse_tok, e->labels,
@@ -3695,6 +3715,12 @@ int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t
   e->out_attn = output_attention;
   e->tgt_w = target_weights;
   e->il.tr.tw = target_weights;
+  if (e->il.on && e->il.reg) {
+    const float* rt = e->il.row_terms;
+    P5_LAUNCH(p5_trie_reg_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, e->il.terms_out, (const float*)nll_out, rt,
+              e->il.ref ? rt + e->Md : (const float*)nullptr, output_attention, B * G, T, target_weights, e->il.ent_coef, e->il.kl_coef);
+    return P5_KCHECK();
+  }
   P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, (const float*)nll_out, output_attention, B * G, T, target_weights);
   return P5_KCHECK();
 }
@@ -3708,6 +3734,7 @@ int p5_train_set_item_loss(P5Engine* e, const int* child_off, const int* child_t
                            int excluded_words, float temperature, int* row_state_out) {
   e->il_next.on = false;
   e->il_next.head = false;        // (the restricted head is armed behind this call, every time: p5_train_set_item_head)
+  e->il_next.reg = false;         // (and so are the regularisers: p5_train_set_item_regularizers)
   P5_REQUIRE(child_off && child_tok && child_node && n_nodes >= 1, "item loss: trie (child_off / child_tok / child_node, n_nodes >= 1)");
   P5_REQUIRE(temperature > 0.f && temperature < __builtin_huge_valf(), "item loss: temperature > 0");
   P5_REQUIRE(excluded_words >= 0 && (excluded_nodes || excluded_words == 0), "item loss: excluded_nodes / excluded_words");
@@ -3749,6 +3776,36 @@ int p5_train_set_item_head(P5Engine* e, const int* head_tokens, int n_tokens, co
   h.head_ws = ws; h.head_ws_bytes = ws_bytes;
   h.tr.col = child_col;
   h.head = true;
+  return 0;
+}
+int p5_train_set_item_regularizers(P5Engine* e, const float* ref_logits, int ld_ref, float* row_terms, float entropy_coef, float kl_coef,
+                                   float* terms_out) {
+  e->il_next.reg = false;
+  P5_REQUIRE(e->il_next.on, "item regularizers: no item loss is armed (call p5_train_set_item_loss first)");
+  P5_REQUIRE(!e->il_next.trunc, "item regularizers: not built for the truncated item loss (top_k / top_p)");
+  P5_REQUIRE(row_terms, "item regularizers: row_terms (device, three fp32 per decoder row)");
+  P5_REQUIRE(entropy_coef - entropy_coef == 0.f && kl_coef - kl_coef == 0.f, "item regularizers: entropy_coef / kl_coef must be finite");
+  const int cols = e->il_next.head ? e->il_next.Nu : e->c.vocab_size;
+  P5_REQUIRE(!ref_logits || ld_ref >= cols, "item regularizers: ld_ref is smaller than the head's columns (vocab_size, or the trie's tokens)");
+  P5Engine::ItemLoss& h = e->il_next;
+  h.ref = ref_logits; h.ld_ref = ref_logits ? ld_ref : 0; h.row_terms = row_terms; h.ent_coef = entropy_coef; h.kl_coef = kl_coef;
+  h.terms_out = terms_out;
+  h.reg = true;
+  return 0;
+}
+int p5_backward_set_item_grads(P5Engine* e, const float* d_entropy, const float* d_kl) {
+  e->bw_dH = e->bw_dKL = nullptr;
+  P5_REQUIRE(e->Md > 0 && e->il.on && e->il.reg, "item grads: the last forward ran without item regularizers (p5_train_set_item_regularizers)");
+  e->bw_dH = d_entropy;
+  e->bw_dKL = d_kl;
+  return 0;
+}
+int p5_train_last_item_logits(const P5Engine* e, const float** ptr, int* rows, int* ld, int* cols) {
+  P5_REQUIRE(ptr && rows && ld && cols, "last item logits: null argument");
+  P5_REQUIRE(e->Md > 0 && e->il.on, "last item logits: the last forward ran without an item loss (p5_train_set_item_loss)");
+  const bool hd = e->il.head;
+  *ptr = hd ? (const float*)e->il.logitsU : (const float*)e->logits;
+  *rows = e->Md; *ld = hd ? e->il.Nup : e->Vp; *cols = hd ? e->il.Nu : e->c.vocab_size;
   return 0;
 }
 int p5_backward_num_stages(const P5Engine* e) { return e->c.n_dec_layers + e->c.n_enc_layers + 4; }
@@ -4746,6 +4803,37 @@ int p5_op_trie_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const 
   P5_REQUIRE(child_col, "trie_ce_bwd_cols: child_col");
   return op_trie_ce_bwd(dtype, dlogits, logits, lse, labels, node, state, dnll, child_off, child_tok, child_node, child_col, excluded, excl_words, temperature,
                         rows, T, ldl, ldd, out_attn, gscale, stream);
+}
+int p5_op_trie_reg_fwd(int dtype, float* nll, float* lse, float* entropy, float* kl, float* lse_ref, const float* logits, const float* ref_logits,
+                       const int64_t* labels, const int* node, const int* state, const int* child_off, const int* child_tok, const int* child_node,
+                       const int* child_col, const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ld_ref,
+                       void* stream) {
+  P5_REQUIRE(nll && lse && entropy && logits && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0 && ldl >= 1, "trie_reg_fwd: arguments");
+  P5_REQUIRE(!ref_logits || (kl && lse_ref && ld_ref >= 1), "trie_reg_fwd: ref_logits needs kl, lse_ref and ld_ref");
+  P5TrieCe tr;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  tr.col = child_col;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == 1) P5_LAUNCH((p5_trie_reg_fwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, nll, lse, entropy, kl, lse_ref, logits, ref_logits, labels, node, state, tr, T, ldl, ld_ref);
+  else P5_LAUNCH((p5_trie_reg_fwd_kernel<float>), dim3(rows), dim3(256), 0, s, nll, lse, entropy, kl, lse_ref, logits, ref_logits, labels, node, state, tr, T, ldl, ld_ref);
+  return P5_KCHECK();
+}
+int p5_op_trie_reg_bwd(int dtype, void* dlogits, const float* logits, const float* ref_logits, const float* lse, const float* entropy, const float* kl,
+                       const float* lse_ref, const int64_t* labels, const int* node, const int* state, const float* dnll, const float* d_entropy,
+                       const float* d_kl, const int* child_off, const int* child_tok, const int* child_node, const int* child_col,
+                       const uint32_t* excluded, int excl_words, float temperature, int rows, int T, int ldl, int ld_ref, int ldd,
+                       const int64_t* out_attn, float gscale, float entropy_coef, float kl_coef, void* stream) {
+  P5_REQUIRE(dlogits && logits && lse && entropy && labels && node && state && rows >= 1 && T >= 1 && rows % T == 0, "trie_reg_bwd: arguments");
+  P5_REQUIRE(ldl >= 1 && ldd >= 1 && ldd % 8 == 0, "trie_reg_bwd: ldd a multiple of 8");
+  P5_REQUIRE(dnll || out_attn, "trie_reg_bwd: dnll, or out_attn [rows / T, T]");
+  P5_REQUIRE(!ref_logits || (kl && lse_ref && ld_ref >= 1), "trie_reg_bwd: ref_logits needs kl, lse_ref and ld_ref");
+  P5TrieCe tr;
+  P5_TRY(trie_ce_args(&tr, child_off, child_tok, child_node, excluded, excl_words, temperature));
+  tr.col = child_col;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == 1) P5_LAUNCH((p5_trie_reg_bwd_kernel<bf16>), dim3(rows), dim3(256), 0, s, (bf16*)dlogits, logits, ref_logits, lse, entropy, kl, lse_ref, labels, node, state, dnll, d_entropy, d_kl, tr, ldl, ld_ref, ldd, out_attn, T, gscale, entropy_coef, kl_coef);
+  else P5_LAUNCH((p5_trie_reg_bwd_kernel<float>), dim3(rows), dim3(256), 0, s, (float*)dlogits, logits, ref_logits, lse, entropy, kl, lse_ref, labels, node, state, dnll, d_entropy, d_kl, tr, ldl, ld_ref, ldd, out_attn, T, gscale, entropy_coef, kl_coef);
+  return P5_KCHECK();
 }
 int p5_op_trunc_ce_fwd_cols(int dtype, float* nll, float* lse, float* row_cut, int* state, const float* logits, const int64_t* labels, const int* node,
                             const int* child_off, const int* child_tok, const int* child_node, const int* child_col, const uint32_t* excluded,

@@ -20,6 +20,7 @@ from __future__ import annotations
 import contextlib
 import warnings
 import os
+import copy
 import ctypes
 import threading
 import math
@@ -121,6 +122,30 @@ class _P5LossFn(torch.autograd.Function):
         return None, None, None, None, None, None, None
 
 
+class _P5RegLossFn(torch.autograd.Function):
+    """The seam of the regularised item loss (csrc/p5_trie_reg.h): three per-row outputs -- NLL, entropy, KL to the reference -- and ONE engine
+    backward that receives the three per-row gradients.  Without reference logits the third output is zeros and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, input_ids, whole_word_ids, attention_mask, labels, item_loss):
+        ctx.model = model
+        ctx.item_loss = item_loss
+        nll = model._engine_forward(input_ids, whole_word_ids, attention_mask, labels, item_loss)
+        rows = nll.numel()
+        ent = item_loss.row_terms[:rows]
+        if item_loss.ref is None:
+            kl = torch.zeros_like(nll)
+            ctx.mark_non_differentiable(kl)
+        else:
+            kl = item_loss.row_terms[rows:2 * rows]
+        return nll, ent, kl
+
+    @staticmethod
+    def backward(ctx, dnll, dent, dkl):
+        ctx.model._engine_backward(dnll, dent, dkl if ctx.item_loss.ref is not None else None)
+        return None, None, None, None, None, None, None
+
+
 class _GenLane:
     """What ONE in-flight generate() call owns: its engines (the bf16 / fp32 search engine and, for verified generation, the fp32 verification
     engine -- all bound to the model's ONE set of parameter arenas), its workspaces, its pinned read-back buffer, its HIP stream.  Lane 0 is
@@ -197,6 +222,7 @@ class P5T5Native(nn.Module):
         self._stats_lock = threading.Lock()
         self.verify_stats = {"calls": 0, "users": 0, "escalated_users": 0, "fallback_users": 0, "rows": 0, "rows_per_user_max": 0, "draft_beams": 0,
                              "wide_fp32_users": 0}
+        self.last_item_loss_terms = None    # fp32 [3] device tensor (L_nll, R_H, R_KL) of the last loss_and_backward if it was regularised, else None
         self.last_item_loss_state = None    # int32 [B, T] device tensor of the last item-loss forward (forward(trie=...)): 0 scored, 1 past the end, 2 off the trie, 3 truncated away
         self.last_generate_path = None      # "verified" | "fp32_search" | "draft_bf16": which search the most recent generate() call ran ("sample": sample_items() / generate(do_sample=True); "slates": sample_slates(); "rank_fp32" | "rank_bf16": rank_items(); "cand_fp32" | "cand_bf16": score_candidates())
         self.rank_stats = {"calls": 0, "users": 0, "rescored_users": 0, "users_per_pass": 0, "rows_per_user": 0,
@@ -564,7 +590,36 @@ class P5T5Native(nn.Module):
         off, tok, nxt = trie.device_arrays(dev)
         head_tok, head_col = trie.head_columns_device(dev) if item_head == "trie" else (None, None)
         return types.SimpleNamespace(tau=tau, off=off, tok=tok, nxt=nxt, n_nodes=int(trie.n_nodes), excl_t=excl_t, excl_words=excl_words, top_k=top_k,
-                                     top_p=top_p, row_cut=None, head_tok=head_tok, head_col=head_col, head_ws=None)
+                                     top_p=top_p, row_cut=None, head_tok=head_tok, head_col=head_col, head_ws=None, reg=False, ref=None,
+                                     entropy_coef=0.0, kl_coef=0.0, row_terms=None, terms=None)
+
+    def _item_regularizers(self, q, rows, ref_logits, entropy_coef=0.0, kl_coef=0.0, fused=False):
+        """The checked setting of the item loss's regularisers (csrc/p5_trie_reg.h) on the item-loss setting q of a call with `rows` decoder
+        rows: per-row entropy and, with `ref_logits`, KL(policy || reference).  Returns q."""
+        if q is None:
+            raise ValueError("item_entropy / ref_logits / entropy_coef / kl_coef need trie=...: they regularise the trie-normalised item loss")
+        if q.top_k > 0 or q.top_p < 1.0:
+            raise ValueError("item_entropy / ref_logits / entropy_coef / kl_coef are not built for the truncated item loss (top_k / top_p)")
+        ec, kc = float(entropy_coef), float(kl_coef)
+        if not (math.isfinite(ec) and math.isfinite(kc)):
+            raise ValueError(f"entropy_coef={entropy_coef!r}, kl_coef={kl_coef!r}: finite values")
+        if kc != 0.0 and ref_logits is None:
+            raise ValueError(f"kl_coef={kl_coef!r} needs ref_logits (a frozen reference model's `item_logits` of this batch)")
+        if ref_logits is not None:
+            cols = int(q.head_tok.numel()) if q.head_tok is not None else int(self.config.vocab_size)
+            head = "trie" if q.head_tok is not None else "dense"
+            if not isinstance(ref_logits, torch.Tensor) or ref_logits.dtype != torch.float32:
+                raise ValueError(f"ref_logits must be a float32 tensor (got {getattr(ref_logits, 'dtype', type(ref_logits))})")
+            if tuple(ref_logits.shape) != (rows, cols):
+                raise ValueError(f"ref_logits {tuple(ref_logits.shape)}: [rows, columns] = {(rows, cols)} for this call (item_head={head!r}: "
+                                 f"{'the tokens of trie.head_columns()' if head == 'trie' else 'the vocabulary'})")
+            if ref_logits.device != self._flat.device:
+                raise ValueError(f"ref_logits is on {ref_logits.device}, the model on {self._flat.device}")
+            q.ref = ref_logits.detach().contiguous()
+        q.reg, q.entropy_coef, q.kl_coef = True, ec, kc
+        if fused:
+            q.terms = torch.empty(3, dtype=torch.float32, device=self._be.device)
+        return q
 
     def _arm_item_loss(self, q, B, T, G=None):
         """p5_train_set_item_loss (or its truncated sibling) for the engine's next forward; the rows' states land in `last_item_loss_state`
@@ -590,6 +645,12 @@ class P5T5Native(nn.Module):
             q.head_ws = raw[skew:skew + need]
             self._be.check(self._lib.p5_train_set_item_head(self._engine, _ptr(q.head_tok), n_tok, _ptr(q.head_col), _ptr(q.head_ws), need),
                            "p5_train_set_item_head")
+        if q.reg:
+            # the rows' entropy | KL | reference log-sum-exp: the caller's, like row_cut (the forward writes them, the backward reads them)
+            q.row_terms = torch.empty(3 * B * T, dtype=torch.float32, device=self._be.device)
+            self._be.check(self._lib.p5_train_set_item_regularizers(self._engine, _ptr(q.ref), 0 if q.ref is None else int(q.ref.shape[1]),
+                                                                    _ptr(q.row_terms), q.entropy_coef, q.kl_coef, _ptr(q.terms)),
+                           "p5_train_set_item_regularizers")
         self.last_item_loss_state = state if G is None else state.view(B // G, G, T)
 
     MAX_TARGET_QUERIES = 512        # G * T: the training attention kernels' query limit (cross-attention runs a user's G * T queries)
@@ -627,7 +688,8 @@ class P5T5Native(nn.Module):
             raise ValueError(f"target_weights {tuple(target_weights.shape)} must have shape [B, G] = {(B, G)}")
         return int(G)
 
-    def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels, item_loss=None):
+    def _engine_forward(self, input_ids, whole_word_ids, attention_mask, labels, item_loss=None, inference=False):
+        """`inference`: no dropout whatever `self.training` says, and the dropout step stays where it is (`item_logits`)."""
         dev = self._be.device
         B, L = input_ids.shape
         G = int(labels.shape[1]) if labels.dim() == 3 else None      # several targets per user (checked by the caller: _check_targets)
@@ -640,7 +702,7 @@ class P5T5Native(nn.Module):
         else:
             ws = self._workspace(self._lib.p5_train_workspace_bytes_targets(self._engine, B, L, T, G))
         nll = torch.empty(Bd * T, dtype=torch.float32, device=dev)
-        training = 1 if (self.training and self.config.dropout_rate > 0) else 0
+        training = 1 if (self.training and self.config.dropout_rate > 0 and not inference) else 0
         if training:
             self._advance_dropout_step()
         self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, item_loss)   # keep device buffers alive
@@ -654,13 +716,18 @@ class P5T5Native(nn.Module):
                                                         G, training, _ptr(nll), _ptr(ws), ws.numel(), self._be.stream_ptr()), "p5_forward_targets")
         return nll
 
-    def _engine_backward(self, dnll):
+    def _engine_backward(self, dnll, d_entropy=None, d_kl=None):
         """dnll = gradient of the per-token NLL (autograd path), or None after `p5_forward_loss`: the engine then seeds
-        the backward with the gradient of the runner's masked-mean loss itself."""
+        the backward with the gradient of the runner's masked-mean loss itself.
+        d_entropy / d_kl: per-row gradients of the regularised item loss's entropy / KL rows (autograd path; None = zeros)."""
         if dnll is not None:
             dnll = dnll.to(torch.float32).contiguous()
         self.finish_exchange()          # (an exchange nobody consumed: its buckets must land before this backward rewrites the arena)
         lib, eng, sp = self._lib, self._engine, self._be.stream_ptr()
+        if d_entropy is not None or d_kl is not None:
+            d_entropy = None if d_entropy is None else d_entropy.to(torch.float32).contiguous()
+            d_kl = None if d_kl is None else d_kl.to(torch.float32).contiguous()
+            self._be.check(lib.p5_backward_set_item_grads(eng, _ptr(d_entropy), _ptr(d_kl)), "p5_backward_set_item_grads")
         exchange = self.ddp_world > 1 and self._ddp_sync
         if exchange or self.staged_backward:
             import torch.distributed as dist
@@ -737,7 +804,7 @@ class P5T5Native(nn.Module):
             self.ddp_wait_ms.append((ev0, ev1))     # (read by bench.py after a synchronize: main-stream time spent waiting for the buckets)
 
     def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None,
-                          top_k=0, top_p=1.0, item_head=None, target_weights=None):
+                          top_k=0, top_p=1.0, item_head=None, target_weights=None, entropy_coef=0.0, kl_coef=0.0, ref_logits=None):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
@@ -747,7 +814,13 @@ class P5T5Native(nn.Module):
         Several targets per user: `labels` and `output_attention` [B, G, T] (see `forward`: one encoder pass per user) and optionally
         `target_weights` [B, G] (float; None = ones; may be negative or zero, as advantages are) -- the loss is
         sum_{b,g} w[b,g] * (sum_t nll*m / max(sum_t m, 1)) / (B*G), the runner's masked mean over the replicated batch when w = 1; a target
-        with weight 0 or an all-zero mask contributes exactly nothing to the loss and the gradients."""
+        with weight 0 or an all-zero mask contributes exactly nothing to the loss and the gradients.
+        `entropy_coef`, `kl_coef`, `ref_logits` (item loss only, not under top_k / top_p; csrc/p5_trie_reg.h): the returned loss is
+        L_nll + kl_coef * R_KL - entropy_coef * R_H, with L_nll the loss above and R_H / R_KL the same masked mean (NOT weighted by
+        `target_weights`: a target of weight 0 still contributes) of the rows' exact entropy over the allowed children and of their exact
+        KL(policy || reference); `ref_logits` fp32 [rows, V] ("dense") or [rows, Nu] ("trie") is a frozen reference model's `item_logits` of the
+        same batch, finite at the allowed children, a constant of the gradient.  `last_item_loss_terms` is the device tensor
+        (L_nll, R_H, R_KL), no host sync (None behind a call without regularisers).  With both coefficients 0 and no `ref_logits` the call is the one above, bit for bit."""
         item_head = self._item_head_mode(item_head, trie)
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
@@ -762,6 +835,9 @@ class P5T5Native(nn.Module):
         T = labels.shape[-1]
         Bd = B * (G or 1)
         item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p, item_head)
+        if entropy_coef != 0.0 or kl_coef != 0.0 or ref_logits is not None:
+            item_loss = self._item_regularizers(item_loss, Bd * T, ref_logits, entropy_coef, kl_coef, fused=True)
+        self.last_item_loss_terms = item_loss.terms if item_loss is not None else None      # (None behind a call without regularisers: never a stale step's)
         self._sync_shadow()
         self._sync_transposed()
         if G is None:
@@ -792,7 +868,7 @@ class P5T5Native(nn.Module):
         self._rng[1] = self._rng_cpu[1] if self._rng_cpu[1] < 2 ** 31 else self._rng_cpu[1] - 2 ** 32
 
     def forward(self, input_ids=None, whole_word_ids=None, attention_mask=None, labels=None, alpha=None, return_dict=True, trie=None,
-                temperature=1.0, excluded_items=None, top_k=0, top_p=1.0, item_head=None, **unused):
+                temperature=1.0, excluded_items=None, top_k=0, top_p=1.0, item_head=None, item_entropy=False, ref_logits=None, **unused):
         """P5_T5.forward (P5_T5.py:275-386): returns {"loss": flat [B*T] per-token NLL}; `alpha` is accepted and ignored
         exactly as in the reference (P5_T5.py:294).
         `trie` (Trie / CompiledTrie; None = the full-vocabulary cross-entropy, unchanged): the trie-normalised item loss (csrc/p5_trie_ce.h),
@@ -818,7 +894,13 @@ class P5T5Native(nn.Module):
         keeps its meaning; `excluded_items` stays per USER and applies to all G targets, `last_item_loss_state` is [B, G, T].
         `sample_items(...)["sequences"].view(B, S, -1)[:, :, 1:]` and the [B, S*K, .] view of a slate are valid `labels` as they are.
         With dropout on, the masks are those of the tensors the engine forms (decoder rows [B*G*T, .], self-attention [B*G, H, T, T],
-        cross-attention [B, H, G*T, L]), not those of the replicated batch.  labels[:, None, :] (G = 1) returns the bits of the 2-D call."""
+        cross-attention [B, H, G*T, L]), not those of the replicated batch.  labels[:, None, :] (G = 1) returns the bits of the 2-D call.
+        `item_entropy=True` / `ref_logits` (item loss only, not under top_k / top_p; csrc/p5_trie_reg.h): the dict gains "item_entropy" and /
+        or "item_kl", flat fp32 like "loss" and differentiable -- per scored row the exact entropy of the row's distribution over its allowed
+        children, and its exact KL(policy || reference) from the distribution `ref_logits` give over the same children at the same
+        temperature (rows that are not scored, and rows with one allowed child: exactly 0).  `ref_logits`: fp32 [rows, V] ("dense") or
+        [rows, Nu] ("trie"), a frozen reference model's `item_logits` of the same batch; finite at the allowed children (not checked); a
+        constant of the gradient.  One engine backward serves the three outputs.  "loss" keeps the bits it has without the keywords."""
         if labels is None:
             raise ValueError("P5T5Native.forward needs labels (the runner always passes them)")
         item_head = self._item_head_mode(item_head, trie)
@@ -833,9 +915,55 @@ class P5T5Native(nn.Module):
         labels = self._i64(labels, dev)
         self._check_targets(input_ids.shape[0], labels)
         item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], top_k, top_p, item_head)
+        if item_entropy or ref_logits is not None:
+            item_loss = self._item_regularizers(item_loss, labels.numel(), ref_logits)
+            nll, ent, kl = _P5RegLossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels, item_loss)
+            out = {"loss": nll}
+            if item_entropy:
+                out["item_entropy"] = ent
+            if ref_logits is not None:
+                out["item_kl"] = kl
+            return out if return_dict else (nll,)
         nll = _P5LossFn.apply(self._anchor, self, input_ids, whole_word_ids, attention_mask, labels, item_loss)
         out = {"loss": nll}
         return out if return_dict else (nll,)
+
+    def frozen_copy(self):
+        """A second model on the same backend with a copy of this model's weights as they are now, in eval mode, same dtype, tied to no
+        optimizer and to no data-parallel group: the frozen reference policy whose `item_logits` are another call's `ref_logits`."""
+        ref = P5T5Native(copy.copy(self.config), dtype="bf16" if self.compute_dtype == 1 else "fp32", backend=self._be)
+        ref.load_state_dict(self.state_dict(), strict=True)
+        ref.item_head = self.item_head
+        ref.eval()
+        return ref
+
+    @torch.no_grad()
+    def item_logits(self, input_ids, whole_word_ids, attention_mask, labels, trie, temperature=1.0, excluded_items=None, item_head=None):
+        """The head's fp32 logits of an item-loss forward, as a frozen REFERENCE model hands them to another model's `ref_logits`:
+        [rows, V] ("dense") or [rows, Nu] ("trie": the columns of `trie.head_columns()`), rows = B*T or B*G*T in the order of "loss".
+        No gradient is recorded, dropout is never applied whatever `self.training` says, `.grad` and the dropout step stay as they are.
+        The result is a fresh tensor copied on the current stream: the engine's buffers may be reused at once.  (The logits do not depend
+        on `temperature` / `excluded_items`; they are accepted so that the call takes the arguments of the forward it mirrors.)
+        Not between a forward of THIS model and its backward: the engine holds one forward at a time."""
+        if trie is None:
+            raise ValueError("item_logits needs trie=...")
+        item_head = self._item_head_mode(item_head, trie)
+        dev = self._be.device
+        input_ids = self._i64(input_ids, dev)
+        whole_word_ids = self._i64(whole_word_ids if whole_word_ids is not None else torch.zeros_like(input_ids), dev)
+        attention_mask = self._i64(attention_mask if attention_mask is not None else (input_ids != self.config.pad_token_id).long(), dev)
+        labels = self._i64(labels, dev)
+        self._check_targets(input_ids.shape[0], labels)
+        q = self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], 0, 1.0, item_head)
+        self._engine_forward(input_ids, whole_word_ids, attention_mask, labels, q, inference=True)
+        ptr, rows, ld, cols = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        self._be.check(self._lib.p5_train_last_item_logits(self._engine, ctypes.byref(ptr), ctypes.byref(rows), ctypes.byref(ld), ctypes.byref(cols)),
+                       "p5_train_last_item_logits")
+        base = q.head_ws if q.head_ws is not None else self._ws       # (the array lives in the buffer this call handed to the engine)
+        off, nbytes = int(ptr.value) - base.data_ptr(), rows.value * ld.value * 4
+        if off < 0 or off + nbytes > base.numel():
+            raise RuntimeError("item_logits: the engine's logits lie outside the workspace of this call")
+        return base[off:off + nbytes].view(torch.float32).view(rows.value, ld.value)[:, :cols.value].clone()
 
     # ------------------------------------------------------------------ generation lanes
     def _drop_lanes(self):

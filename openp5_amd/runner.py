@@ -82,6 +82,12 @@ def parse_runner_args(parser):
     parser.add_argument("--item_loss_head", type=str, default="dense", choices=["dense", "trie"], help="head of --train_item_loss 1: dense = the "
                         "tied head over the whole vocabulary; trie = over the distinct tokens of the item trie only (the same loss, no [B*T, V] "
                         "logits; P5T5Native.forward(item_head=...))")
+    parser.add_argument("--item_loss_entropy_coef", type=float, default=0.0, help="--train_item_loss 1: the loss gains -coef * (masked mean of the exact "
+                        "entropy of every target row's distribution over the allowed children of its trie node); 0 = off")
+    parser.add_argument("--item_loss_kl_coef", type=float, default=0.0, help="--train_item_loss 1: the loss gains +coef * (masked mean of the exact "
+                        "KL(policy || reference) over the same children); needs --item_loss_kl_ref; 0 = off")
+    parser.add_argument("--item_loss_kl_ref", type=str, default="", choices=["", "init"], help="reference policy of --item_loss_kl_coef: init = a frozen "
+                        "copy of the model's weights at the start of training (eval mode, same dtype, no optimizer, not data-parallel)")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -125,10 +131,18 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
     (SingleRunner.py:182), which drives its schedule to lr = 0 after 1/accum of the run; this is the intended behaviour.
 
     `item_loss` (None = the full-vocabulary cross-entropy): keyword arguments of the native model's trie-normalised item loss --
-    {"trie": ..., "temperature": ...[, "top_k": ..., "top_p": ...]} (`P5T5Native.forward`)."""
-    kw = item_loss or {}
+    {"trie": ..., "temperature": ...[, "top_k": ..., "top_p": ...]} (`P5T5Native.forward`); with "entropy_coef" / "kl_coef" (native model
+    only) the loss gains the regularisers of `P5T5Native.loss_and_backward`, and "ref_model" (a frozen `P5T5Native`) supplies the
+    reference's `item_logits` of the batch when kl_coef != 0."""
+    kw = dict(item_loss or {})
     input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
     fused = getattr(model, "loss_and_backward", None)
+    ref_model = kw.pop("ref_model", None)
+    if fused is None and [kw.pop(k, 0.0) for k in ("entropy_coef", "kl_coef")] != [0.0, 0.0]:
+        raise ValueError("item-loss regularisers (entropy_coef / kl_coef) need the native model")
+    if ref_model is not None and kw.get("kl_coef", 0.0) != 0.0:
+        kw["ref_logits"] = ref_model.item_logits(input_ids, whole_ids, attn, output_ids, kw["trie"], temperature=kw.get("temperature", 1.0),
+                                                 item_head=kw.get("item_head"))
     last = micro == accum - 1
     if fused is not None and hasattr(model, "begin_micro_batch"):
         model.begin_micro_batch(first=micro == 0, sync=last)
@@ -414,22 +428,42 @@ class DistributedRunner:
         """--train_item_loss 1: the keyword arguments of the trie-normalised item loss -- ONE union trie over the items of all training
         datasets (item ids carry their dataset's name, so the union is a tree), built once; None with the flag at 0."""
         if not int(getattr(self.args, "train_item_loss", 0)):
+            if float(getattr(self.args, "item_loss_entropy_coef", 0.0)) != 0.0 or float(getattr(self.args, "item_loss_kl_coef", 0.0)) != 0.0:
+                raise ValueError("--item_loss_entropy_coef / --item_loss_kl_coef require --train_item_loss 1")
             return None
         kw = self.__dict__.get("_item_loss")
         if kw is None:
+            # (every flag is checked before anything is built, and the dict is cached only when it is complete: a caller that catches an
+            #  error never meets a half-built setting on its next call)
+            top_k, top_p = int(getattr(self.args, "item_loss_top_k", 0)), float(getattr(self.args, "item_loss_top_p", 1.0))
+            ec, kc = float(getattr(self.args, "item_loss_entropy_coef", 0.0)), float(getattr(self.args, "item_loss_kl_coef", 0.0))
+            if ec != 0.0 or kc != 0.0:
+                if top_k != 0 or top_p != 1.0:
+                    raise ValueError("--item_loss_entropy_coef / --item_loss_kl_coef are not built for --item_loss_top_k / --item_loss_top_p")
+                if kc != 0.0 and str(getattr(self.args, "item_loss_kl_ref", "")) != "init":
+                    raise ValueError("--item_loss_kl_coef needs a reference policy: --item_loss_kl_ref init")
+                if not (hasattr(self.model, "loss_and_backward") and hasattr(self.model, "frozen_copy")):
+                    raise ValueError("--item_loss_entropy_coef / --item_loss_kl_coef need the native model (P5T5Native)")
             loader = self.train_loader if self.train_loader is not None else self.valid_loader
             seqs, seen = [], set()
             for ds in loader.dataset.datasets:
                 if ds.dataset not in seen:
                     seen.add(ds.dataset)
                     seqs += self._item_sequences(ds, list(ds.all_items))
-            kw = self._item_loss = {"trie": CompiledTrie.from_trie(Trie(seqs)), "temperature": float(getattr(self.args, "item_loss_temperature", 1.0))}
-            top_k, top_p = int(getattr(self.args, "item_loss_top_k", 0)), float(getattr(self.args, "item_loss_top_p", 1.0))
+            kw = {"trie": CompiledTrie.from_trie(Trie(seqs)), "temperature": float(getattr(self.args, "item_loss_temperature", 1.0))}
             if top_k != 0 or top_p != 1.0:          # (off: the keyword arguments of the untruncated loss, as before)
                 kw.update(top_k=top_k, top_p=top_p)
             if str(getattr(self.args, "item_loss_head", "dense")) == "trie":      # (dense: the keyword arguments of the run without the flag)
                 kw["item_head"] = "trie"
+            if ec != 0.0 or kc != 0.0:           # (both 0: the keyword arguments of the run without the flags)
+                kw.update(entropy_coef=ec, kl_coef=kc)
+                if kc != 0.0:
+                    # the frozen reference: this model's weights as they are NOW (the first call precedes the first step)
+                    kw["ref_model"] = self.model.frozen_copy()
+            self._item_loss = kw
         return kw
+
+    TRAIN_ONLY_ITEM_LOSS_KEYS = ("entropy_coef", "kl_coef", "ref_model")      # of training_step; `forward` (validation) does not take them
 
     @torch.no_grad()
     def validate(self):
@@ -441,7 +475,8 @@ class DistributedRunner:
         for batch in self.valid_loader:
             input_ids, attn, whole_ids, output_ids, output_attention = self._to_dev(batch)[:5]
             out = self.model(input_ids=input_ids, whole_word_ids=whole_ids, attention_mask=attn, labels=output_ids,
-                             alpha=self.args.alpha, return_dict=True, **(self._item_loss_kw() or {}))
+                             alpha=self.args.alpha, return_dict=True,
+                             **{k: v for k, v in (self._item_loss_kw() or {}).items() if k not in self.TRAIN_ONLY_ITEM_LOSS_KEYS})
             losses.append(masked_mean_loss(out["loss"], output_attention))
         v = torch.stack(losses).mean()
         if self.world > 1:
