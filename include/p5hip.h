@@ -692,6 +692,21 @@ int p5_op_trunc_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const
                             float gscale, void* stream);
 /* loss[0] = mean_b(sum_t nll[b, t] m[b, t] / max(sum_t m[b, t], 1)), m = (out_attn != 0) */
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
+/* The batch of an on-policy fine-tuning step from what p5_sample_items / p5_sample_slates returned (p5_policy.h), two launches on `stream`,
+ * no host synchronisation, no engine.  sequences int64 [B*S, Ts] (decoder start first, the drawn tokens through eos_id, pad_id behind; an
+ * all-pad row = nothing drawn); labels / output_attention int64 [B, Tg]: every user's gold target (attended: output_attention != 0 in
+ * front of the first -100 label, which ends the gold); rewards fp32 [B, S] or NULL = the hit reward (1 where the draw equals the gold's attended tokens, else 0).
+ * baseline 0 none / 1 mean / 2 loo (S >= 2) / 3 grpo (adv_eps added to the population standard deviation).  With G = S + with_gold and
+ * To = max(Tg, Ts - 1): labels_out / attention_out int64 [B, G, To] (slot 0 the gold when with_gold, then the draws), rewards_out /
+ * advantages fp32 [B, S], weights_out fp32 [B, G] -- w[b, 0] = sft_coef G, w[b, s] = policy_coef A[b, s] G / S (times the draw's token count
+ * when token_sum): the target_weights of p5_forward_loss_targets --, user_stats fp32 [B, 4] (scratch of the second launch), stats fp32 [8]:
+ * mean reward of the existing draws, share of users whose draws differ in reward, mean |A|, share of draws equal to the gold, share of users
+ * with such a draw, users without a draw, 0, 0.  No atomics: equal inputs give equal bits.  Non-zero (p5_last_error) for S < 1, S > 1024,
+ * loo with S < 2, an unknown baseline, non-finite coefficients, NULL required pointers. */
+int p5_policy_batch(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards, int B, int S, int Ts,
+                    int Tg, int baseline, float policy_coef, float sft_coef, int token_sum, float adv_eps, int with_gold, int pad_id, int eos_id,
+                    int64_t* labels_out, int64_t* attention_out, float* rewards_out, float* advantages, float* weights_out, float* user_stats,
+                    float* stats, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];
  * amode 1: A = fp32 residual stream [M, K], normalised with T5LayerNorm weight `ln` by the kernel itself.
  * (K <= 1024 then).  epi: 0 store T (alpha), 1 relu store T, 2 fp32 atomic accumulate (split-K), 3 store fp32 (alpha), 4 fp32 += by one writer */

@@ -32,6 +32,7 @@
 #include "p5_trie_reg.h"
 #include "p5_item_head.h"
 #include "p5_trunc.h"
+#include "p5_policy.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -4853,6 +4854,31 @@ int p5_op_trunc_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream) {
   P5_REQUIRE(loss && nll && out_attn && B >= 1 && T >= 1, "masked_mean: arguments");
   P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss, nll, out_attn, B, T);
+  return P5_KCHECK();
+}
+// the batch of an on-policy step from the sampler's output (p5_policy.h): both launches, stateless
+int p5_policy_batch(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards, int B, int S, int Ts, int Tg,
+                    int baseline, float policy_coef, float sft_coef, int token_sum, float adv_eps, int with_gold, int pad_id, int eos_id,
+                    int64_t* labels_out, int64_t* attention_out, float* rewards_out, float* advantages, float* weights_out, float* user_stats,
+                    float* stats, void* stream) {
+  P5_REQUIRE(sequences && labels && output_attention, "policy_batch: null input pointer (sequences, labels, output_attention)");
+  P5_REQUIRE(labels_out && attention_out && rewards_out && advantages && weights_out && user_stats && stats, "policy_batch: null output pointer");
+  P5_REQUIRE(B >= 1 && Ts >= 2 && Tg >= 1 && Tg <= (1 << 24), "policy_batch: shapes B >= 1, Ts >= 2, 1 <= Tg <= 2^24");
+  P5_REQUIRE(S >= 1, "policy_batch: S >= 1 draws per user");
+  P5_REQUIRE(S <= P5_POLICY_MAX_S, "policy_batch: S <= 1024 draws per user");
+  P5_REQUIRE(baseline >= P5_BASELINE_NONE && baseline <= P5_BASELINE_GRPO, "policy_batch: unknown baseline (0 none, 1 mean, 2 loo, 3 grpo)");
+  P5_REQUIRE(baseline != P5_BASELINE_LOO || S >= 2, "policy_batch: the loo baseline needs S >= 2");
+  P5_REQUIRE(std::isfinite(policy_coef) && std::isfinite(sft_coef) && std::isfinite(adv_eps) && adv_eps >= 0.f, "policy_batch: non-finite coefficient (policy_coef, sft_coef, adv_eps)");
+  P5_REQUIRE((token_sum == 0 || token_sum == 1) && (with_gold == 0 || with_gold == 1), "policy_batch: token_sum and with_gold are 0 or 1");
+  P5PolicyArgs a;
+  a.seq = sequences; a.labels = labels; a.out_attn = output_attention; a.rewards = rewards;
+  a.labels_out = labels_out; a.attn_out = attention_out; a.rewards_out = rewards_out; a.adv = advantages; a.weights = weights_out; a.user_stats = user_stats;
+  a.S = S; a.Ts = Ts; a.Tg = Tg; a.To = Tg > Ts - 1 ? Tg : Ts - 1; a.baseline = baseline; a.token_sum = token_sum; a.with_gold = with_gold;
+  a.pad_id = pad_id; a.eos_id = eos_id; a.policy_coef = policy_coef; a.sft_coef = sft_coef; a.adv_eps = adv_eps;
+  P5_REQUIRE((int64_t)(S + with_gold) * a.To <= (int64_t)1 << 30, "policy_batch: G * To too large");
+  hipStream_t s = (hipStream_t)stream;
+  P5_LAUNCH(p5_policy_batch_kernel, dim3(B), dim3(256), 0, s, a);
+  P5_LAUNCH(p5_policy_stats_kernel, dim3(1), dim3(256), 0, s, stats, user_stats, B);
   return P5_KCHECK();
 }
 int p5_op_skinny_gemm(int dtype, int amode, const void* A, int lda, const float* ln, const void* W, int ldw, void* C, int ldc, int M, int N, int K,

@@ -863,6 +863,124 @@ class P5T5Native(nn.Module):
         self._engine_backward(None)
         return out[Bd * T]
 
+    # ------------------------------------------------------------------ on-policy fine-tuning (csrc/p5_policy.h)
+    POLICY_BASELINES = {"none": 0, "mean": 1, "loo": 2, "grpo": 3}
+    POLICY_STATS = ("reward_mean", "users_with_signal", "abs_advantage_mean", "hit_rate", "users_with_hit", "users_without_draw")
+    last_policy_batch = None      # of the last policy_step: the dict of policy_batch / its "stats", on the device
+    last_policy_stats = None
+
+    def _policy_args(self, num_samples, baseline, policy_coef, sft_coef, token_sum, adv_eps):
+        """the checked scalars of policy_batch / policy_step: (S, baseline code, policy_coef, sft_coef, token_sum, adv_eps, with_gold)"""
+        if isinstance(num_samples, bool) or int(num_samples) != num_samples or int(num_samples) < 1:
+            raise ValueError(f"num_samples={num_samples!r}: an integer >= 1 (draws per user)")
+        S = int(num_samples)
+        if baseline not in self.POLICY_BASELINES:
+            raise ValueError(f"baseline={baseline!r}: one of {sorted(self.POLICY_BASELINES)}")
+        if baseline == "loo" and S < 2:
+            raise ValueError(f'baseline="loo" needs num_samples >= 2 (got {S}): a draw\'s baseline is the mean of the OTHER draws')
+        pc, sc, eps = float(policy_coef), float(sft_coef), float(adv_eps)
+        if not (math.isfinite(pc) and math.isfinite(sc)):
+            raise ValueError(f"policy_coef={policy_coef!r}, sft_coef={sft_coef!r}: finite values")
+        if not (math.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"adv_eps={adv_eps!r}: a finite value >= 0")
+        return S, self.POLICY_BASELINES[baseline], pc, sc, 1 if token_sum else 0, eps, 0 if sc == 0.0 else 1
+
+    def _check_policy_shapes(self, B, S, Ts, labels, output_attention, with_gold):
+        """the grouped call a policy batch of these shapes becomes, held to `_check_targets` before anything is sampled or launched"""
+        if labels.dim() != 2 or labels.shape[0] != B:
+            raise ValueError(f"labels {tuple(labels.shape)}: the gold target of every user, [B, T] with B = {B}")
+        if tuple(output_attention.shape) != tuple(labels.shape):
+            raise ValueError(f"output_attention {tuple(output_attention.shape)} must match labels {tuple(labels.shape)}")
+        G, To = S + with_gold, max(int(labels.shape[1]), Ts - 1)
+        self._check_targets(B, torch.empty(B, G, To, dtype=torch.int64, device="meta"))
+        return G, To
+
+    @torch.no_grad()
+    def policy_batch(self, sequences, labels, output_attention, num_samples, rewards=None, baseline="loo", policy_coef=1.0, sft_coef=1.0,
+                     token_sum=False, adv_eps=1e-6):
+        """The batch of one on-policy (REINFORCE-style) step from drawn sequences, built on the device in two launches (csrc/p5_policy.h), no
+        host sync: for callers who bring their own sequences (`sample_slates` with num_samples = num_slates * slate_size) or rewards.
+        `sequences` int64 [B * S, Ts] as `sample_items` / `sample_slates` return them (an all-pad row: nothing drawn); `labels` /
+        `output_attention` [B, T]: every user's gold target (a label of -100 ends it: that position and everything behind it count as not
+        attended, as the engine scores nothing there); `rewards` fp32 [B, S] or None = the hit
+        reward (1 where the draw is the gold item, else 0).  `baseline`: "none" A = r; "mean" A = r - mean(r); "loo" A_s = r_s - mean of the
+        other draws' r (num_samples >= 2; a user with ONE existing draw gets A = 0); "grpo" A = (r - mean) / (population std + adv_eps) -- over
+        the draws that exist; a user whose rewards are all equal has A exactly 0.
+        Returns device tensors {"labels", "output_attention" [B, G, To], "target_weights" [B, G], "rewards", "advantages" [B, S], "stats" [8]}
+        with G = S + 1 (slot 0 = the gold) or G = S when sft_coef == 0, To = max(T, Ts - 1).  `loss_and_backward(labels, output_attention,
+        target_weights=...)` on them is sft_coef * mean_b nll(gold_b) + policy_coef * mean_b (1/S) sum_s A_bs nll(draw_bs), nll the token mean
+        or -- `token_sum` -- the token sum, whose gradient is REINFORCE's.  `stats`: the values named by `POLICY_STATS`, then two zeros."""
+        S, base, pc, sc, tsum, eps, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, adv_eps)
+        dev = self._be.device
+        if not torch.is_tensor(sequences) or sequences.dim() != 2 or sequences.shape[0] % S != 0 or sequences.shape[0] == 0 or sequences.shape[1] < 2:
+            raise ValueError(f"sequences {tuple(getattr(sequences, 'shape', ()))}: [B * num_samples, Ts] with num_samples = {S}, Ts >= 2")
+        B, Ts = sequences.shape[0] // S, int(sequences.shape[1])
+        labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
+        G, To = self._check_policy_shapes(B, S, Ts, labels, output_attention, with_gold)
+        if rewards is not None:
+            if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
+                raise ValueError(f"rewards {tuple(getattr(rewards, 'shape', ()))}: a tensor [B, S] = {(B, S)}")
+            rewards = rewards.to(device=dev, dtype=torch.float32).contiguous()
+        sequences, labels, output_attention = self._i64(sequences, dev), self._i64(labels, dev), self._i64(output_attention, dev)
+        lab_o = torch.empty(B, G, To, dtype=torch.int64, device=dev)
+        att_o = torch.empty(B, G, To, dtype=torch.int64, device=dev)
+        f = torch.empty(2 * B * S + B * G + 4 * B + 8, dtype=torch.float32, device=dev)       # rewards | advantages | weights | user stats | stats
+        r_o, a_o, w_o, us, st = torch.split(f, [B * S, B * S, B * G, 4 * B, 8])
+        self._be.check(self._lib.p5_policy_batch(_ptr(sequences), _ptr(labels), _ptr(output_attention), _ptr(rewards), B, S, Ts, int(labels.shape[1]), base,
+                                                 pc, sc, tsum, eps, with_gold, int(self.config.pad_token_id), int(self.config.eos_token_id), _ptr(lab_o),
+                                                 _ptr(att_o), _ptr(r_o), _ptr(a_o), _ptr(w_o), _ptr(us), _ptr(st), self._be.stream_ptr()), "p5_policy_batch")
+        return {"labels": lab_o, "output_attention": att_o, "target_weights": w_o.view(B, G), "rewards": r_o.view(B, S), "advantages": a_o.view(B, S),
+                "stats": st}
+
+    def policy_step(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=1.0, excluded_items=None,
+                    top_k=0, top_p=1.0, item_head=None, baseline="loo", policy_coef=1.0, sft_coef=1.0, token_sum=False, reward_fn=None, seed=None,
+                    streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None):
+        """One on-policy fine-tuning step: (1) `sample_items(num_samples=...)` with the trie, temperature, exclusion and truncation the loss
+        uses -- that sameness is what on-policy means here; (2) `policy_batch` on the draws (`reward_fn`, if given, is called with the
+        sampler's dict and returns fp32 [B, S] on the device; else the hit reward against `labels`); (3) `loss_and_backward` on the grouped
+        batch [B, G, To] with the advantages as `target_weights`.  With `kl_coef != 0`, `ref_model` (a `frozen_copy()`) supplies `ref_logits`
+        of the grouped labels; entropy and KL keep the meaning and the limits of `loss_and_backward` (not under top_k / top_p).
+        Returns the loss as a 0-dim tensor, gradients in `.grad`; `last_policy_batch` (the dict of `policy_batch`) and `last_policy_stats`
+        (fp32 [8], `POLICY_STATS`) stay on the device, no host sync.  The limits of a grouped call (G * To <= 512, ...) are checked before
+        anything is sampled.  Sampling ignores `self.training` (no dropout in the draw, as in `sample_items`); the training forward applies
+        dropout as usual, so under dropout the draws come from the dropout-free policy.  `seed` / `streams`: those of `sample_items`."""
+        if trie is None:
+            raise ValueError("policy_step needs trie=...: the draws and the item loss share it")
+        S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
+        item_head = self._item_head_mode(item_head, trie)
+        top_k, top_p = self._truncation(top_k, top_p)
+        ec, kc = float(entropy_coef), float(kl_coef)
+        if ec != 0.0 or kc != 0.0:
+            if top_k > 0 or top_p < 1.0:
+                raise ValueError("entropy_coef / kl_coef are not built for the truncated item loss (top_k / top_p)")
+            if not (math.isfinite(ec) and math.isfinite(kc)):
+                raise ValueError(f"entropy_coef={entropy_coef!r}, kl_coef={kl_coef!r}: finite values")
+            if kc != 0.0 and ref_model is None:
+                raise ValueError(f"kl_coef={kl_coef!r} needs ref_model (a frozen_copy() of the reference policy)")
+        trie = self._compiled_trie(trie)
+        input_ids = torch.as_tensor(input_ids)
+        B = int(input_ids.shape[0])
+        depth = int(trie.max_depth)
+        Ts = max(2, depth)
+        labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
+        self._check_policy_shapes(B, S, Ts, labels, output_attention, with_gold)
+        drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
+                                  temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams, top_k=top_k, top_p=top_p)
+        rewards = None if reward_fn is None else reward_fn(drawn)
+        pb = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=rewards, baseline=baseline, policy_coef=policy_coef,
+                               sft_coef=sft_coef, token_sum=token_sum)
+        kw = {}
+        if ec != 0.0 or kc != 0.0:
+            kw.update(entropy_coef=ec, kl_coef=kc)
+            if kc != 0.0:
+                kw["ref_logits"] = ref_model.item_logits(input_ids, whole_word_ids, attention_mask, pb["labels"], trie, temperature=temperature,
+                                                         excluded_items=excluded_items, item_head=item_head)
+        loss = self.loss_and_backward(input_ids, whole_word_ids, attention_mask, pb["labels"], pb["output_attention"], trie=trie, temperature=temperature,
+                                      excluded_items=excluded_items, top_k=top_k, top_p=top_p, item_head=item_head, target_weights=pb["target_weights"],
+                                      **kw)
+        self.last_policy_batch, self.last_policy_stats = pb, pb["stats"]
+        return loss
+
     def _advance_dropout_step(self):
         self._rng_cpu[1] = (self._rng_cpu[1] + 1) & 0xFFFFFFFF
         self._rng[1] = self._rng_cpu[1] if self._rng_cpu[1] < 2 ** 31 else self._rng_cpu[1] - 2 ** 32

@@ -88,6 +88,17 @@ def parse_runner_args(parser):
                         "KL(policy || reference) over the same children); needs --item_loss_kl_ref; 0 = off")
     parser.add_argument("--item_loss_kl_ref", type=str, default="", choices=["", "init"], help="reference policy of --item_loss_kl_coef: init = a frozen "
                         "copy of the model's weights at the start of training (eval mode, same dtype, no optimizer, not data-parallel)")
+    parser.add_argument("--train_policy_samples", type=int, default=0, help="S > 0 = on-policy fine-tuning (P5T5Native.policy_step; needs "
+                        "--train_item_loss 1 and the native model): every step draws S items per user from the model's own distribution on the "
+                        "item trie, rewards a draw that is the gold item with 1, and trains on the gold (--policy_sft_coef) and on the draws weighted "
+                        "by their advantages (--policy_coef).  0 = off, nothing changes.")
+    parser.add_argument("--policy_baseline", type=str, default="loo", choices=["loo", "mean", "grpo", "none"], help="advantage of a draw: its reward "
+                        "minus the mean of the user's OTHER draws (loo, S >= 2), minus the user's mean (mean), that divided by the user's standard "
+                        "deviation (grpo), or the reward itself (none)")
+    parser.add_argument("--policy_coef", type=float, default=1.0, help="weight of the policy-gradient term")
+    parser.add_argument("--policy_sft_coef", type=float, default=1.0, help="weight of the likelihood of the gold item (0 = the draws alone)")
+    parser.add_argument("--policy_token_sum", type=int, default=0, choices=[0, 1], help="1 = a draw's term is the SUM of its tokens' NLL (REINFORCE "
+                        "proper) instead of their mean")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -117,7 +128,15 @@ def masked_mean_loss(nll, output_attention):
     return (loss.sum(dim=1) / m.sum(dim=1).clamp(min=1)).mean()
 
 
-def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=None):
+def policy_seed(seed, step, micro, rank):
+    """The sampling seed of an on-policy step: a pure function of (--seed, optimizer step index, micro-batch index, rank), so that a resumed
+    run draws what the uninterrupted run would have drawn (no state of its own in the resume file)."""
+    from .model import P5T5Native
+    mix = P5T5Native._mix32
+    return mix(mix(mix(mix(int(seed) + 0x9E3779B9) ^ (int(step) & 0xFFFFFFFF)) ^ (int(micro) & 0xFFFFFFFF)) ^ (int(rank) & 0xFFFFFFFF))
+
+
+def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=None, policy=None):
     """One pass of the reference loop body (DistributedRunner.py:63-87): forward, masked-mean loss, backward, clip + AdamW +
     scheduler (fused), zero_grad.  `batch` = (input_ids, whole_word_ids, attention_mask, labels, output_attention) on the
     device.  With the native model the loss and its gradient seed are computed by the engine
@@ -133,20 +152,28 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
     `item_loss` (None = the full-vocabulary cross-entropy): keyword arguments of the native model's trie-normalised item loss --
     {"trie": ..., "temperature": ...[, "top_k": ..., "top_p": ...]} (`P5T5Native.forward`); with "entropy_coef" / "kl_coef" (native model
     only) the loss gains the regularisers of `P5T5Native.loss_and_backward`, and "ref_model" (a frozen `P5T5Native`) supplies the
-    reference's `item_logits` of the batch when kl_coef != 0."""
+    reference's `item_logits` of the batch when kl_coef != 0.
+
+    `policy` (None = off): keyword arguments of `P5T5Native.policy_step` on top of `item_loss` -- {"num_samples", "baseline", "policy_coef",
+    "sft_coef", "token_sum", "seed"}: the step samples, rewards, weights and trains in one call."""
     kw = dict(item_loss or {})
     input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
     fused = getattr(model, "loss_and_backward", None)
     ref_model = kw.pop("ref_model", None)
     if fused is None and [kw.pop(k, 0.0) for k in ("entropy_coef", "kl_coef")] != [0.0, 0.0]:
         raise ValueError("item-loss regularisers (entropy_coef / kl_coef) need the native model")
-    if ref_model is not None and kw.get("kl_coef", 0.0) != 0.0:
+    if ref_model is not None and kw.get("kl_coef", 0.0) != 0.0 and policy is None:
         kw["ref_logits"] = ref_model.item_logits(input_ids, whole_ids, attn, output_ids, kw["trie"], temperature=kw.get("temperature", 1.0),
                                                  item_head=kw.get("item_head"))
     last = micro == accum - 1
     if fused is not None and hasattr(model, "begin_micro_batch"):
         model.begin_micro_batch(first=micro == 0, sync=last)
-    if fused is not None:
+    if policy is not None:
+        if not hasattr(model, "policy_step") or "trie" not in kw:
+            raise ValueError("the on-policy step needs the native model and the item loss's keywords (trie=...)")
+        kw.pop("ref_logits", None)         # (policy_step takes the reference's logits on the grouped labels itself)
+        loss = model.policy_step(input_ids, whole_ids, attn, output_ids, output_attention, ref_model=ref_model, **kw, **policy)
+    elif fused is not None:
         loss = fused(input_ids, whole_ids, attn, output_ids, output_attention, **kw)
     else:
         out = model(input_ids=input_ids, whole_word_ids=whole_ids, attention_mask=attn, labels=output_ids, alpha=alpha, return_dict=True, **kw)
@@ -232,6 +259,7 @@ class DistributedRunner:
         self.metrics = args.metrics.split(",")
         self.generate_num = max(int(m.split("@")[1]) for m in self.metrics)
         self.get_testloader()
+        self._policy = self._policy_flags()          # (raises now, not at the first step)
         if args.train:
             self.optimizer, self.scheduler = self.create_optimizer_and_scheduler()
         self.samples_per_sec = None
@@ -375,8 +403,19 @@ class DistributedRunner:
                 g0 = (n_batches - 1) // accum * accum
                 gsize = min(accum, n_total - g0)
                 micro = n_batches - 1 - g0
-                loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
-                                     micro=micro, accum=gsize, item_loss=self._item_loss_kw())
+                if self._policy is None:
+                    loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
+                                         micro=micro, accum=gsize, item_loss=self._item_loss_kw())
+                else:
+                    pol = dict(self._policy, seed=policy_seed(getattr(self.args, "seed", 0), self.optimizer.t, micro, self.rank))
+                    loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
+                                         micro=micro, accum=gsize, item_loss=self._item_loss_kw(), policy=pol)
+                    # the one host read of the statistics -- and of this batch's loss: this runner logs no per-batch loss elsewhere, so with the
+                    # flag on rank 0 synchronises with the device once per --logging_step batches; with the flag off nothing is read
+                    if self.rank == 0 and n_batches % max(1, int(self.args.logging_step)) == 0:
+                        st = [float(x) for x in self.model.last_policy_stats[:6].cpu()]
+                        logging.info(f"policy step {self.optimizer.t} batch {n_batches}: loss {float(loss):.6f} "
+                                     + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.POLICY_STATS, st)))
                 losses.append(loss)
                 n_samples += input_ids.shape[0]
                 if resume and save_steps > 0 and micro == gsize - 1 and self.optimizer.t % save_steps == 0:
@@ -423,6 +462,27 @@ class DistributedRunner:
                 torch.save(self.model.state_dict(), self.args.model_path)
                 logging.info(f"Save the current model to {self.args.model_path}")
         return train_losses
+
+    def _policy_flags(self):
+        """--train_policy_samples S: the keyword arguments of `P5T5Native.policy_step` (None with the flag at 0), every flag checked here."""
+        S = int(getattr(self.args, "train_policy_samples", 0))
+        if S == 0:
+            return None
+        if S < 0:
+            raise ValueError(f"--train_policy_samples {S}: the number of draws per user (0 = off)")
+        if not int(getattr(self.args, "train_item_loss", 0)):
+            raise ValueError("--train_policy_samples requires --train_item_loss 1 (the draws and the loss share the union item trie)")
+        if not hasattr(self.model, "policy_step"):
+            raise ValueError("--train_policy_samples needs the native model (P5T5Native)")
+        baseline = str(getattr(self.args, "policy_baseline", "loo"))
+        if baseline not in ("loo", "mean", "grpo", "none"):
+            raise ValueError(f"--policy_baseline {baseline}: loo, mean, grpo or none")
+        if baseline == "loo" and S < 2:
+            raise ValueError("--policy_baseline loo needs --train_policy_samples >= 2")
+        pc, sc = float(getattr(self.args, "policy_coef", 1.0)), float(getattr(self.args, "policy_sft_coef", 1.0))
+        if not (math.isfinite(pc) and math.isfinite(sc)):
+            raise ValueError(f"--policy_coef {pc} / --policy_sft_coef {sc}: finite values")
+        return {"num_samples": S, "baseline": baseline, "policy_coef": pc, "sft_coef": sc, "token_sum": bool(int(getattr(self.args, "policy_token_sum", 0)))}
 
     def _item_loss_kw(self):
         """--train_item_loss 1: the keyword arguments of the trie-normalised item loss -- ONE union trie over the items of all training
