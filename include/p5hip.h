@@ -692,6 +692,12 @@ int p5_op_trunc_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const
                             float gscale, void* stream);
 /* loss[0] = mean_b(sum_t nll[b, t] m[b, t] / max(sum_t m[b, t], 1)), m = (out_attn != 0) */
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream);
+/* The loss of p5_forward_loss_targets and its gradient with respect to the per-token NLL: loss[0] = mean_b(tw[b] * masked mean of nll[b, :]),
+ * g_out [B * T] = out_attn != 0 ? gscale / max(count of the row's b, 1) * tw[b] : 0, and 0 where labels == -100 (tw may be NULL = 1).
+ * merged 1: one launch (p5_masked_mean_g_kernel, the engine's route under p5_set_option("loss_fuse", 1)); merged 0: the loss kernel and the
+ * stand-alone scale kernel.  Both give the same bits. */
+int p5_op_masked_mean_g(int merged, float* loss, float* g_out, const float* nll, const int64_t* out_attn, const int64_t* labels, const float* tw, int B, int T,
+                        float gscale, void* stream);
 /* The batch of an on-policy fine-tuning step from what p5_sample_items / p5_sample_slates returned (p5_policy.h), two launches on `stream`,
  * no host synchronisation, no engine.  sequences int64 [B*S, Ts] (decoder start first, the drawn tokens through eos_id, pad_id behind; an
  * all-pad row = nothing drawn); labels / output_attention int64 [B, Tg]: every user's gold target (attended: output_attention != 0 in

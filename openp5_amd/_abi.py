@@ -142,6 +142,7 @@ PROTOTYPES = {
     "p5_op_trunc_ce_fwd_cols": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, f32, i32, i32, i32, vp]),
     "p5_op_trunc_ce_bwd_cols": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, vp, f32, vp]),
     "p5_op_masked_mean": (i32, [vp, vp, vp, i32, i32, vp]),
+    "p5_op_masked_mean_g": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "p5_policy_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),

@@ -12,12 +12,21 @@
 template <class T>
 __global__ __launch_bounds__(256) void p5_embed_fwd_kernel(T* __restrict__ out, const T* __restrict__ E, const T* __restrict__ WW,
                                                           const int64_t* __restrict__ ids, const int64_t* __restrict__ ww,
-                                                          int rows, int d, P5Drop drop, float* __restrict__ ssq_part = nullptr) {
+                                                          int rows, int d, P5Drop drop, float* __restrict__ ssq_part = nullptr,
+                                                          const int64_t* __restrict__ shift_labels = nullptr, int64_t* __restrict__ ids_out = nullptr,
+                                                          int Tlen = 1, int64_t start = 0) {
   constexpr int EPF = TT<T>::EPF;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const int64_t id = ids[row];
+  int64_t id;
+  if (shift_labels) {      // (uniform) the decoder's lookup: the label to the left, the start token at t = 0 and for an ignored label (the shift-right
+    id = row % Tlen == 0 ? start : shift_labels[row - 1];      //  of p5_shift_right_kernel), stored for the backward and the embedding gradient
+    if (id == -100) id = start;
+    if (lane == 0) ids_out[row] = id;
+  } else {
+    id = ids[row];
+  }
   const int64_t w = WW ? ww[row] : 0;
   const bool do_drop = drop.state != nullptr && drop.thr != 0;
   const uint32_t seed = p5_seed(drop);

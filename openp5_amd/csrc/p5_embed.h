@@ -7,7 +7,7 @@
 // profiles/r04_repro_before_fix.txt): two runs of the same training differed by up to 2 x lr.  Here the rows are summed in a FIXED order:
 //   1. p5_embed_sortchunk_kernel + p5_embed_rank_kernel
 //                               stable rank of every lookup row by (key, row): sorted position, start and length of its key's segment
-//                               (chunks of 256 rows sorted in LDS, then one binary search per row and chunk -- integer comparisons only);
+//                               (chunks of 256 rows sorted in LDS, then binary searches per row and chunk -- integer comparisons only);
 //   2. p5_embed_seg_kernel      one workgroup per block of 32 sorted positions: rows of one key are added in row order; a segment that
 //                               lies inside the block is added to the table row by its only owner (plain read-modify-write), pieces of
 //                               segments that cross block boundaries go to a partial buffer;
@@ -46,7 +46,7 @@ __device__ static __forceinline__ int emb_key(const P5EmbSet& s, int r) { return
 //                               -> `csort` (sorted chunks, back to back);
 //   p5_embed_rank_kernel        one thread per row: its rank = sum over ALL chunks of the number of values below its own (a binary
 //                               search per chunk, chunks staged through LDS), likewise the start and the end of its key's segment
-//                               (values below key << 32 / below (key + 1) << 32).
+//                               (values below key << 32 / below (key + 1) << 32); the three searches of two chunks run in lockstep.
 // Integer comparisons only: the same permutation on every run.
 #define P5_EMB_CHUNK 256
 __global__ __launch_bounds__(256) void p5_embed_sortchunk_kernel(P5EmbArgs a) {
@@ -71,22 +71,39 @@ __global__ __launch_bounds__(256) void p5_embed_sortchunk_kernel(P5EmbArgs a) {
   s.csort[(size_t)blockIdx.x * P5_EMB_CHUNK + threadIdx.x] = sv[threadIdx.x];
 }
 
-// number of values of the sorted array v[0..m) that are < x
-__device__ static __forceinline__ int emb_lower_bound(const unsigned long long* v, int m, unsigned long long x) {
-  int lo = 0, hi = m;
-#pragma unroll 1
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (v[mid] < x) lo = mid + 1; else hi = mid;
+// number of values of the sorted chunk v[0..256) that are < x: eight halving steps over v[0..255), then the last value.  No branch and no
+// data-dependent trip count, so several searches written side by side advance in lockstep and their LDS reads overlap.
+__device__ static __forceinline__ void emb_count_below(const unsigned long long* const (&v)[2], const unsigned long long (&x)[3], int (&cnt)[2][3]) {
+  int p[2][3] = {};
+#pragma unroll
+  for (int s = P5_EMB_CHUNK / 2; s > 0; s >>= 1) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) p[h][q] += v[h][p[h][q] + s - 1] < x[q] ? s : 0;
+    }
   }
-  return lo;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) cnt[h][q] = p[h][q] + (v[h][p[h][q]] < x[q] ? 1 : 0);
+  }
 }
 
+typedef unsigned long long emb_u64x2 __attribute__((ext_vector_type(2), aligned(8)));
+
 // grid (ceil(max n / 64), nsets), 256 threads: lane = one of 64 rows, wave w searches the chunks c = w (mod 4) of every LDS batch
-// (16 sorted chunks = 32 KiB at a time); the four waves' counts are added through LDS
+// (16 sorted chunks = 32 KiB at a time); the four waves' counts are added through LDS.
+// A batch is fetched with eight 16-byte loads per thread that are all in flight together (clamped addresses: the tail of a short last batch
+// re-reads the batch's first pair and lands in LDS nobody searches), and the next batch is requested before the current one is searched.
+// A wave takes two chunks at a time and runs their six counts (values below key << 32, below (key + 1) << 32, below the row's own value) as
+// one lockstep search of nine dependent LDS reads.  (Until round 7 the staging loop waited for each of its 8-byte loads before issuing
+// the next -- 34 dependent round trips to L2 per workgroup at n = 8704 -- and the three counts of a chunk were three searches one after the
+// other, about 17 dependent LDS reads per chunk; the counts, and with them perm / skey / sstart / slen, are the same integers.)
 __global__ __launch_bounds__(256) void p5_embed_rank_kernel(P5EmbArgs a) {
   constexpr int CPB = 16;                 // chunks per LDS batch
-  __shared__ unsigned long long sc[CPB * P5_EMB_CHUNK];
+  constexpr int NLD = CPB * P5_EMB_CHUNK / 2 / 256;      // 16-byte loads per thread and batch
+  __shared__ __attribute__((aligned(16))) unsigned long long sc[CPB * P5_EMB_CHUNK];
   __shared__ int scnt[3][4][64];
   const P5EmbSet& s = a.s[blockIdx.y];
   const int n = s.n0 + s.n1;
@@ -94,103 +111,158 @@ __global__ __launch_bounds__(256) void p5_embed_rank_kernel(P5EmbArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = blockIdx.x * 64 + lane;
   const int k = r < n ? emb_key(s, r) : 0;
-  const unsigned long long me = (((unsigned long long)(unsigned)k) << 32) | (unsigned)r;
-  const unsigned long long klo = ((unsigned long long)(unsigned)k) << 32, khi = ((unsigned long long)(unsigned)k + 1ull) << 32;
+  const unsigned long long x[3] = {((unsigned long long)(unsigned)k) << 32, ((unsigned long long)(unsigned)k + 1ull) << 32,
+                                   (((unsigned long long)(unsigned)k) << 32) | (unsigned)r};      // start, end, own position
   const int nchunks = (n + P5_EMB_CHUNK - 1) / P5_EMB_CHUNK;
-  int pos = 0, start = 0, end = 0;
+  emb_u64x2 t[NLD];
+  auto fetch = [&](int c0) {
+    const int lim = (nchunks - c0 < CPB ? nchunks - c0 : CPB) * P5_EMB_CHUNK;
+    const unsigned long long* src = s.csort + (size_t)c0 * P5_EMB_CHUNK;
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) {
+      const int i = (q * 256 + (int)threadIdx.x) * 2;
+      t[q] = *(const emb_u64x2*)(src + (i < lim ? i : 0));
+    }
+  };
+  fetch(0);
+  int tot[3] = {0, 0, 0};
   for (int c0 = 0; c0 < nchunks; c0 += CPB) {
     const int nc = nchunks - c0 < CPB ? nchunks - c0 : CPB;
     __syncthreads();
-    for (int i = threadIdx.x; i < nc * P5_EMB_CHUNK; i += 256) sc[i] = s.csort[(size_t)c0 * P5_EMB_CHUNK + i];
+#pragma unroll
+    for (int q = 0; q < NLD; ++q) *(emb_u64x2*)(sc + (q * 256 + (int)threadIdx.x) * 2) = t[q];
     __syncthreads();
-    for (int c = wave; c < nc; c += 4) {
-      const unsigned long long* v = sc + c * P5_EMB_CHUNK;
-      const int lo = emb_lower_bound(v, P5_EMB_CHUNK, klo);      // (padding values ~0 are above every real value)
-      start += lo;
-      // the chunk's values of this key form the run [lo, hi): search the rest inside it
-      const int hi = lo + emb_lower_bound(v + lo, P5_EMB_CHUNK - lo, khi);
-      end += hi;
-      pos += lo + emb_lower_bound(v + lo, hi - lo, me);
+    if (c0 + CPB < nchunks) fetch(c0 + CPB);      // (uniform) lands while this batch is searched
+    for (int c = wave; c < nc; c += 8) {
+      const bool two = c + 4 < nc;                // (uniform)
+      const unsigned long long* const v[2] = {sc + c * P5_EMB_CHUNK, sc + (two ? c + 4 : c) * P5_EMB_CHUNK};
+      int cnt[2][3];
+      emb_count_below(v, x, cnt);                 // (padding values ~0 are above every real value)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) tot[q] += cnt[0][q] + (two ? cnt[1][q] : 0);
     }
   }
-  scnt[0][wave][lane] = pos; scnt[1][wave][lane] = start; scnt[2][wave][lane] = end;
+  scnt[0][wave][lane] = tot[2]; scnt[1][wave][lane] = tot[0]; scnt[2][wave][lane] = tot[1];
   __syncthreads();
   if (wave == 0 && r < n) {
-    pos = scnt[0][0][lane] + scnt[0][1][lane] + scnt[0][2][lane] + scnt[0][3][lane];
-    start = scnt[1][0][lane] + scnt[1][1][lane] + scnt[1][2][lane] + scnt[1][3][lane];
-    end = scnt[2][0][lane] + scnt[2][1][lane] + scnt[2][2][lane] + scnt[2][3][lane];
+    const int pos = scnt[0][0][lane] + scnt[0][1][lane] + scnt[0][2][lane] + scnt[0][3][lane];
+    const int start = scnt[1][0][lane] + scnt[1][1][lane] + scnt[1][2][lane] + scnt[1][3][lane];
+    const int end = scnt[2][0][lane] + scnt[2][1][lane] + scnt[2][2][lane] + scnt[2][3][lane];
     s.perm[pos] = r; s.skey[pos] = k; s.sstart[pos] = start; s.slen[pos] = end - start;
   }
 }
 
-// value of lookup row `r`, columns c..c+1 (dropout of the forward re-applied)
-__device__ static __forceinline__ void emb_row2(const P5EmbSet& s, int r, int d, int c, uint32_t seed0, uint32_t seed1, float& x0, float& x1) {
-  const bool first = r < s.n0;
-  const int lr = first ? r : r - s.n0;
-  const float* src = (first ? s.dres0 : s.dres1) + (size_t)lr * d + c;
-  const P5Drop& dp = first ? s.drop0 : s.drop1;
-  x0 = src[0]; x1 = src[1];
-  if (dp.state != nullptr && dp.thr != 0) {
-    const uint32_t seed = first ? seed0 : seed1;
-    const uint32_t i0 = (uint32_t)(lr * d + c);
-    x0 = p5_keep(seed, dp.site_key, i0, dp.thr) ? x0 * dp.scale : 0.f;
-    x1 = p5_keep(seed, dp.site_key, i0 + 1, dp.thr) ? x1 * dp.scale : 0.f;
+typedef float emb_f4 __attribute__((ext_vector_type(4), aligned(4)));      // 16-byte access of four columns (rows are only known to be float-aligned)
+// a pointer read back from LDS has lost its address space: say "global" again, or the loads are compiled as flat ones
+#ifdef P5_EMU
+#define EMB_GLOBAL
+#else
+#define EMB_GLOBAL __attribute__((address_space(1)))
+#endif
+
+// 0 in a vector register the compiler cannot see through: an LDS index `j + emb_vzero()` keeps what is read there in vector registers.
+// (Read with a plain constant index, the 64 staged row pointers of a block are all moved to scalar registers, which do not hold them:
+// the compiled kernel spilled several hundred of them into lanes of vector registers.)
+__device__ static __forceinline__ int emb_vzero() {
+  int z = 0;
+#ifndef P5_EMU
+  asm volatile("" : "+v"(z));
+#endif
+  return z;
+}
+
+// one half (positions H0 .. H0 + 15) of a block of p5_embed_seg_kernel, columns c..c+3: all loads, then dropout, then the adds
+template <int H0>
+__device__ static __forceinline__ void emb_seg_half(const P5EmbSet& s, const float* const* srow, const float* const* sown, const int* slr, const int* sk,
+                                                    const int* sst, const int* sln, int p0, int cnt, int d, int c, int z, uint32_t seed0, uint32_t seed1,
+                                                    bool use0, bool use1, float (&acc)[4]) {
+  constexpr int S = P5_EMB_SEG, HB = S / 2;
+  emb_f4 v[HB], o[HB];
+#pragma unroll
+  for (int i = 0; i < HB; ++i) v[i] = *(const EMB_GLOBAL emb_f4*)(srow[H0 + i + z] + c);
+#pragma unroll
+  for (int i = 0; i < HB; ++i) o[i] = *(const EMB_GLOBAL emb_f4*)(sown[H0 + i + z] + c);
+  P5_SCHED_FENCE();                               // (the scalar work of the dropout and of the adds stays below the loads)
+  if (use0 || use1) {                             // (uniform) the forward's dropout, same element index and scale
+#pragma unroll
+    for (int i = 0; i < HB; ++i) {
+      const int lr = slr[H0 + i];                 // local row; bit 31 set: a row of the second key array
+      const bool first = lr >= 0;
+      if (first ? use0 : use1) {                  // (uniform)
+        const uint32_t seed = first ? seed0 : seed1, site_key = first ? s.drop0.site_key : s.drop1.site_key;
+        const uint32_t thr = first ? s.drop0.thr : s.drop1.thr;
+        const float scale = first ? s.drop0.scale : s.drop1.scale;
+        const uint32_t i0 = (uint32_t)((lr & 0x7fffffff) * d + c);
+        v[i].x = p5_keep(seed, site_key, i0, thr) ? v[i].x * scale : 0.f;
+        v[i].y = p5_keep(seed, site_key, i0 + 1, thr) ? v[i].y * scale : 0.f;
+        v[i].z = p5_keep(seed, site_key, i0 + 2, thr) ? v[i].z * scale : 0.f;
+        v[i].w = p5_keep(seed, site_key, i0 + 3, thr) ? v[i].w * scale : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < HB; ++i) {
+    const int j = H0 + i;
+    if (j < cnt) {                                // (uniform)
+      acc[0] += v[i].x; acc[1] += v[i].y; acc[2] += v[i].z; acc[3] += v[i].w;
+      if (sk[j + 1] != sk[j]) {                   // (uniform) the last row of its key in this block
+        const int ss = sst[j], se = ss + sln[j];
+        const bool head = ss < p0, tail = se > p0 + S;
+        if (!head && !tail) {
+          *(emb_f4*)(s.table + (size_t)sk[j] * d + c) = (emb_f4){o[i].x + acc[0], o[i].y + acc[1], o[i].z + acc[2], o[i].w + acc[3]};
+        } else {
+          *(emb_f4*)(s.part + ((size_t)blockIdx.x * 2 + (head ? 0 : 1)) * d + c) = (emb_f4){acc[0], acc[1], acc[2], acc[3]};
+        }
+        acc[0] = 0.f; acc[1] = 0.f; acc[2] = 0.f; acc[3] = 0.f;
+      }
+    }
   }
 }
 
-// grid (ceil(max n / 32), nsets), 256 threads = 512 columns per pass
+// grid (ceil(max n / 32), nsets), 256 threads = 1024 columns per pass (four per thread).
+// The block's 32 positions are handled as two halves of 16.  A half first REQUESTS everything it reads -- its 16 gradient rows and the
+// table rows of the segments that end in it and lie inside the block (distinct keys, this workgroup their only writer) -- and only then
+// adds.  For that the loads carry no control flow: the first 32 threads work out one row pointer and one table-row pointer per position
+// and stage them in LDS; a position past the end of the set repeats the set's last position, a position that owns no table row requests
+// its own gradient row a second time (a cache hit), and dropout is applied to the registers after the loads.  (Until round 7 the loop
+// read "every row is requested before the first add", but the guards `if (j < cnt)`, `if (last)` and the per-row choice of the dropout
+// descriptor were branches, and the compiled kernel waited for every one of its 64 loads before issuing the next: 64 dependent round
+// trips per workgroup, 48 us per launch at the C2 shape for 35 MB of reads.)
+// The association is unchanged: rows of a key are added in sorted order starting from 0; a segment inside the block writes
+// table_old + a; a piece of a segment that crosses a block boundary goes to part[block][0 (continues from before) | 1 (continues after)].
 __global__ __launch_bounds__(256) void p5_embed_seg_kernel(P5EmbArgs a) {
   constexpr int S = P5_EMB_SEG;
-  __shared__ int sp[S], sk[S], sst[S], sln[S];
+  __shared__ const float* srow[S];
+  __shared__ const float* sown[S];
+  __shared__ int slr[S], sk[S + 1], sst[S], sln[S];
   const P5EmbSet& s = a.s[blockIdx.y];
   const int n = s.n0 + s.n1, d = a.d;
   const int p0 = blockIdx.x * S;
   if (p0 >= n) return;
   const int cnt = n - p0 < S ? n - p0 : S;
   if (threadIdx.x < S) {
-    const int p = p0 + threadIdx.x;
-    const bool ok = threadIdx.x < cnt;
-    sp[threadIdx.x] = ok ? s.perm[p] : 0; sk[threadIdx.x] = ok ? s.skey[p] : -1;
-    sst[threadIdx.x] = ok ? s.sstart[p] : 0; sln[threadIdx.x] = ok ? s.slen[p] : 0;
+    const int t = threadIdx.x;
+    const bool ok = t < cnt;
+    const int p = p0 + (ok ? t : cnt - 1);        // (clamped: a padding position names a row that exists)
+    const int r = s.perm[p], key = s.skey[p], ss = s.sstart[p], ln = s.slen[p];
+    const int next = t + 1 < cnt ? s.skey[p + 1] : -1;
+    const bool first = r < s.n0;
+    const int lr = first ? r : r - s.n0;
+    const float* src = (first ? s.dres0 : s.dres1) + (size_t)lr * d;
+    const bool own = ok && next != key && ss >= p0 && ss + ln <= p0 + S;
+    srow[t] = src; sown[t] = own ? s.table + (size_t)key * d : src;
+    slr[t] = first ? lr : (lr | (int)0x80000000);
+    sk[t] = ok ? key : -1; sst[t] = ss; sln[t] = ln;
+    if (t == 0) sk[S] = -1;
   }
   __syncthreads();
   const uint32_t seed0 = p5_seed(s.drop0), seed1 = p5_seed(s.drop1);
-  for (int c = threadIdx.x * 2; c < d; c += 512) {
-    float v0[S], v1[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {                 // every row of the block is requested before the first add
-      v0[j] = 0.f; v1[j] = 0.f;
-      if (j < cnt) emb_row2(s, sp[j], d, c, seed0, seed1, v0[j], v1[j]);
-    }
-    // the table rows this block owns (segments that lie inside it: distinct keys, distinct rows, this workgroup their only writer) are
-    // requested up front as well: `dst += a` row by row was one dependent HBM round trip per key (48 us per launch at the C2 shape for
-    // 35 MB of reads; round 6)
-    float o0[S], o1[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      o0[j] = 0.f; o1[j] = 0.f;
-      if (j < cnt && (j == cnt - 1 || sk[j + 1] != sk[j])) {       // (uniform)
-        const int ss = sst[j], se = ss + sln[j];
-        if (ss >= p0 && se <= p0 + S) {
-          const float* src = s.table + (size_t)sk[j] * d + c;
-          o0[j] = src[0]; o1[j] = src[1];
-        }
-      }
-    }
-    float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-      if (j >= cnt) break;                        // (uniform)
-      a0 += v0[j]; a1 += v1[j];
-      const bool last = j == cnt - 1 || sk[j + 1] != sk[j];       // (uniform)
-      if (last) {
-        const int ss = sst[j], se = ss + sln[j];
-        const bool head = ss < p0, tail = se > p0 + S;
-        float* dst = (!head && !tail) ? s.table + (size_t)sk[j] * d + c : s.part + ((size_t)blockIdx.x * 2 + (head ? 0 : 1)) * d + c;
-        if (!head && !tail) { dst[0] = o0[j] + a0; dst[1] = o1[j] + a1; } else { dst[0] = a0; dst[1] = a1; }
-        a0 = 0.f; a1 = 0.f;
-      }
-    }
+  const bool use0 = s.drop0.state != nullptr && s.drop0.thr != 0, use1 = s.drop1.state != nullptr && s.drop1.thr != 0;
+  const int z = emb_vzero();
+  for (int c = threadIdx.x * 4; c < d; c += 1024) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    emb_seg_half<0>(s, srow, sown, slr, sk, sst, sln, p0, cnt, d, c, z, seed0, seed1, use0, use1, acc);
+    if (cnt > S / 2) emb_seg_half<S / 2>(s, srow, sown, slr, sk, sst, sln, p0, cnt, d, c, z, seed0, seed1, use0, use1, acc);      // (uniform)
   }
 }
 

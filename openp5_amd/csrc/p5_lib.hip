@@ -52,6 +52,8 @@ static int g_opt_dec_atomic = getenv("P5_DEC_ATOMIC") ? atoi(getenv("P5_DEC_ATOM
 static int g_opt_adam_tiles = getenv("P5_ADAM_TILES") ? atoi(getenv("P5_ADAM_TILES")) : 1;       // p5_engine_adamw_step: tile-wise update that also writes W^T and W diag(ln)
 static int g_opt_gen_ff = getenv("P5_GEN_FF") ? atoi(getenv("P5_GEN_FF")) : 1;             // forced-prefix fast-forward (p5_decode.h): 0 = every step is a decode step
 static int g_opt_dec_head_nv = getenv("P5_DEC_HEAD_NV") ? atoi(getenv("P5_DEC_HEAD_NV")) : 0;   // streaming head: forced E rows per workgroup (0 = auto)
+static int g_opt_shift_fuse = getenv("P5_SHIFT_FUSE") ? atoi(getenv("P5_SHIFT_FUSE")) : 1;   // 1 = the decoder's embedding lookup shifts the labels itself (no p5_shift_right_kernel launch)
+static int g_opt_loss_fuse = getenv("P5_LOSS_FUSE") ? atoi(getenv("P5_LOSS_FUSE")) : 1;      // 1 = the loss kernel of p5_forward_loss* also writes the NLL gradients (no p5_ce_gscale_kernel launch in the backward)
 static int g_opt_gen_wide = getenv("P5_GEN_WIDE") ? atoi(getenv("P5_GEN_WIDE")) : 0;       // 1 = the wide search (p5_decode_wide.h) at every width, not only K > 64
 
 __global__ __launch_bounds__(256) void p5_shift_right_kernel(int64_t* out, const int64_t* labels, int B, int T, int64_t start) {
@@ -61,6 +63,35 @@ __global__ __launch_bounds__(256) void p5_shift_right_kernel(int64_t* out, const
   int64_t v = (t == 0) ? start : labels[i - 1];
   if (v == -100) v = start;
   out[i] = v;
+}
+
+// p5_masked_mean_kernel that also writes g_out [B * T] = what p5_ce_gscale_kernel writes without dnll (the gradient of this loss with
+// respect to the per-token NLL, gscale = 1 / B in the engine): the same expressions on the same operands, so the same bits, and the
+// backward of p5_forward_loss* needs no launch of its own for them
+__global__ __launch_bounds__(256) void p5_masked_mean_g_kernel(float* __restrict__ loss, float* __restrict__ g_out, const float* __restrict__ nll,
+                                                              const int64_t* __restrict__ out_attn, const int64_t* __restrict__ labels, int B, int T,
+                                                              float gscale, const float* __restrict__ tw = nullptr) {
+  __shared__ float sred[4];
+  float s = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    float num = 0.f, cnt = 0.f;
+    for (int t = 0; t < T; ++t) {
+      const float m = out_attn[(size_t)b * T + t] != 0 ? 1.f : 0.f;
+      num += nll[(size_t)b * T + t] * m;
+      cnt += m;
+    }
+    float r = num / fmaxf(cnt, 1.f);
+    if (tw) r *= tw[b];
+    s += r;
+    for (int t = 0; t < T; ++t) {
+      float g = out_attn[(size_t)b * T + t] != 0 ? gscale / fmaxf(cnt, 1.f) : 0.f;
+      if (tw) g *= tw[b];
+      if (labels[(size_t)b * T + t] == -100) g = 0.f;
+      g_out[(size_t)b * T + t] = g;
+    }
+  }
+  s = block_reduce(s, false, sred);
+  if (threadIdx.x == 0) loss[0] = s / (float)B;
 }
 
 __global__ __launch_bounds__(64) void p5_tr_probe_kernel(unsigned short* out, const unsigned short* in) {
@@ -153,6 +184,7 @@ struct P5Engine {
   float *logits = nullptr, *lse_tok = nullptr, *ssq_scratch = nullptr;
   float *ce_part = nullptr, *ce_lab = nullptr, *ce_g = nullptr;      // logit-free cross-entropy: per-row partial (max, sum exp) pairs, label logits, NLL gradients
   bool ce_free_fwd = false;       // the last training forward took the logit-free head (the backward recomputes the logits tile by tile)
+  bool ce_g_ready = false;        // ce_g already holds the NLL gradients of the last p5_forward_loss* (written by its loss kernel: option loss_fuse)
   // trie-normalised item loss (p5_trie_ce.h): il_next = p5_train_set_item_loss, armed for the NEXT forward (one-shot); il = what the last
   // forward ran under, read by the backward that follows it.  The rows' trie nodes and states live in ce_lab / ce_g (Md x 4 bytes each),
   // which only the logit-free route uses -- and an item-loss forward never takes it.
@@ -1083,11 +1115,17 @@ static int decoder_fwd(P5Engine* e, hipStream_t s, float* nll_out = nullptr) {
 #endif
     }
   }
-  P5_LAUNCH(p5_shift_right_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->dec_ids, e->labels, e->Bd, e->T, (int64_t)c.pad_id);
-  P5_TRY(P5_KCHECK());
   const bool nf = norm_fused<T>(e);
-  P5_LAUNCH((p5_embed_fwd_kernel<T>), dim3((Md + 3) / 4), dim3(256), 0, s, (T*)e->dec_x0, Wc<T>(e, e->off_E), (const T*)nullptr,
-            (const int64_t*)e->dec_ids, (const int64_t*)nullptr, Md, d, mk_drop(e, 1, 0, 0), nf ? e->ds[0].ssq_sa : (float*)nullptr);
+  if (g_opt_shift_fuse) {      // the lookup shifts the labels itself and leaves e->dec_ids behind (the backward and the embedding gradient read it)
+    P5_LAUNCH((p5_embed_fwd_kernel<T>), dim3((Md + 3) / 4), dim3(256), 0, s, (T*)e->dec_x0, Wc<T>(e, e->off_E), (const T*)nullptr,
+              (const int64_t*)nullptr, (const int64_t*)nullptr, Md, d, mk_drop(e, 1, 0, 0), nf ? e->ds[0].ssq_sa : (float*)nullptr, e->labels, e->dec_ids,
+              e->T, (int64_t)c.pad_id);
+  } else {
+    P5_LAUNCH(p5_shift_right_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->dec_ids, e->labels, e->Bd, e->T, (int64_t)c.pad_id);
+    P5_TRY(P5_KCHECK());
+    P5_LAUNCH((p5_embed_fwd_kernel<T>), dim3((Md + 3) / 4), dim3(256), 0, s, (T*)e->dec_x0, Wc<T>(e, e->off_E), (const T*)nullptr,
+              (const int64_t*)e->dec_ids, (const int64_t*)nullptr, Md, d, mk_drop(e, 1, 0, 0), nf ? e->ds[0].ssq_sa : (float*)nullptr);
+  }
   P5_TRY(P5_KCHECK());
   for (int i = 0; i < c.n_dec_layers; ++i) {
     const LayerOff& lo = e->dec[i];
@@ -1416,8 +1454,11 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     const int hd_ld = hd ? e->il.Nup : e->Vp;
     if (e->ce_free_fwd) {
       // dlogits = (softmax - onehot) * g straight out of the recomputed head GEMM (same operands, same accumulation order: the same logits)
-      P5_LAUNCH(p5_ce_gscale_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->ce_g, e->labels, dnll, e->out_attn, e->T, 1.0f / (float)e->Bd, Md, e->tgt_w);
-      P5_TRY(P5_KCHECK());
+      if (dnll || !e->ce_g_ready || !e->training) {      // (otherwise the loss kernel of p5_forward_loss* has written them)
+        P5_LAUNCH(p5_ce_gscale_kernel, dim3((Md + 255) / 256), dim3(256), 0, s, e->ce_g, e->labels, dnll, e->out_attn, e->T, 1.0f / (float)e->Bd, Md, e->tgt_w);
+        P5_TRY(P5_KCHECK());
+        e->ce_g_ready = false;      // (dnll's values are not the masked-mean rule's)
+      }
       P5GemmArgs g;
       memset(&g, 0, sizeof(g));
       g.A = e->dec_hn; g.B = Wc<T>(e, e->off_E); g.C = e->dlogits; g.M = Md; g.N = c.vocab_size; g.K = d; g.lda = d; g.ldb = d; g.ldc = e->Vp;
@@ -3398,6 +3439,8 @@ int p5_set_option(const char* name, int value) {
   else if (!strcmp(name, "wgrad_wide_min")) g_opt_wgrad_wide_min = value;
   else if (!strcmp(name, "grad_store_first")) g_opt_grad_store_first = value;
   else if (!strcmp(name, "embed_det")) g_opt_embed_det = value;
+  else if (!strcmp(name, "shift_fuse")) g_opt_shift_fuse = value;
+  else if (!strcmp(name, "loss_fuse")) g_opt_loss_fuse = value;
   else if (!strcmp(name, "g4_nst")) g_opt_g4_nst = value;
   else if (!strcmp(name, "g4_wgs")) g_opt_g4_wgs = value;
   else return fail("p5_set_option: unknown option");
@@ -3696,6 +3739,7 @@ int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* who
   e->B = B; e->Gt = G; e->Bd = B * G; e->L = L; e->T = T; e->M = B * L; e->Md = B * G * T; e->training = training;
   e->Vp = (e->c.vocab_size + 63) / 64 * 64;
   e->ids = input_ids; e->ww = whole_word_ids; e->mask = attention_mask; e->labels = labels; e->out_attn = nullptr; e->tgt_w = nullptr;
+  e->ce_g_ready = false;
   if (training && e->c.dropout > 0.f) P5_REQUIRE(e->rng, "training with dropout needs rng_state");
   e->il = e->il_next;            // one-shot: this forward and the backward behind it
   e->il_next.on = false;
@@ -3721,6 +3765,14 @@ int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t
     P5_LAUNCH(p5_trie_reg_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, e->il.terms_out, (const float*)nll_out, rt,
               e->il.ref ? rt + e->Md : (const float*)nullptr, output_attention, B * G, T, target_weights, e->il.ent_coef, e->il.kl_coef);
     return P5_KCHECK();
+  }
+  if (g_opt_loss_fuse && training && e->ce_free_fwd && nll_out) {
+    // the backward behind this call (dnll == nullptr) scales by exactly this mask and these weights: its NLL gradients are written here
+    P5_LAUNCH(p5_masked_mean_g_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, e->ce_g, (const float*)nll_out, output_attention, e->labels, B * G, T,
+              1.0f / (float)e->Bd, target_weights);
+    P5_TRY(P5_KCHECK());
+    e->ce_g_ready = true;
+    return 0;
   }
   P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, (const float*)nll_out, output_attention, B * G, T, target_weights);
   return P5_KCHECK();
@@ -4854,6 +4906,19 @@ int p5_op_trunc_ce_bwd_cols(int dtype, void* dlogits, const float* logits, const
 int p5_op_masked_mean(float* loss, const float* nll, const int64_t* out_attn, int B, int T, void* stream) {
   P5_REQUIRE(loss && nll && out_attn && B >= 1 && T >= 1, "masked_mean: arguments");
   P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss, nll, out_attn, B, T);
+  return P5_KCHECK();
+}
+int p5_op_masked_mean_g(int merged, float* loss, float* g_out, const float* nll, const int64_t* out_attn, const int64_t* labels, const float* tw, int B, int T,
+                        float gscale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  P5_REQUIRE(loss && g_out && nll && out_attn && labels && B >= 1 && T >= 1, "masked_mean_g: arguments");
+  if (merged) {
+    P5_LAUNCH(p5_masked_mean_g_kernel, dim3(1), dim3(256), 0, s, loss, g_out, nll, out_attn, labels, B, T, gscale, tw);
+    return P5_KCHECK();
+  }
+  P5_LAUNCH(p5_masked_mean_kernel, dim3(1), dim3(256), 0, s, loss, nll, out_attn, B, T, tw);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_ce_gscale_kernel, dim3((B * T + 255) / 256), dim3(256), 0, s, g_out, labels, (const float*)nullptr, out_attn, T, gscale, B * T, tw);
   return P5_KCHECK();
 }
 // the batch of an on-policy step from the sampler's output (p5_policy.h): both launches, stateless
