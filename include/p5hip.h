@@ -192,6 +192,25 @@ int p5_train_set_item_head(P5Engine* e, const int* head_tokens /* DEVICE [n_toke
  * coefficient that is not finite. */
 int p5_train_set_item_regularizers(P5Engine* e, const float* ref_logits, int ld_ref, float* row_terms, float entropy_coef, float kl_coef,
                                    float* terms_out);
+/* The clipped-ratio (PPO / GRPO style) policy objective (p5_clip.h) for several updates on one sampled batch.  One-shot, like
+ * p5_train_set_item_loss (call it behind that one): arms the NEXT p5_forward_loss / p5_forward_loss_targets and the backward behind it.  Two
+ * launches take the place of the masked-mean loss kernels.  Per target (b, g) with mask m = output_attention != 0, cnt = sum_t m, w =
+ * target_weights[b, g] (NULL = 1), lo = 1 - eps_low, hi = 1 + eps_high and rho = exp(log p_new - log p_old) = exp(-(old_logprobs + nll)):
+ *   ratio_mode 0 (token)     l = (1 / max(cnt, 1)) sum_t m_t max(-rho_t w, -clamp(rho_t, lo, hi) w)
+ *   ratio_mode 1 (sequence)  rho = exp(-(sum_t m_t (old_t + nll_t)) / max(cnt, 1)), l = max(-rho w, -clamp(rho, lo, hi) w); cnt = 0: l = 0
+ * loss = sum l / (B G); a target with target_mode 0 keeps its plain weighted term (target_mode int32 DEVICE [B * G], NULL = all 1); armed
+ * regularisers add their terms unchanged.  old_logprobs: DEVICE fp32 [rows], rows = B G T, read where m.  A unit (token, or target) with
+ * (w > 0 and rho > hi) or (w < 0 and rho < lo) is clipped: its rows' seeds are exact zeros; w == 0 gives zeros too.  With rho == 1 the seeds
+ * are the plain weighted step's bits.  Rows are taken as they come (nll 0 at rows the item loss did not score: clipped targets should be
+ * fully scored).  row_seed: DEVICE fp32, caller-owned until the backward has run: [rows], or [3 * rows] with regularisers armed (then the
+ * rows' entropy / KL seeds follow); user_partials DEVICE fp32 [B * 16] scratch; clip_stats DEVICE fp32 [8], no host sync: units, share clipped,
+ * share clipped at hi, share clipped at lo, mean rho, max rho, min rho, mean of (rho - 1) - log rho -- the two means over units with
+ * 0 < rho < inf; no unit: (0, 0, 0, 0, 1, 1, 1, 0).  The backward with dnll == NULL feeds row_seed through the per-row-seed path of every
+ * route (p5_backward, p5_backward_stage, p5_backward_staged).  No atomics: equal inputs give equal bits.
+ * Errors: eps not finite or negative, an unknown ratio mode, NULL required pointers, the truncated item loss armed (not built: the kept set
+ * may differ between the two policies); p5_forward / p5_forward_targets called while it is armed refuse and disarm it. */
+int p5_train_set_clip_objective(P5Engine* e, const float* old_logprobs, const int* target_mode, float eps_low, float eps_high, int ratio_mode,
+                                float* row_seed, float* user_partials, float* clip_stats);
 /* One-shot, in front of p5_backward / p5_backward_stage (stage 0) / p5_backward_staged called WITH dnll: DEVICE fp32 [rows] gradients of the
  * rows' H and KL of the last forward (NULL = zeros).  Error: the last forward ran without p5_train_set_item_regularizers. */
 int p5_backward_set_item_grads(P5Engine* e, const float* d_entropy, const float* d_kl);
@@ -713,6 +732,21 @@ int p5_policy_batch(const int64_t* sequences, const int64_t* labels, const int64
                     int Tg, int baseline, float policy_coef, float sft_coef, int token_sum, float adv_eps, int with_gold, int pad_id, int eos_id,
                     int64_t* labels_out, int64_t* attention_out, float* rewards_out, float* advantages, float* weights_out, float* user_stats,
                     float* stats, void* stream);
+/* p5_policy_batch plus the clipped objective's inputs: token_logprobs fp32 [B*S, Ts-1] (the sampler's) in; old_logprobs_out fp32 [B, G, To]
+ * (the draws' token log-probabilities at their label positions; the gold slot and positions behind a draw's end: 0) and target_mode_out
+ * int32 [B, G] (gold 0, draws 1) out.  Every other output carries the bits of p5_policy_batch. */
+int p5_policy_batch_clip(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards,
+                         const float* token_logprobs, int B, int S, int Ts, int Tg, int baseline, float policy_coef, float sft_coef, int token_sum,
+                         float adv_eps, int with_gold, int pad_id, int eos_id, int64_t* labels_out, int64_t* attention_out, float* rewards_out,
+                         float* advantages, float* weights_out, float* user_stats, float* stats, float* old_logprobs_out, int* target_mode_out,
+                         void* stream);
+/* The two kernels of p5_train_set_clip_objective behind a given per-token NLL, no engine: nll / old_logprobs fp32 [B*G*T], out_attn / labels
+ * int64 [B*G*T], tw fp32 [B*G] or NULL, target_mode int32 [B*G] or NULL, entropy_rows / kl_rows fp32 [B*G*T] or NULL (the regularised loss:
+ * terms fp32 [3] or NULL receives its parts, row_seed is [3*B*G*T] then, else [B*G*T]), user_partials fp32 [B*16], clip_stats fp32 [8]. */
+int p5_op_clip_objective(float* loss, float* terms, float* row_seed, float* user_partials, float* clip_stats, const float* nll,
+                         const float* old_logprobs, const int64_t* out_attn, const int64_t* labels, const float* tw, const int* target_mode,
+                         const float* entropy_rows, const float* kl_rows, float entropy_coef, float kl_coef, float eps_low, float eps_high,
+                         int ratio_mode, int B, int G, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];
  * amode 1: A = fp32 residual stream [M, K], normalised with T5LayerNorm weight `ln` by the kernel itself.
  * (K <= 1024 then).  epi: 0 store T (alpha), 1 relu store T, 2 fp32 atomic accumulate (split-K), 3 store fp32 (alpha), 4 fp32 += by one writer */

@@ -33,6 +33,7 @@
 #include "p5_item_head.h"
 #include "p5_trunc.h"
 #include "p5_policy.h"
+#include "p5_clip.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -205,6 +206,13 @@ struct P5Engine {
     float* terms_out = nullptr;
   };
   ItemLoss il_next, il;
+  // clipped-ratio objective (p5_clip.h): clip_next = p5_train_set_clip_objective, armed for the NEXT p5_forward_loss* (one-shot); clip = what the
+  // last forward ran under: the backward behind it (dnll == nullptr) takes its per-row seeds from clip.seed
+  struct ClipObj {
+    bool on = false; const float* old_lp = nullptr; const int* mode = nullptr; float eps_low = 0.f, eps_high = 0.f; int ratio_mode = 0;
+    float *seed = nullptr, *partials = nullptr, *stats = nullptr;
+  };
+  ClipObj clip_next, clip;
   const float *bw_dH = nullptr, *bw_dKL = nullptr;      // p5_backward_set_item_grads: per-row gradients of H / KL for the NEXT backward (one-shot)
   void* Sf = nullptr;              // folded bf16 weight copy W diag(ln) for q/k/v, wi, cross-attention q (same arena offsets; behind St)
   float *dres_a = nullptr, *dres_b = nullptr, *d_enc = nullptr, *Dvec = nullptr, *dres_cur = nullptr, *rel_partial = nullptr;
@@ -1445,6 +1453,11 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
     e->zg_pending = false;
     if (!dnll) P5_REQUIRE(e->out_attn, "backward without dnll needs p5_forward_loss (output_attention mask)");
     struct ItemGradsOnce { P5Engine* e; ~ItemGradsOnce() { e->bw_dH = e->bw_dKL = nullptr; } } item_grads_once{e};      // one-shot, whatever stage 0 returns
+    if (!dnll && e->clip.on) {
+      // the clipped objective's kernel has written this backward's seeds (and the regularisers'): every route below takes them as it takes autograd's
+      dnll = e->clip.seed;
+      if (e->il.on && e->il.reg) { e->bw_dH = e->clip.seed + Md; e->bw_dKL = e->clip.seed + 2 * (size_t)Md; }
+    }
     const float alpha = 1.0f / sqrtf((float)d);
     // the head's logits, their gradient and their leading dimension: the vocabulary's, or -- item loss on the restricted head
     // (p5_item_head.h) -- the compact arrays of the caller's workspace
@@ -3722,8 +3735,33 @@ int64_t p5_train_workspace_bytes_targets(const P5Engine* e, int B, int L, int T,
 }
 int64_t p5_train_workspace_bytes(const P5Engine* e, int B, int L, int T) { return p5_train_workspace_bytes_targets(e, B, L, T, 1); }
 
-int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
-                       int B, int L, int T, int G, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream) {
+// both kernels of p5_clip.h behind a per-token NLL: the seeds, the users' partials, then loss / terms / stats
+static int launch_clip(hipStream_t s, float* loss, float* terms, float* seed, float* partials, float* stats, const float* nll, const float* old_lp,
+                       const int64_t* out_attn, const int64_t* labels, const float* tw, const int* mode, const float* ent, const float* kl,
+                       float entropy_coef, float kl_coef, float eps_low, float eps_high, int ratio_mode, int B, int G, int T) {
+  P5ClipArgs a;
+  a.nll = nll; a.old_lp = old_lp; a.out_attn = out_attn; a.labels = labels; a.tw = tw; a.mode = mode; a.ent = ent; a.kl = ent ? kl : nullptr;
+  a.seed = seed; a.partials = partials; a.G = G; a.T = T; a.ratio_mode = ratio_mode; a.rows = B * G * T;
+  a.lo = 1.0f - eps_low; a.hi = 1.0f + eps_high; a.gscale = 1.0f / (float)(B * G); a.entropy_coef = entropy_coef; a.kl_coef = kl_coef;
+  P5_LAUNCH(p5_clip_objective_kernel, dim3(B), dim3(256), 0, s, a);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_clip_finish_kernel, dim3(1), dim3(256), 0, s, loss, terms, stats, (const float*)partials, B, B * G, ent ? 1 : 0, entropy_coef, kl_coef);
+  return P5_KCHECK();
+}
+static int clip_params_ok(float eps_low, float eps_high, int ratio_mode) {
+  P5_REQUIRE(eps_low - eps_low == 0.f && eps_high - eps_high == 0.f && eps_low >= 0.f && eps_high >= 0.f,
+             "clip objective: eps_low / eps_high must be finite and >= 0");
+  P5_REQUIRE(ratio_mode == P5_RATIO_TOKEN || ratio_mode == P5_RATIO_SEQUENCE, "clip objective: unknown ratio mode (0 token, 1 sequence)");
+  return 0;
+}
+static int forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
+                           int B, int L, int T, int G, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream, bool with_loss) {
+  e->clip = e->clip_next;        // one-shot, whatever this call returns
+  e->clip_next.on = false;
+  if (e->clip.on && !with_loss) {
+    e->clip.on = false;
+    P5_REQUIRE(false, "p5_forward / p5_forward_targets: a clip objective is armed (p5_train_set_clip_objective): it needs p5_forward_loss / p5_forward_loss_targets");
+  }
   P5_REQUIRE(e->P, "engine not bound");
   P5_REQUIRE(B >= 1 && L >= 1 && L <= 512 && T >= 1 && T <= 512, "shape limits: 1 <= L,T <= 512");
   P5_REQUIRE(G >= 1, "targets per user: G >= 1");
@@ -3746,7 +3784,15 @@ int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* who
   e->il.tr.group = G;            // (the excluded-node bitmap is per USER: sample b * G + g reads row b)
   e->il.tr.tw = nullptr;
   if (e->il.on) P5_REQUIRE(nll_out, "item loss: nll_out");
+  if (e->clip.on) {
+    P5_REQUIRE(nll_out, "clip objective: nll_out");
+    P5_REQUIRE(!(e->il.on && e->il.trunc), "clip objective: not built for the truncated item loss (top_k / top_p): the kept set may differ between the two policies");
+  }
   return e->c.dtype == 1 ? forward_impl<bf16>(e, nll_out, (hipStream_t)stream) : forward_impl<float>(e, nll_out, (hipStream_t)stream);
+}
+int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
+                       int B, int L, int T, int G, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream) {
+  return forward_targets(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, G, training, nll_out, ws, ws_bytes, stream, false);
 }
 int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
                int B, int L, int T, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream) {
@@ -3755,11 +3801,23 @@ int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_
 int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
                             const int64_t* output_attention, int B, int L, int T, int G, const float* target_weights, int training, float* nll_out,
                             float* loss_out, void* ws, int64_t ws_bytes, void* stream) {
+  if (!(output_attention && loss_out)) e->clip_next.on = false;     // (one-shot, refused calls included)
   P5_REQUIRE(output_attention && loss_out, "null argument");
-  P5_TRY(p5_forward_targets(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, G, training, nll_out, ws, ws_bytes, stream));
+  {
+    const int rc = forward_targets(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, G, training, nll_out, ws, ws_bytes, stream, true);
+    if (rc) { e->clip.on = false; return rc; }
+  }
   e->out_attn = output_attention;
   e->tgt_w = target_weights;
   e->il.tr.tw = target_weights;
+  if (e->clip.on) {
+    // the clipped objective in the loss kernels' place: it writes the seeds of the backward behind this call
+    const bool reg = e->il.on && e->il.reg;
+    const float* rt = reg ? e->il.row_terms : nullptr;
+    return launch_clip((hipStream_t)stream, loss_out, reg ? e->il.terms_out : nullptr, e->clip.seed, e->clip.partials, e->clip.stats, (const float*)nll_out,
+                       e->clip.old_lp, output_attention, e->labels, target_weights, e->clip.mode, rt, reg && e->il.ref ? rt + e->Md : nullptr,
+                       reg ? e->il.ent_coef : 0.f, reg ? e->il.kl_coef : 0.f, e->clip.eps_low, e->clip.eps_high, e->clip.ratio_mode, B, G, T);
+  }
   if (e->il.on && e->il.reg) {
     const float* rt = e->il.row_terms;
     P5_LAUNCH(p5_trie_reg_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, e->il.terms_out, (const float*)nll_out, rt,
@@ -3844,6 +3902,19 @@ int p5_train_set_item_regularizers(P5Engine* e, const float* ref_logits, int ld_
   h.ref = ref_logits; h.ld_ref = ref_logits ? ld_ref : 0; h.row_terms = row_terms; h.ent_coef = entropy_coef; h.kl_coef = kl_coef;
   h.terms_out = terms_out;
   h.reg = true;
+  return 0;
+}
+int p5_train_set_clip_objective(P5Engine* e, const float* old_logprobs, const int* target_mode, float eps_low, float eps_high, int ratio_mode,
+                                float* row_seed, float* user_partials, float* clip_stats) {
+  e->clip_next.on = false;
+  P5_TRY(clip_params_ok(eps_low, eps_high, ratio_mode));
+  P5_REQUIRE(old_logprobs && row_seed && user_partials && clip_stats,
+             "clip objective: null pointer (old_logprobs, row_seed, user_partials and clip_stats are required)");
+  P5_REQUIRE(!(e->il_next.on && e->il_next.trunc),
+             "clip objective: not built for the truncated item loss (top_k / top_p): the kept set may differ between the two policies");
+  e->clip_next.old_lp = old_logprobs; e->clip_next.mode = target_mode; e->clip_next.eps_low = eps_low; e->clip_next.eps_high = eps_high;
+  e->clip_next.ratio_mode = ratio_mode; e->clip_next.seed = row_seed; e->clip_next.partials = user_partials; e->clip_next.stats = clip_stats;
+  e->clip_next.on = true;
   return 0;
 }
 int p5_backward_set_item_grads(P5Engine* e, const float* d_entropy, const float* d_kl) {
@@ -4921,11 +4992,22 @@ int p5_op_masked_mean_g(int merged, float* loss, float* g_out, const float* nll,
   P5_LAUNCH(p5_ce_gscale_kernel, dim3((B * T + 255) / 256), dim3(256), 0, s, g_out, labels, (const float*)nullptr, out_attn, T, gscale, B * T, tw);
   return P5_KCHECK();
 }
-// the batch of an on-policy step from the sampler's output (p5_policy.h): both launches, stateless
-int p5_policy_batch(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards, int B, int S, int Ts, int Tg,
+// the clipped-ratio objective (p5_clip.h) behind a given per-token NLL: both launches, no engine
+int p5_op_clip_objective(float* loss, float* terms, float* row_seed, float* user_partials, float* clip_stats, const float* nll, const float* old_logprobs,
+                         const int64_t* out_attn, const int64_t* labels, const float* tw, const int* target_mode, const float* entropy_rows,
+                         const float* kl_rows, float entropy_coef, float kl_coef, float eps_low, float eps_high, int ratio_mode, int B, int G, int T,
+                         void* stream) {
+  P5_TRY(clip_params_ok(eps_low, eps_high, ratio_mode));
+  P5_REQUIRE(loss && row_seed && user_partials && clip_stats && nll && old_logprobs && out_attn && labels, "clip objective: null pointer argument");
+  P5_REQUIRE(B >= 1 && G >= 1 && T >= 1 && (int64_t)B * G * T <= ((int64_t)1 << 30), "clip objective: shapes B, G, T >= 1, B * G * T <= 2^30");
+  P5_REQUIRE(entropy_rows || !kl_rows, "clip objective: kl_rows needs entropy_rows");
+  return launch_clip((hipStream_t)stream, loss, terms, row_seed, user_partials, clip_stats, nll, old_logprobs, out_attn, labels, tw, target_mode, entropy_rows,
+                     kl_rows, entropy_coef, kl_coef, eps_low, eps_high, ratio_mode, B, G, T);
+}
+static int policy_batch_impl(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards, int B, int S, int Ts, int Tg,
                     int baseline, float policy_coef, float sft_coef, int token_sum, float adv_eps, int with_gold, int pad_id, int eos_id,
                     int64_t* labels_out, int64_t* attention_out, float* rewards_out, float* advantages, float* weights_out, float* user_stats,
-                    float* stats, void* stream) {
+                    float* stats, const float* token_lp, float* old_lp_out, int* mode_out, void* stream) {
   P5_REQUIRE(sequences && labels && output_attention, "policy_batch: null input pointer (sequences, labels, output_attention)");
   P5_REQUIRE(labels_out && attention_out && rewards_out && advantages && weights_out && user_stats && stats, "policy_batch: null output pointer");
   P5_REQUIRE(B >= 1 && Ts >= 2 && Tg >= 1 && Tg <= (1 << 24), "policy_batch: shapes B >= 1, Ts >= 2, 1 <= Tg <= 2^24");
@@ -4940,11 +5022,30 @@ int p5_policy_batch(const int64_t* sequences, const int64_t* labels, const int64
   a.labels_out = labels_out; a.attn_out = attention_out; a.rewards_out = rewards_out; a.adv = advantages; a.weights = weights_out; a.user_stats = user_stats;
   a.S = S; a.Ts = Ts; a.Tg = Tg; a.To = Tg > Ts - 1 ? Tg : Ts - 1; a.baseline = baseline; a.token_sum = token_sum; a.with_gold = with_gold;
   a.pad_id = pad_id; a.eos_id = eos_id; a.policy_coef = policy_coef; a.sft_coef = sft_coef; a.adv_eps = adv_eps;
+  a.token_lp = token_lp; a.old_lp_out = old_lp_out; a.mode_out = mode_out;
   P5_REQUIRE((int64_t)(S + with_gold) * a.To <= (int64_t)1 << 30, "policy_batch: G * To too large");
   hipStream_t s = (hipStream_t)stream;
   P5_LAUNCH(p5_policy_batch_kernel, dim3(B), dim3(256), 0, s, a);
   P5_LAUNCH(p5_policy_stats_kernel, dim3(1), dim3(256), 0, s, stats, user_stats, B);
   return P5_KCHECK();
+}
+// the batch of an on-policy step from the sampler's output (p5_policy.h): both launches, stateless
+int p5_policy_batch(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards, int B, int S, int Ts, int Tg,
+                    int baseline, float policy_coef, float sft_coef, int token_sum, float adv_eps, int with_gold, int pad_id, int eos_id,
+                    int64_t* labels_out, int64_t* attention_out, float* rewards_out, float* advantages, float* weights_out, float* user_stats,
+                    float* stats, void* stream) {
+  return policy_batch_impl(sequences, labels, output_attention, rewards, B, S, Ts, Tg, baseline, policy_coef, sft_coef, token_sum, adv_eps, with_gold, pad_id,
+                           eos_id, labels_out, attention_out, rewards_out, advantages, weights_out, user_stats, stats, nullptr, nullptr, nullptr, stream);
+}
+// ... and the clipped objective's two inputs: old_logprobs_out fp32 [B, G, To] gathered from the sampler's token_logprobs [B * S, Ts - 1], target_mode_out int32 [B, G]
+int p5_policy_batch_clip(const int64_t* sequences, const int64_t* labels, const int64_t* output_attention, const float* rewards, const float* token_logprobs,
+                         int B, int S, int Ts, int Tg, int baseline, float policy_coef, float sft_coef, int token_sum, float adv_eps, int with_gold, int pad_id,
+                         int eos_id, int64_t* labels_out, int64_t* attention_out, float* rewards_out, float* advantages, float* weights_out, float* user_stats,
+                         float* stats, float* old_logprobs_out, int* target_mode_out, void* stream) {
+  P5_REQUIRE(token_logprobs && old_logprobs_out && target_mode_out, "policy_batch_clip: null pointer (token_logprobs, old_logprobs_out, target_mode_out)");
+  return policy_batch_impl(sequences, labels, output_attention, rewards, B, S, Ts, Tg, baseline, policy_coef, sft_coef, token_sum, adv_eps, with_gold, pad_id,
+                           eos_id, labels_out, attention_out, rewards_out, advantages, weights_out, user_stats, stats, token_logprobs, old_logprobs_out,
+                           target_mode_out, stream);
 }
 int p5_op_skinny_gemm(int dtype, int amode, const void* A, int lda, const float* ln, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                       int epi, float alpha, float eps, void* stream) {

@@ -38,6 +38,10 @@ struct P5PolicyArgs {
   int64_t* labels_out; int64_t* attn_out; float* rewards_out; float* adv; float* weights; float* user_stats;
   int S, Ts, Tg, To, baseline, token_sum, with_gold, pad_id, eos_id;
   float policy_coef, sft_coef, adv_eps;
+  // the clipped-ratio objective's inputs (p5_clip.h), both optional: the behaviour policy's log-probabilities of the draws' labels, gathered from
+  // the sampler's token_logprobs fp32 [B * S, Ts - 1] into old_lp_out fp32 [G, To] (the gold slot and positions behind a draw's end: 0), and
+  // mode_out int32 [G] (gold 0 = plain weighted NLL, draws 1 = clipped surrogate).  Null: nothing is read or written.
+  const float* token_lp = nullptr; float* old_lp_out = nullptr; int* mode_out = nullptr;
 };
 
 // position j of the gold is attended iff j lies in front of the gold's first -100 label (Te; the engine scores nothing at a -100 and behind
@@ -96,7 +100,13 @@ __global__ __launch_bounds__(256) void p5_policy_batch_kernel(P5PolicyArgs a) {
     }
     a.labels_out[(size_t)b * G * To + e] = lab;
     a.attn_out[(size_t)b * G * To + e] = m;
+    if (a.old_lp_out) {
+      const int s = g - a.with_gold;
+      a.old_lp_out[(size_t)b * G * To + e] = (s >= 0 && t < s_n[s]) ? a.token_lp[((size_t)b * S + s) * (Ts - 1) + t] : 0.f;
+    }
   }
+  if (a.mode_out)
+    for (int g = tid; g < G; g += 256) a.mode_out[(size_t)b * G + g] = (a.with_gold && g == 0) ? 0 : 1;
   // 3. the first existing draw, the count, the sums.  A thread visits its draws in index order and block_reduce has a fixed order.
   float cnt = 0.f, rsum = 0.f, lead = 0.f;
   for (int s = tid; s < S; s += 256)

@@ -804,7 +804,8 @@ class P5T5Native(nn.Module):
             self.ddp_wait_ms.append((ev0, ev1))     # (read by bench.py after a synchronize: main-stream time spent waiting for the buckets)
 
     def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None,
-                          top_k=0, top_p=1.0, item_head=None, target_weights=None, entropy_coef=0.0, kl_coef=0.0, ref_logits=None):
+                          top_k=0, top_p=1.0, item_head=None, target_weights=None, entropy_coef=0.0, kl_coef=0.0, ref_logits=None, old_logprobs=None,
+                          target_mode=None, clip_eps=None, ratio="token"):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
@@ -820,8 +821,23 @@ class P5T5Native(nn.Module):
         `target_weights`: a target of weight 0 still contributes) of the rows' exact entropy over the allowed children and of their exact
         KL(policy || reference); `ref_logits` fp32 [rows, V] ("dense") or [rows, Nu] ("trie") is a frozen reference model's `item_logits` of the
         same batch, finite at the allowed children, a constant of the gradient.  `last_item_loss_terms` is the device tensor
-        (L_nll, R_H, R_KL), no host sync (None behind a call without regularisers).  With both coefficients 0 and no `ref_logits` the call is the one above, bit for bit."""
+        (L_nll, R_H, R_KL), no host sync (None behind a call without regularisers).  With both coefficients 0 and no `ref_logits` the call is the one above, bit for bit.
+        `old_logprobs`, `clip_eps`, `target_mode`, `ratio`: the clipped-ratio (PPO / GRPO style) objective (csrc/p5_clip.h), for several updates
+        on one sampled batch; `old_logprobs` and `clip_eps` come together.  `old_logprobs` fp32, shaped like `labels`: the BEHAVIOUR policy's
+        log-probability of every label (read where `output_attention != 0`); `clip_eps` a float or a (low, high) pair, lo = 1 - low, hi = 1 + high;
+        `target_mode` int [B, G] ([B] without G): 1 = clipped surrogate, 0 = the plain weighted NLL above (a gold target); None = all 1.  With
+        rho = exp(-nll - old), w the target's weight and cnt its attended tokens, a mode-1 target's term is
+          ratio="token"     (1 / max(cnt, 1)) sum_t m_t max(-rho_t w, -clamp(rho_t, lo, hi) w)
+          ratio="sequence"  max(-rho w, -clamp(rho, lo, hi) w), rho = exp(-(sum_t m_t (old_t + nll_t)) / max(cnt, 1)) (GSPO's length-normalised
+                            ratio; a target without an attended token contributes nothing)
+        in the place of w * (masked mean of nll); the regularisers keep their terms.  A unit (token, or target) is clipped -- no gradient, an
+        exact zero -- iff (w > 0 and rho > hi) or (w < 0 and rho < lo).  With rho == 1 everywhere (old = -nll of these weights) every gradient
+        carries the bits of the call without the objective.  Rows are taken as they come: the item loss gives NLL 0 to a row it did not score
+        (`last_item_loss_state`), so clipped targets should be fully scored -- `policy_batch`'s draws are.  Not under top_k / top_p (the kept set
+        may differ between the two policies).  `last_clip_stats` is the device tensor fp32 [8] named by `CLIP_STATS`, no host sync (None behind
+        a call without the objective).  Without these keywords the call issues the engine calls it always did."""
         item_head = self._item_head_mode(item_head, trie)
+        clip = self._clip_args(old_logprobs, target_mode, clip_eps, ratio, top_k, top_p)
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
         B, L = input_ids.shape
@@ -834,6 +850,11 @@ class P5T5Native(nn.Module):
         G = self._check_targets(B, labels, output_attention, target_weights, fused=True)
         T = labels.shape[-1]
         Bd = B * (G or 1)
+        if clip is not None:
+            if not torch.is_tensor(old_logprobs) or tuple(old_logprobs.shape) != tuple(labels.shape):
+                raise ValueError(f"old_logprobs {tuple(getattr(old_logprobs, 'shape', ()))} must be a tensor shaped like labels {tuple(labels.shape)}")
+            if target_mode is not None and (not torch.is_tensor(target_mode) or tuple(target_mode.shape) != tuple(labels.shape[:-1])):
+                raise ValueError(f"target_mode {tuple(getattr(target_mode, 'shape', ()))} must be a tensor of shape {tuple(labels.shape[:-1])} (one per target)")
         item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p, item_head)
         if entropy_coef != 0.0 or kl_coef != 0.0 or ref_logits is not None:
             item_loss = self._item_regularizers(item_loss, Bd * T, ref_logits, entropy_coef, kl_coef, fused=True)
@@ -851,6 +872,18 @@ class P5T5Native(nn.Module):
         self._saved_inputs = (input_ids, whole_word_ids, attention_mask, labels, output_attention, item_loss, target_weights)
         if item_loss is not None:
             self._arm_item_loss(item_loss, Bd, T, G)
+        self.last_clip_stats = None            # (None behind a call without the objective: never a stale step's)
+        if clip is not None:
+            # the seeds (and, regularised, the entropy / KL seeds behind them), the users' partials and the statistics: the caller's, like row_cut
+            old = old_logprobs.detach().to(device=dev, dtype=torch.float32).contiguous()
+            mode = None if target_mode is None else target_mode.to(device=dev, dtype=torch.int32).contiguous()
+            reg = item_loss is not None and item_loss.reg
+            buf = torch.empty((3 if reg else 1) * Bd * T + 16 * B + 8, dtype=torch.float32, device=dev)
+            seed, partials, stats = torch.split(buf, [buf.numel() - 16 * B - 8, 16 * B, 8])
+            self._saved_inputs += (old, mode, buf)
+            self._be.check(self._lib.p5_train_set_clip_objective(self._engine, _ptr(old), _ptr(mode), clip[0], clip[1], clip[2], _ptr(seed), _ptr(partials),
+                                                                 _ptr(stats)), "p5_train_set_clip_objective")
+            self.last_clip_stats = stats
         if G is None:
             self._be.check(self._lib.p5_forward_loss(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels),
                                                      _ptr(output_attention), B, L, T, training, _ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * B * T),
@@ -868,6 +901,38 @@ class P5T5Native(nn.Module):
     POLICY_STATS = ("reward_mean", "users_with_signal", "abs_advantage_mean", "hit_rate", "users_with_hit", "users_without_draw")
     last_policy_batch = None      # of the last policy_step: the dict of policy_batch / its "stats", on the device
     last_policy_stats = None
+
+    CLIP_STATS = ("units", "clipped", "clipped_high", "clipped_low", "ratio_mean", "ratio_max", "ratio_min", "kl_old_new_k3")
+    CLIP_RATIOS = {"token": 0, "sequence": 1}
+    last_clip_stats = None        # of the last loss_and_backward with the clipped objective: fp32 [8] on the device (CLIP_STATS); else None
+
+    def _clip_args(self, old_logprobs, target_mode, clip_eps, ratio, top_k=0, top_p=1.0):
+        """the checked scalars of the clipped objective, (eps_low, eps_high, ratio code), or None when the call does not ask for it"""
+        if old_logprobs is None and clip_eps is None:
+            if target_mode is not None:
+                raise ValueError("target_mode belongs to the clipped objective: it needs old_logprobs and clip_eps")
+            if ratio not in self.CLIP_RATIOS:
+                raise ValueError(f"ratio={ratio!r}: one of {sorted(self.CLIP_RATIOS)}")
+            return None
+        if clip_eps is None:
+            raise ValueError("old_logprobs needs clip_eps (a float, or a (low, high) pair): the clipped objective takes both")
+        if old_logprobs is None:
+            raise ValueError("clip_eps needs old_logprobs (the behaviour policy's log-probabilities of the labels): the clipped objective takes both")
+        if ratio not in self.CLIP_RATIOS:
+            raise ValueError(f"ratio={ratio!r}: one of {sorted(self.CLIP_RATIOS)}")
+        try:
+            lo, hi = (float(clip_eps),) * 2 if not isinstance(clip_eps, (tuple, list)) else (float(clip_eps[0]), float(clip_eps[1]))
+            if isinstance(clip_eps, (tuple, list)) and len(clip_eps) != 2:
+                raise TypeError
+        except (TypeError, ValueError, IndexError):
+            raise ValueError(f"clip_eps={clip_eps!r}: a float, or a (low, high) pair") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo >= 0.0 and hi >= 0.0):
+            raise ValueError(f"clip_eps={clip_eps!r}: finite values >= 0")
+        tk, tp = self._truncation(top_k, top_p)
+        if tk > 0 or tp < 1.0:
+            raise ValueError("the clipped objective (clip_eps) is not built for the truncated item loss (top_k / top_p): the kept set may differ "
+                             "between the two policies")
+        return lo, hi, self.CLIP_RATIOS[ratio]
 
     def _policy_args(self, num_samples, baseline, policy_coef, sft_coef, token_sum, adv_eps):
         """the checked scalars of policy_batch / policy_step: (S, baseline code, policy_coef, sft_coef, token_sum, adv_eps, with_gold)"""
@@ -897,7 +962,7 @@ class P5T5Native(nn.Module):
 
     @torch.no_grad()
     def policy_batch(self, sequences, labels, output_attention, num_samples, rewards=None, baseline="loo", policy_coef=1.0, sft_coef=1.0,
-                     token_sum=False, adv_eps=1e-6):
+                     token_sum=False, adv_eps=1e-6, token_logprobs=None):
         """The batch of one on-policy (REINFORCE-style) step from drawn sequences, built on the device in two launches (csrc/p5_policy.h), no
         host sync: for callers who bring their own sequences (`sample_slates` with num_samples = num_slates * slate_size) or rewards.
         `sequences` int64 [B * S, Ts] as `sample_items` / `sample_slates` return them (an all-pad row: nothing drawn); `labels` /
@@ -909,7 +974,10 @@ class P5T5Native(nn.Module):
         Returns device tensors {"labels", "output_attention" [B, G, To], "target_weights" [B, G], "rewards", "advantages" [B, S], "stats" [8]}
         with G = S + 1 (slot 0 = the gold) or G = S when sft_coef == 0, To = max(T, Ts - 1).  `loss_and_backward(labels, output_attention,
         target_weights=...)` on them is sft_coef * mean_b nll(gold_b) + policy_coef * mean_b (1/S) sum_s A_bs nll(draw_bs), nll the token mean
-        or -- `token_sum` -- the token sum, whose gradient is REINFORCE's.  `stats`: the values named by `POLICY_STATS`, then two zeros."""
+        or -- `token_sum` -- the token sum, whose gradient is REINFORCE's.  `stats`: the values named by `POLICY_STATS`, then two zeros.
+        `token_logprobs` fp32 [B * S, Ts - 1] (the sampler's): the dict gains the clipped objective's inputs, "old_logprobs" fp32 [B, G, To] (the
+        draws' token log-probabilities at their label positions; the gold slot and positions behind a draw's end: 0) and "target_mode" int32
+        [B, G] (gold 0, draws 1); everything else keeps its bits."""
         S, base, pc, sc, tsum, eps, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, adv_eps)
         dev = self._be.device
         if not torch.is_tensor(sequences) or sequences.dim() != 2 or sequences.shape[0] % S != 0 or sequences.shape[0] == 0 or sequences.shape[1] < 2:
@@ -921,11 +989,24 @@ class P5T5Native(nn.Module):
             if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S):
                 raise ValueError(f"rewards {tuple(getattr(rewards, 'shape', ()))}: a tensor [B, S] = {(B, S)}")
             rewards = rewards.to(device=dev, dtype=torch.float32).contiguous()
+        if token_logprobs is not None:
+            if not torch.is_tensor(token_logprobs) or tuple(token_logprobs.shape) != (B * S, Ts - 1):
+                raise ValueError(f"token_logprobs {tuple(getattr(token_logprobs, 'shape', ()))}: a tensor [B * S, Ts - 1] = {(B * S, Ts - 1)}")
+            token_logprobs = token_logprobs.to(device=dev, dtype=torch.float32).contiguous()
         sequences, labels, output_attention = self._i64(sequences, dev), self._i64(labels, dev), self._i64(output_attention, dev)
         lab_o = torch.empty(B, G, To, dtype=torch.int64, device=dev)
         att_o = torch.empty(B, G, To, dtype=torch.int64, device=dev)
         f = torch.empty(2 * B * S + B * G + 4 * B + 8, dtype=torch.float32, device=dev)       # rewards | advantages | weights | user stats | stats
         r_o, a_o, w_o, us, st = torch.split(f, [B * S, B * S, B * G, 4 * B, 8])
+        if token_logprobs is not None:
+            old_o = torch.empty(B, G, To, dtype=torch.float32, device=dev)
+            mode_o = torch.empty(B, G, dtype=torch.int32, device=dev)
+            self._be.check(self._lib.p5_policy_batch_clip(_ptr(sequences), _ptr(labels), _ptr(output_attention), _ptr(rewards), _ptr(token_logprobs), B, S, Ts,
+                                                          int(labels.shape[1]), base, pc, sc, tsum, eps, with_gold, int(self.config.pad_token_id),
+                                                          int(self.config.eos_token_id), _ptr(lab_o), _ptr(att_o), _ptr(r_o), _ptr(a_o), _ptr(w_o), _ptr(us),
+                                                          _ptr(st), _ptr(old_o), _ptr(mode_o), self._be.stream_ptr()), "p5_policy_batch_clip")
+            return {"labels": lab_o, "output_attention": att_o, "target_weights": w_o.view(B, G), "rewards": r_o.view(B, S), "advantages": a_o.view(B, S),
+                    "stats": st, "old_logprobs": old_o, "target_mode": mode_o}
         self._be.check(self._lib.p5_policy_batch(_ptr(sequences), _ptr(labels), _ptr(output_attention), _ptr(rewards), B, S, Ts, int(labels.shape[1]), base,
                                                  pc, sc, tsum, eps, with_gold, int(self.config.pad_token_id), int(self.config.eos_token_id), _ptr(lab_o),
                                                  _ptr(att_o), _ptr(r_o), _ptr(a_o), _ptr(w_o), _ptr(us), _ptr(st), self._be.stream_ptr()), "p5_policy_batch")
@@ -934,7 +1015,7 @@ class P5T5Native(nn.Module):
 
     def policy_step(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=1.0, excluded_items=None,
                     top_k=0, top_p=1.0, item_head=None, baseline="loo", policy_coef=1.0, sft_coef=1.0, token_sum=False, reward_fn=None, seed=None,
-                    streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None):
+                    streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None, clip_eps=None, ratio="token", old_logprobs="sampler"):
         """One on-policy fine-tuning step: (1) `sample_items(num_samples=...)` with the trie, temperature, exclusion and truncation the loss
         uses -- that sameness is what on-policy means here; (2) `policy_batch` on the draws (`reward_fn`, if given, is called with the
         sampler's dict and returns fp32 [B, S] on the device; else the hit reward against `labels`); (3) `loss_and_backward` on the grouped
@@ -943,7 +1024,17 @@ class P5T5Native(nn.Module):
         Returns the loss as a 0-dim tensor, gradients in `.grad`; `last_policy_batch` (the dict of `policy_batch`) and `last_policy_stats`
         (fp32 [8], `POLICY_STATS`) stay on the device, no host sync.  The limits of a grouped call (G * To <= 512, ...) are checked before
         anything is sampled.  Sampling ignores `self.training` (no dropout in the draw, as in `sample_items`); the training forward applies
-        dropout as usual, so under dropout the draws come from the dropout-free policy.  `seed` / `streams`: those of `sample_items`."""
+        dropout as usual, so under dropout the draws come from the dropout-free policy.  `seed` / `streams`: those of `sample_items`.
+        `clip_eps` (None = off: the step above, bit for bit): `policy_collect` and then ONE `policy_update` with the clipped-ratio objective
+        (`ratio`, `old_logprobs`: theirs) -- call the two yourself for several updates per sampled batch."""
+        if clip_eps is not None:
+            rollout = self.policy_collect(input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=temperature,
+                                          excluded_items=excluded_items, top_k=top_k, top_p=top_p, item_head=item_head, baseline=baseline,
+                                          policy_coef=policy_coef, sft_coef=sft_coef, token_sum=token_sum, reward_fn=reward_fn, seed=seed, streams=streams,
+                                          entropy_coef=entropy_coef, kl_coef=kl_coef, ref_model=ref_model, old_logprobs=old_logprobs, clip_eps=clip_eps,
+                                          ratio=ratio)
+            return self.policy_update(input_ids, whole_word_ids, attention_mask, rollout, trie, clip_eps, ratio=ratio, temperature=temperature,
+                                      excluded_items=excluded_items, item_head=item_head, entropy_coef=entropy_coef, kl_coef=kl_coef)
         if trie is None:
             raise ValueError("policy_step needs trie=...: the draws and the item loss share it")
         S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
@@ -980,6 +1071,79 @@ class P5T5Native(nn.Module):
                                       **kw)
         self.last_policy_batch, self.last_policy_stats = pb, pb["stats"]
         return loss
+
+    def policy_collect(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=1.0,
+                       excluded_items=None, top_k=0, top_p=1.0, item_head=None, baseline="loo", policy_coef=1.0, sft_coef=1.0, token_sum=False,
+                       reward_fn=None, seed=None, streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None, old_logprobs="sampler", clip_eps=0.2,
+                       ratio="token"):
+        """The rollout of a clipped-ratio (PPO / GRPO style) step: `sample_items` and `policy_batch` as in `policy_step`, ONCE, for several
+        `policy_update` calls.  Returns the dict of `policy_batch` plus "old_logprobs" fp32 [B, G, To] (the behaviour policy's log-probability
+        of every label), "target_mode" int32 [B, G] (gold 0, draws 1), "sampled" (the sampler's dict) and -- with `kl_coef != 0` -- "ref_logits"
+        (`ref_model.item_logits` of the grouped labels: they depend on the labels only, so the updates share them).
+        `old_logprobs`: "sampler" = the sampler's `token_logprobs`, which cost nothing (the decode kernels and the training forward differ in
+        their last bits: the first update's ratio is 1 up to those); "forward" = recomputed with one grouped item-loss forward of this model,
+        no gradient, no dropout: the first update's ratio is then exactly 1 when dropout is off.  `clip_eps` / `ratio` / `entropy_coef` are only
+        checked here (every refusal of the update is raised before anything is sampled).  Not under top_k / top_p."""
+        if trie is None:
+            raise ValueError("policy_collect needs trie=...: the draws and the item loss share it")
+        if old_logprobs not in ("sampler", "forward"):
+            raise ValueError(f'old_logprobs={old_logprobs!r}: "sampler" (the sampler\'s token_logprobs) or "forward" (recomputed by a training-path forward)')
+        self._clip_args(True, None, clip_eps, ratio, top_k, top_p)
+        S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
+        item_head = self._item_head_mode(item_head, trie)
+        ec, kc = float(entropy_coef), float(kl_coef)
+        if not (math.isfinite(ec) and math.isfinite(kc)):
+            raise ValueError(f"entropy_coef={entropy_coef!r}, kl_coef={kl_coef!r}: finite values")
+        if kc != 0.0 and ref_model is None:
+            raise ValueError(f"kl_coef={kl_coef!r} needs ref_model (a frozen_copy() of the reference policy)")
+        trie = self._compiled_trie(trie)
+        input_ids = torch.as_tensor(input_ids)
+        B = int(input_ids.shape[0])
+        Ts = max(2, int(trie.max_depth))
+        labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
+        self._check_policy_shapes(B, S, Ts, labels, output_attention, with_gold)
+        drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
+                                  temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
+        rewards = None if reward_fn is None else reward_fn(drawn)
+        rollout = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=rewards, baseline=baseline, policy_coef=policy_coef,
+                                    sft_coef=sft_coef, token_sum=token_sum, token_logprobs=drawn["token_logprobs"])
+        rollout["sampled"] = drawn
+        if old_logprobs == "forward":
+            dev = self._be.device
+            ids = self._i64(input_ids, dev)
+            ww = self._i64(whole_word_ids if whole_word_ids is not None else torch.zeros_like(ids), dev)
+            am = self._i64(attention_mask if attention_mask is not None else (ids != self.config.pad_token_id).long(), dev)
+            q = self._item_loss_setup(trie, temperature, excluded_items, B, 0, 1.0, item_head)
+            with torch.no_grad():
+                nll = self._engine_forward(ids, ww, am, rollout["labels"], q, inference=True)
+            rollout["old_logprobs"] = (-nll).view_as(rollout["old_logprobs"])
+        if kc != 0.0:
+            rollout["ref_logits"] = ref_model.item_logits(input_ids, whole_word_ids, attention_mask, rollout["labels"], trie, temperature=temperature,
+                                                          excluded_items=excluded_items, item_head=item_head)
+        self.last_policy_batch, self.last_policy_stats = rollout, rollout["stats"]
+        return rollout
+
+    def policy_update(self, input_ids, whole_word_ids, attention_mask, rollout, trie, clip_eps, ratio="token", temperature=1.0, excluded_items=None,
+                      item_head=None, entropy_coef=0.0, kl_coef=0.0):
+        """One update on a rollout of `policy_collect`: `loss_and_backward` on its grouped batch with the clipped-ratio objective (the gold
+        slot keeps its plain weighted NLL).  Callable several times per rollout: optimizer step and `zero_grad` in between are the caller's.
+        Trie, temperature, exclusion and head must be those of the collect.  With `kl_coef != 0` the rollout's "ref_logits" are used.
+        Returns the loss; `last_clip_stats` says how much was clipped."""
+        if trie is None:
+            raise ValueError("policy_update needs trie=...: the item loss of the rollout's draws")
+        if clip_eps is None:
+            raise ValueError("policy_update needs clip_eps (a float, or a (low, high) pair)")
+        kw = {}
+        if float(entropy_coef) != 0.0 or float(kl_coef) != 0.0:
+            kw.update(entropy_coef=float(entropy_coef), kl_coef=float(kl_coef))
+            if float(kl_coef) != 0.0:
+                if "ref_logits" not in rollout:
+                    raise ValueError(f"kl_coef={kl_coef!r}: the rollout holds no ref_logits (policy_collect(kl_coef=..., ref_model=...) computes them once)")
+                kw["ref_logits"] = rollout["ref_logits"]
+        return self.loss_and_backward(input_ids, whole_word_ids, attention_mask, rollout["labels"], rollout["output_attention"], trie=trie,
+                                      temperature=temperature, excluded_items=excluded_items, item_head=item_head,
+                                      target_weights=rollout["target_weights"], old_logprobs=rollout["old_logprobs"], target_mode=rollout["target_mode"],
+                                      clip_eps=clip_eps, ratio=ratio, **kw)
 
     def _advance_dropout_step(self):
         self._rng_cpu[1] = (self._rng_cpu[1] + 1) & 0xFFFFFFFF

@@ -97,6 +97,17 @@ def parse_runner_args(parser):
                         "deviation (grpo), or the reward itself (none)")
     parser.add_argument("--policy_coef", type=float, default=1.0, help="weight of the policy-gradient term")
     parser.add_argument("--policy_sft_coef", type=float, default=1.0, help="weight of the likelihood of the gold item (0 = the draws alone)")
+    parser.add_argument("--policy_clip_eps", type=float, default=0.0, help="eps > 0 = the clipped-ratio (PPO / GRPO style) objective on the draws "
+                        "(P5T5Native.policy_collect / policy_update): a draw whose probability ratio to the sampled policy left [1 - eps, 1 + eps_high] "
+                        "on the side its advantage pushes to gets no gradient.  0 = off, nothing changes.")
+    parser.add_argument("--policy_clip_eps_high", type=float, default=-1.0, help="upper clip range (negative = --policy_clip_eps)")
+    parser.add_argument("--policy_ratio", type=str, default="token", choices=["token", "sequence"], help="per-token ratios, or one length-normalised "
+                        "ratio per draw")
+    parser.add_argument("--policy_epochs", type=int, default=1, help="E optimizer steps per sampled batch (E > 1 needs --policy_clip_eps > 0 and "
+                        "--gradient_accumulation_steps 1); the schedule runs over batches x E steps")
+    parser.add_argument("--policy_old_logprobs", type=str, default="sampler", choices=["sampler", "forward"], help="the sampled policy's "
+                        "log-probabilities: the sampler's own (free), or recomputed by one training-path forward (the first update's ratio is then "
+                        "exactly 1 without dropout)")
     parser.add_argument("--policy_token_sum", type=int, default=0, choices=[0, 1], help="1 = a draw's term is the SUM of its tokens' NLL (REINFORCE "
                         "proper) instead of their mean")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
@@ -188,6 +199,30 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
     return loss.detach()
 
 
+def policy_clip_steps(model, optimizer, batch, item_loss, policy, clip):
+    """One sampled batch of the clipped-ratio objective with E = clip["epochs"] optimizer steps: `P5T5Native.policy_collect` once, then E x
+    (`policy_update`, clip + AdamW + scheduler, zero_grad).  `policy`: the keywords of `training_step`'s `policy` (with "seed"); `clip`:
+    {"clip_eps", "ratio", "old_logprobs", "epochs"}.  Returns (mean loss of the E updates, their `last_clip_stats` stacked [E, 8]), on the
+    device, no host sync."""
+    kw = dict(item_loss or {})
+    if not hasattr(model, "policy_collect") or "trie" not in kw:
+        raise ValueError("the clipped policy objective needs the native model and the item loss's keywords (trie=...)")
+    input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
+    ref_model = kw.pop("ref_model", None)
+    kw.pop("ref_logits", None)
+    rollout = model.policy_collect(input_ids, whole_ids, attn, output_ids, output_attention, ref_model=ref_model, clip_eps=clip["clip_eps"],
+                                   ratio=clip["ratio"], old_logprobs=clip["old_logprobs"], **kw, **policy)
+    upd = {k: v for k, v in kw.items() if k in ("temperature", "excluded_items", "item_head", "entropy_coef", "kl_coef")}
+    losses, stats = [], []
+    for _ in range(int(clip["epochs"])):
+        model.begin_micro_batch(first=True, sync=True)
+        losses.append(model.policy_update(input_ids, whole_ids, attn, rollout, kw["trie"], clip["clip_eps"], ratio=clip["ratio"], **upd).detach())
+        stats.append(model.last_clip_stats)
+        optimizer.step()
+        model.zero_grad()
+    return torch.stack(losses).mean(), torch.stack(stats)
+
+
 class Prefetcher:
     """Background collation: the DataLoader (tokenisation + whole-word ids, num_workers=0 as in main.py:61) runs in a thread
     and stays `depth` batches ahead, so host-side batch preparation overlaps the asynchronously issued GPU step instead of
@@ -270,6 +305,8 @@ class DistributedRunner:
         batch_per_epoch = len(self.train_loader)
         # one optimizer step per group of `accum` batches, the trailing (shorter) group of an epoch included
         total_steps = math.ceil(batch_per_epoch / max(1, self.args.gradient_accumulation_steps)) * self.args.epochs
+        if getattr(self, "_policy_clip", None) is not None:
+            total_steps *= self._policy_clip["epochs"]          # (E optimizer steps per sampled batch)
         warmup_steps = int(total_steps * self.args.warmup_prop)
         if self.rank == 0:
             logging.info(f"Batch per epoch: {batch_per_epoch}; total steps: {total_steps}; warm up steps: {warmup_steps}")
@@ -408,14 +445,28 @@ class DistributedRunner:
                                          micro=micro, accum=gsize, item_loss=self._item_loss_kw())
                 else:
                     pol = dict(self._policy, seed=policy_seed(getattr(self.args, "seed", 0), self.optimizer.t, micro, self.rank))
-                    loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
-                                         micro=micro, accum=gsize, item_loss=self._item_loss_kw(), policy=pol)
+                    clip_stats = None
+                    if self._policy_clip is None:
+                        loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
+                                             micro=micro, accum=gsize, item_loss=self._item_loss_kw(), policy=pol)
+                    elif accum > 1:           # (one update per batch: the accumulating step with the clipped objective inside policy_step)
+                        cl = {k: v for k, v in self._policy_clip.items() if k != "epochs"}
+                        loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
+                                             micro=micro, accum=gsize, item_loss=self._item_loss_kw(), policy=dict(pol, **cl))
+                        clip_stats = self.model.last_clip_stats[None]
+                    else:
+                        loss, clip_stats = policy_clip_steps(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention),
+                                                             self._item_loss_kw(), pol, self._policy_clip)
                     # the one host read of the statistics -- and of this batch's loss: this runner logs no per-batch loss elsewhere, so with the
                     # flag on rank 0 synchronises with the device once per --logging_step batches; with the flag off nothing is read
                     if self.rank == 0 and n_batches % max(1, int(self.args.logging_step)) == 0:
                         st = [float(x) for x in self.model.last_policy_stats[:6].cpu()]
                         logging.info(f"policy step {self.optimizer.t} batch {n_batches}: loss {float(loss):.6f} "
                                      + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.POLICY_STATS, st)))
+                        if clip_stats is not None:
+                            cs = [float(x) for x in clip_stats.mean(0).cpu()]
+                            logging.info(f"policy clip step {self.optimizer.t} batch {n_batches} (mean of {clip_stats.shape[0]} updates): "
+                                         + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.CLIP_STATS, cs)))
                 losses.append(loss)
                 n_samples += input_ids.shape[0]
                 if resume and save_steps > 0 and micro == gsize - 1 and self.optimizer.t % save_steps == 0:
@@ -466,8 +517,31 @@ class DistributedRunner:
     def _policy_flags(self):
         """--train_policy_samples S: the keyword arguments of `P5T5Native.policy_step` (None with the flag at 0), every flag checked here."""
         S = int(getattr(self.args, "train_policy_samples", 0))
+        self._policy_clip = None
+        eps = float(getattr(self.args, "policy_clip_eps", 0.0))
+        eps_high = float(getattr(self.args, "policy_clip_eps_high", -1.0))
+        E = int(getattr(self.args, "policy_epochs", 1))
+        if not (math.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"--policy_clip_eps {eps}: a finite value >= 0 (0 = off)")
+        if E < 1:
+            raise ValueError(f"--policy_epochs {E}: at least one update per sampled batch")
+        if E > 1 and eps == 0.0:
+            raise ValueError(f"--policy_epochs {E} requires --policy_clip_eps > 0: updates behind the first are off-policy without the clipped ratio")
+        if E > 1 and int(getattr(self.args, "gradient_accumulation_steps", 1)) > 1:
+            raise ValueError(f"--policy_epochs {E} cannot be combined with --gradient_accumulation_steps > 1")
+        if eps > 0.0 and S == 0:
+            raise ValueError("--policy_clip_eps requires --train_policy_samples > 0")
         if S == 0:
             return None
+        if eps > 0.0:
+            if eps_high >= 0.0 and not math.isfinite(eps_high):
+                raise ValueError(f"--policy_clip_eps_high {eps_high}: a finite value (negative = --policy_clip_eps)")
+            if not hasattr(self.model, "policy_collect"):
+                raise ValueError("--policy_clip_eps needs the native model (P5T5Native)")
+            if int(getattr(self.args, "item_loss_top_k", 0) or 0) > 0 or float(getattr(self.args, "item_loss_top_p", 1.0) or 1.0) < 1.0:
+                raise ValueError("--policy_clip_eps is not built for the truncated item loss (top_k / top_p)")
+            self._policy_clip = {"clip_eps": (eps, eps_high if eps_high >= 0.0 else eps), "ratio": str(getattr(self.args, "policy_ratio", "token")),
+                                 "old_logprobs": str(getattr(self.args, "policy_old_logprobs", "sampler")), "epochs": E}
         if S < 0:
             raise ValueError(f"--train_policy_samples {S}: the number of draws per user (0 = off)")
         if not int(getattr(self.args, "train_item_loss", 0)):
