@@ -740,6 +740,30 @@ int p5_policy_batch_clip(const int64_t* sequences, const int64_t* labels, const 
                          float adv_eps, int with_gold, int pad_id, int eos_id, int64_t* labels_out, int64_t* attention_out, float* rewards_out,
                          float* advantages, float* weights_out, float* user_stats, float* stats, float* old_logprobs_out, int* target_mode_out,
                          void* stream);
+/* The batch of an on-policy step from SLATES (p5_slate_policy.h): the importance-weighted without-replacement estimator of Kool, van Hoof and
+ * Welling on what p5_sample_slates(slate_size = K1 = K + 1) returned; two launches on `stream`, stateless.  Per user S slates of K1 slots:
+ * sequences int64 [B*S*K1, Ts], sequences_logprob fp32 [B*S*K1] (log p(item)), perturbed fp32 [B, S, K1] (descending); slot K of a slate is the
+ * threshold kappa only and becomes no training row (kappa = -inf: the allowed items ran out, every slot has inclusion probability 1).
+ * rewards fp32 [B, S, K1] (the last slot is never read) or NULL = the hit reward; token_logprobs fp32 [B*S*K1, Ts-1] or NULL.
+ * omega = p / q_kappa, q_kappa = 1 - exp(-exp(log p - kappa)); estimator 0 unbiased A = omega r, 1 normalized A = (omega / W)(r - V / W) with
+ * W = sum omega, V = sum omega r over the slate's existing slots (K >= 2).  With G = S*K + with_gold, To = max(Tg, Ts - 1): labels_out /
+ * attention_out int64 [B, G, To] (slot 0 = the gold when with_gold, then the slates in (slate, slot) order), rewards_out / advantages /
+ * importance fp32 [B, S, K], weights_out fp32 [B, G] (w[b, 0] = sft_coef G, the others policy_coef A G / S, times the token count when
+ * token_sum), slate_stats fp32 [B, S, 4] = (V, W, kappa, W^2 / sum omega^2), user_stats fp32 [B, 8] (scratch of the second launch), stats
+ * fp32 [8]: mean V and mean W over the slates with an existing slot, share of users with a non-zero advantage, mean |A|, share of slates
+ * that contain the gold, share of slates with kappa = -inf, users without a draw, mean effective sample size.  old_logprobs_out fp32
+ * [B, G, To] (with token_logprobs, else NULL) and target_mode_out int32 [B, G] (nullable) as p5_policy_batch_clip writes them.  No atomics.
+ * root_streams int32 [B] (nullable) with root_seed / slate_base: the stream ids, seed and slate_base the slates were drawn with by
+ * p5_sample_slates, whose root starts at G = 0 (the maximum of the perturbed values is conditioned to be 0): kappa is then un-conditioned
+ * with one Exp(1) draw per slate, E = -log u(seed, stream, slate, step 0, edge 2^32 - 1) of p5_rng.h, kappa = g[K] - log1p((E - 1) exp(g[K])).
+ * NULL: perturbed holds unconditioned values log p + Gumbel and kappa = g[K] as it is.  slate_stats reports the kappa that was used.
+ * Non-zero (p5_last_error) for NULL required pointers, K1 < 2, S * K1 > 1024, Ts < 2, an unknown estimator, normalized with K1 = 2. */
+int p5_policy_slate_batch(const int64_t* sequences, const float* sequences_logprob, const float* perturbed, const int64_t* labels,
+                          const int64_t* output_attention, const float* rewards, const float* token_logprobs, int B, int S, int K1, int Ts, int Tg,
+                          int estimator, float policy_coef, float sft_coef, int token_sum, int with_gold, int pad_id, int eos_id, int64_t* labels_out,
+                          int64_t* attention_out, float* rewards_out, float* advantages, float* importance, float* weights_out, float* slate_stats,
+                          float* user_stats, float* stats, float* old_logprobs_out, int* target_mode_out, const int* root_streams, uint32_t root_seed,
+                          uint32_t slate_base, void* stream);
 /* The two kernels of p5_train_set_clip_objective behind a given per-token NLL, no engine: nll / old_logprobs fp32 [B*G*T], out_attn / labels
  * int64 [B*G*T], tw fp32 [B*G] or NULL, target_mode int32 [B*G] or NULL, entropy_rows / kl_rows fp32 [B*G*T] or NULL (the regularised loss:
  * terms fp32 [3] or NULL receives its parts, row_seed is [3*B*G*T] then, else [B*G*T]), user_partials fp32 [B*16], clip_stats fp32 [8]. */

@@ -146,6 +146,7 @@ PROTOTYPES = {
     "p5_op_masked_mean_g": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "p5_policy_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "p5_policy_batch_clip": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "p5_policy_slate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp]),
     "p5_op_clip_objective": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),

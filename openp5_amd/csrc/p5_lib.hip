@@ -33,6 +33,7 @@
 #include "p5_item_head.h"
 #include "p5_trunc.h"
 #include "p5_policy.h"
+#include "p5_slate_policy.h"
 #include "p5_clip.h"
 #include "../../include/p5hip.h"
 
@@ -5046,6 +5047,40 @@ int p5_policy_batch_clip(const int64_t* sequences, const int64_t* labels, const 
   return policy_batch_impl(sequences, labels, output_attention, rewards, B, S, Ts, Tg, baseline, policy_coef, sft_coef, token_sum, adv_eps, with_gold, pad_id,
                            eos_id, labels_out, attention_out, rewards_out, advantages, weights_out, user_stats, stats, token_logprobs, old_logprobs_out,
                            target_mode_out, stream);
+}
+// the batch of an on-policy step from slates (p5_slate_policy.h): the importance-weighted without-replacement estimator; both launches, stateless
+int p5_policy_slate_batch(const int64_t* sequences, const float* sequences_logprob, const float* perturbed, const int64_t* labels,
+                          const int64_t* output_attention, const float* rewards, const float* token_logprobs, int B, int S, int K1, int Ts, int Tg,
+                          int estimator, float policy_coef, float sft_coef, int token_sum, int with_gold, int pad_id, int eos_id, int64_t* labels_out,
+                          int64_t* attention_out, float* rewards_out, float* advantages, float* importance, float* weights_out, float* slate_stats,
+                          float* user_stats, float* stats, float* old_logprobs_out, int* target_mode_out, const int* root_streams, uint32_t root_seed,
+                          uint32_t slate_base, void* stream) {
+  P5_REQUIRE(sequences && sequences_logprob && perturbed && labels && output_attention,
+             "policy_slate_batch: null input pointer (sequences, sequences_logprob, perturbed, labels, output_attention)");
+  P5_REQUIRE(labels_out && attention_out && rewards_out && advantages && importance && weights_out && slate_stats && user_stats && stats,
+             "policy_slate_batch: null output pointer");
+  P5_REQUIRE((token_logprobs != nullptr) == (old_logprobs_out != nullptr), "policy_slate_batch: token_logprobs and old_logprobs_out go together (both or neither)");
+  P5_REQUIRE(B >= 1 && Tg >= 1 && Tg <= (1 << 24), "policy_slate_batch: shapes B >= 1, 1 <= Tg <= 2^24");
+  P5_REQUIRE(Ts >= 2, "policy_slate_batch: Ts >= 2 (the decoder start and at least one token)");
+  P5_REQUIRE(S >= 1, "policy_slate_batch: S >= 1 slates per user");
+  P5_REQUIRE(K1 >= 2, "policy_slate_batch: K1 >= 2 (K >= 1 used slots and the threshold slot)");
+  P5_REQUIRE((int64_t)S * K1 <= P5_SLATE_POLICY_MAX_SLOTS, "policy_slate_batch: S * K1 <= 1024 slots per user");
+  P5_REQUIRE(estimator == P5_SLATE_UNBIASED || estimator == P5_SLATE_NORMALIZED, "policy_slate_batch: unknown estimator (0 unbiased, 1 normalized)");
+  P5_REQUIRE(estimator != P5_SLATE_NORMALIZED || K1 >= 3, "policy_slate_batch: the normalized estimator needs K >= 2 (K1 >= 3)");
+  P5_REQUIRE(std::isfinite(policy_coef) && std::isfinite(sft_coef), "policy_slate_batch: non-finite coefficient (policy_coef, sft_coef)");
+  P5_REQUIRE((token_sum == 0 || token_sum == 1) && (with_gold == 0 || with_gold == 1), "policy_slate_batch: token_sum and with_gold are 0 or 1");
+  P5SlatePolicyArgs a;
+  a.seq = sequences; a.logp = sequences_logprob; a.pert = perturbed; a.labels = labels; a.out_attn = output_attention; a.rewards = rewards;
+  a.token_lp = token_logprobs; a.labels_out = labels_out; a.attn_out = attention_out; a.rewards_out = rewards_out; a.adv = advantages;
+  a.importance = importance; a.weights = weights_out; a.slate_stats = slate_stats; a.user_stats = user_stats; a.old_lp_out = old_logprobs_out;
+  a.mode_out = target_mode_out; a.streams = root_streams; a.seed = root_seed; a.slate_base = slate_base;
+  a.S = S; a.K1 = K1; a.Ts = Ts; a.Tg = Tg; a.To = Tg > Ts - 1 ? Tg : Ts - 1; a.estimator = estimator; a.token_sum = token_sum; a.with_gold = with_gold;
+  a.pad_id = pad_id; a.eos_id = eos_id; a.policy_coef = policy_coef; a.sft_coef = sft_coef;
+  P5_REQUIRE((int64_t)(S * (K1 - 1) + with_gold) * a.To <= (int64_t)1 << 30, "policy_slate_batch: G * To too large");
+  hipStream_t s = (hipStream_t)stream;
+  P5_LAUNCH(p5_policy_slate_batch_kernel, dim3(B), dim3(256), 0, s, a);
+  P5_LAUNCH(p5_policy_slate_stats_kernel, dim3(1), dim3(256), 0, s, stats, user_stats, B);
+  return P5_KCHECK();
 }
 int p5_op_skinny_gemm(int dtype, int amode, const void* A, int lda, const float* ln, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                       int epi, float alpha, float eps, void* stream) {

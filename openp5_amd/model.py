@@ -1013,9 +1013,129 @@ class P5T5Native(nn.Module):
         return {"labels": lab_o, "output_attention": att_o, "target_weights": w_o.view(B, G), "rewards": r_o.view(B, S), "advantages": a_o.view(B, S),
                 "stats": st}
 
+    SLATE_ESTIMATORS = {"unbiased": 0, "normalized": 1}
+    SLATE_POLICY_STATS = ("value_mean", "weight_sum_mean", "users_with_signal", "abs_advantage_mean", "slates_with_hit", "slates_exhausted",
+                          "users_without_draw", "ess_mean")
+    SLATE_POLICY_MAX_SLOTS = 1024          # num_slates * (slate_size + 1) per user (csrc/p5_slate_policy.h)
+
+    def _slate_policy_args(self, slate_size, num_slates, estimator, policy_coef, sft_coef, token_sum):
+        """the checked scalars of policy_slate_batch / policy_step(slate_size=...): (K, S, estimator code, policy_coef, sft_coef, token_sum,
+        with_gold)"""
+        if isinstance(slate_size, bool) or int(slate_size) != slate_size or int(slate_size) < 1:
+            raise ValueError(f"slate_size={slate_size!r}: an integer >= 1 (items per slate; the sampler draws slate_size + 1, the last one is the threshold)")
+        if isinstance(num_slates, bool) or int(num_slates) != num_slates or int(num_slates) < 1:
+            raise ValueError(f"num_samples={num_slates!r}: an integer >= 1 (slates per user)")
+        K, S = int(slate_size), int(num_slates)
+        if estimator not in self.SLATE_ESTIMATORS:
+            raise ValueError(f"slate_estimator={estimator!r}: one of {sorted(self.SLATE_ESTIMATORS)}")
+        if estimator == "normalized" and K < 2:
+            raise ValueError(f'slate_estimator="normalized" needs slate_size >= 2 (got {K}): its baseline is the slate\'s own weighted mean reward; '
+                             'use "unbiased"')
+        if S * (K + 1) > self.SLATE_POLICY_MAX_SLOTS:
+            raise ValueError(f"num_samples * (slate_size + 1) = {S * (K + 1)}: at most {self.SLATE_POLICY_MAX_SLOTS} slots per user")
+        pc, sc = float(policy_coef), float(sft_coef)
+        if not (math.isfinite(pc) and math.isfinite(sc)):
+            raise ValueError(f"policy_coef={policy_coef!r}, sft_coef={sft_coef!r}: finite values")
+        return K, S, self.SLATE_ESTIMATORS[estimator], pc, sc, 1 if token_sum else 0, 0 if sc == 0.0 else 1
+
+    @torch.no_grad()
+    def policy_slate_batch(self, sampled, labels, output_attention, slate_size, num_slates, rewards=None, estimator="normalized", policy_coef=1.0,
+                           sft_coef=1.0, token_sum=False, with_old_logprobs=False):
+        """The batch of one on-policy step from SLATES: the importance-weighted without-replacement estimator of Kool, van Hoof and Welling
+        (2019, 2020), built on the device in two launches (csrc/p5_slate_policy.h), no host sync.  `sampled` is the dict of
+        `sample_slates(slate_size=slate_size + 1, num_slates=num_slates)`: the extra slot's perturbed value is the threshold kappa, an item s
+        enters the slate with probability q(s) = 1 - exp(-exp(log p(s) - kappa)), and sum_{s in slate} p(s) / q(s) f(s) estimates E_p[f] without
+        bias; the threshold slot becomes no training row.  A user whose allowed items all fit in the slate has kappa = -inf and weights p: the
+        exact expectation.  q is the inclusion probability under UNCONDITIONED perturbed values; the sampler's are conditioned on a maximum of
+        0, so with sampled["noise_key"] (which `sample_slates` returns) the kernel un-conditions kappa with one Exp(1) draw per slate keyed
+        by the slate's own (seed, stream, index) -- without it the estimator is biased (mean W 0.94 instead of 1 at 8 items, K = 3).  A dict
+        without "noise_key" is taken to hold unconditioned values log p + Gumbel.
+        `rewards` fp32 [B, S, K + 1] (the last slot is never read) or None = the hit reward.  `estimator`: "unbiased"
+        A = omega r; "normalized" A = (omega / W)(r - V / W) with W = sum omega, V = sum omega r over the slate (slate_size >= 2): biased,
+        consistent, lower in variance; a slate whose rewards are all equal gets A exactly 0.
+        Returns the dict of `policy_batch` -- "labels" / "output_attention" [B, G, To], "target_weights" [B, G] with G = S K + 1 (slot 0 = the
+        gold; G = S K when sft_coef == 0), "rewards" / "advantages" [B, S, K] -- plus "importance" [B, S, K] (omega), "slate_stats" [B, S, 4] =
+        (V, W, kappa, effective sample size W^2 / sum omega^2) and "stats" fp32 [8] named by `SLATE_POLICY_STATS`.  `loss_and_backward` on them
+        is sft_coef * mean_b nll(gold_b) + policy_coef * mean_b (1/S) sum_j sum_i A_bji nll_bji.  The estimator's unbiasedness is that of
+        `token_sum=True`: the weights refer to log p(item), the SUM of the item's token log-probabilities; `token_sum=False` is the
+        length-normalised variant the plain step also offers.  `with_old_logprobs`: the dict gains "old_logprobs" fp32 [B, G, To] and
+        "target_mode" int32 [B, G], the clipped objective's inputs, as `policy_batch(token_logprobs=...)` returns them."""
+        K, S, est, pc, sc, tsum, with_gold = self._slate_policy_args(slate_size, num_slates, estimator, policy_coef, sft_coef, token_sum)
+        K1, dev = K + 1, self._be.device
+        try:
+            seq, lp, pert = sampled["sequences"], sampled["sequences_logprob"], sampled["perturbed"]
+            tok_lp = sampled["token_logprobs"] if with_old_logprobs else None
+        except (TypeError, KeyError):
+            raise ValueError('sampled: the dict of sample_slates ("sequences", "sequences_logprob", "perturbed", "token_logprobs")') from None
+        if not torch.is_tensor(seq) or seq.dim() != 2 or seq.shape[0] == 0 or seq.shape[0] % (S * K1) != 0 or seq.shape[1] < 2:
+            raise ValueError(f"sampled['sequences'] {tuple(getattr(seq, 'shape', ()))}: [B * num_slates * (slate_size + 1), Ts] with num_slates = {S}, "
+                             f"slate_size + 1 = {K1}, Ts >= 2 -- draw with sample_slates(slate_size={K1})")
+        B, Ts = seq.shape[0] // (S * K1), int(seq.shape[1])
+        if not torch.is_tensor(lp) or lp.numel() != B * S * K1 or not torch.is_tensor(pert) or pert.numel() != B * S * K1:
+            raise ValueError(f"sampled['sequences_logprob'] / ['perturbed']: {B * S * K1} values each, one per slot")
+        labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
+        G, To = self._check_policy_shapes(B, S * K, Ts, labels, output_attention, with_gold)
+        if rewards is not None:
+            if not torch.is_tensor(rewards) or tuple(rewards.shape) != (B, S, K1):
+                raise ValueError(f"rewards {tuple(getattr(rewards, 'shape', ()))}: a tensor [B, S, slate_size + 1] = {(B, S, K1)}")
+            rewards = rewards.to(device=dev, dtype=torch.float32).contiguous()
+        if tok_lp is not None:
+            if not torch.is_tensor(tok_lp) or tuple(tok_lp.shape) != (B * S * K1, Ts - 1):
+                raise ValueError(f"sampled['token_logprobs'] {tuple(getattr(tok_lp, 'shape', ()))}: a tensor {(B * S * K1, Ts - 1)}")
+            tok_lp = tok_lp.to(device=dev, dtype=torch.float32).contiguous()
+        seq, labels, output_attention = self._i64(seq, dev), self._i64(labels, dev), self._i64(output_attention, dev)
+        lp, pert = lp.to(device=dev, dtype=torch.float32).contiguous(), pert.to(device=dev, dtype=torch.float32).contiguous()
+        lab_o = torch.empty(B, G, To, dtype=torch.int64, device=dev)
+        att_o = torch.empty(B, G, To, dtype=torch.int64, device=dev)
+        n = B * S * K
+        f = torch.empty(3 * n + B * G + 4 * B * S + 8 * B + 8, dtype=torch.float32, device=dev)   # rewards | advantages | importance | weights | slate stats | user stats | stats
+        r_o, a_o, i_o, w_o, ss, us, st = torch.split(f, [n, n, n, B * G, 4 * B * S, 8 * B, 8])
+        old_o = mode_o = None
+        if tok_lp is not None:
+            old_o = torch.empty(B, G, To, dtype=torch.float32, device=dev)
+            mode_o = torch.empty(B, G, dtype=torch.int32, device=dev)
+        r_seed, r_streams, r_base = 0, None, 0
+        if sampled.get("noise_key") is not None:
+            r_seed, r_streams, r_base = sampled["noise_key"]
+            if not torch.is_tensor(r_streams) or r_streams.numel() != B:
+                raise ValueError(f"sampled['noise_key']: (seed, stream ids [B = {B}], slate_base) as sample_slates returns it")
+            r_streams = r_streams.to(device=dev, dtype=torch.int32).contiguous()
+            r_seed, r_base = int(r_seed) & 0xFFFFFFFF, int(r_base) & 0xFFFFFFFF
+        self._be.check(self._lib.p5_policy_slate_batch(_ptr(seq), _ptr(lp), _ptr(pert), _ptr(labels), _ptr(output_attention), _ptr(rewards), _ptr(tok_lp), B, S,
+                                                       K1, Ts, int(labels.shape[1]), est, pc, sc, tsum, with_gold, int(self.config.pad_token_id),
+                                                       int(self.config.eos_token_id), _ptr(lab_o), _ptr(att_o), _ptr(r_o), _ptr(a_o), _ptr(i_o), _ptr(w_o),
+                                                       _ptr(ss), _ptr(us), _ptr(st), _ptr(old_o), _ptr(mode_o), _ptr(r_streams), r_seed, r_base,
+                                                       self._be.stream_ptr()),
+                       "p5_policy_slate_batch")
+        out = {"labels": lab_o, "output_attention": att_o, "target_weights": w_o.view(B, G), "rewards": r_o.view(B, S, K), "advantages": a_o.view(B, S, K),
+               "importance": i_o.view(B, S, K), "slate_stats": ss.view(B, S, 4), "stats": st}
+        if tok_lp is not None:
+            out.update(old_logprobs=old_o, target_mode=mode_o)
+        return out
+
+    def _check_slate_step(self, trie, slate_size, num_samples, slate_estimator, baseline, top_k, top_p, policy_coef, sft_coef, token_sum):
+        """the refusals of policy_step / policy_collect with `slate_size` set, raised before anything is sampled; returns the checked scalars of
+        `_slate_policy_args`"""
+        q = self._slate_policy_args(slate_size, num_samples, slate_estimator, policy_coef, sft_coef, token_sum)
+        tk, tp = self._truncation(top_k, top_p)
+        if tk > 0 or tp < 1.0:
+            raise ValueError("slate_size: the slate sampler has no truncation (top_k / top_p); use the plain step (slate_size=None) for truncated draws")
+        if baseline != "loo":
+            raise ValueError(f'slate_size: baseline={baseline!r} belongs to the plain step; a slate\'s baseline is chosen by slate_estimator '
+                             '("normalized" = the slate\'s own weighted mean, "unbiased" = none)')
+        if trie.grafted:
+            raise ValueError("slate_size: a trie with an appended trie (Trie.append) is a DAG, which sample_slates refuses; use the plain step "
+                             "(slate_size=None)")
+        K1 = q[0] + 1
+        if K1 > self.SLATE_MAX_K or K1 > int(self.wide_max_rows):
+            raise ValueError(f"slate_size={q[0]}: the sampler draws slate_size + 1 = {K1} items per slate, at most min(SLATE_MAX_K, wide_max_rows) = "
+                             f"{min(self.SLATE_MAX_K, int(self.wide_max_rows))}; use a smaller slate and more slates (num_samples)")
+        return q
+
     def policy_step(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=1.0, excluded_items=None,
                     top_k=0, top_p=1.0, item_head=None, baseline="loo", policy_coef=1.0, sft_coef=1.0, token_sum=False, reward_fn=None, seed=None,
-                    streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None, clip_eps=None, ratio="token", old_logprobs="sampler"):
+                    streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None, clip_eps=None, ratio="token", old_logprobs="sampler", slate_size=None,
+                    slate_estimator="normalized"):
         """One on-policy fine-tuning step: (1) `sample_items(num_samples=...)` with the trie, temperature, exclusion and truncation the loss
         uses -- that sameness is what on-policy means here; (2) `policy_batch` on the draws (`reward_fn`, if given, is called with the
         sampler's dict and returns fp32 [B, S] on the device; else the hit reward against `labels`); (3) `loss_and_backward` on the grouped
@@ -1026,18 +1146,31 @@ class P5T5Native(nn.Module):
         anything is sampled.  Sampling ignores `self.training` (no dropout in the draw, as in `sample_items`); the training forward applies
         dropout as usual, so under dropout the draws come from the dropout-free policy.  `seed` / `streams`: those of `sample_items`.
         `clip_eps` (None = off: the step above, bit for bit): `policy_collect` and then ONE `policy_update` with the clipped-ratio objective
-        (`ratio`, `old_logprobs`: theirs) -- call the two yourself for several updates per sampled batch."""
+        (`ratio`, `old_logprobs`: theirs) -- call the two yourself for several updates per sampled batch.
+        `slate_size=K` (None = off: the step above, bit for bit): the draws are `num_samples` SLATES of K distinct items per user,
+        `sample_slates(slate_size=K + 1, num_slates=num_samples)` (the extra slot is the threshold), `reward_fn` returns fp32 [B, S, K + 1], and
+        the batch comes from `policy_slate_batch(estimator=slate_estimator)`: the importance-weighted without-replacement estimator, G = S K + 1
+        training rows.  Its unbiasedness ("unbiased") is that of `token_sum=True`: the weights refer to log p(item); `token_sum=False` is the
+        length-normalised variant the plain step also offers.  With `slate_size` set, `top_k` / `top_p` (the slate sampler has no truncation), a
+        `baseline` other than its default (the slate's baseline is `slate_estimator`'s), a grafted trie and K + 1 above `SLATE_MAX_K` /
+        `wide_max_rows` are ValueErrors raised before anything is sampled.  `last_policy_stats` are then named by `SLATE_POLICY_STATS`."""
         if clip_eps is not None:
             rollout = self.policy_collect(input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=temperature,
                                           excluded_items=excluded_items, top_k=top_k, top_p=top_p, item_head=item_head, baseline=baseline,
                                           policy_coef=policy_coef, sft_coef=sft_coef, token_sum=token_sum, reward_fn=reward_fn, seed=seed, streams=streams,
                                           entropy_coef=entropy_coef, kl_coef=kl_coef, ref_model=ref_model, old_logprobs=old_logprobs, clip_eps=clip_eps,
-                                          ratio=ratio)
+                                          ratio=ratio, **({} if slate_size is None else dict(slate_size=slate_size, slate_estimator=slate_estimator)))
             return self.policy_update(input_ids, whole_word_ids, attention_mask, rollout, trie, clip_eps, ratio=ratio, temperature=temperature,
                                       excluded_items=excluded_items, item_head=item_head, entropy_coef=entropy_coef, kl_coef=kl_coef)
         if trie is None:
             raise ValueError("policy_step needs trie=...: the draws and the item loss share it")
-        S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
+        K = None
+        if slate_size is not None:
+            trie = self._compiled_trie(trie)
+            K, S, _, _, _, _, with_gold = self._check_slate_step(trie, slate_size, num_samples, slate_estimator, baseline, top_k, top_p, policy_coef,
+                                                                 sft_coef, token_sum)
+        else:
+            S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
         item_head = self._item_head_mode(item_head, trie)
         top_k, top_p = self._truncation(top_k, top_p)
         ec, kc = float(entropy_coef), float(kl_coef)
@@ -1054,12 +1187,19 @@ class P5T5Native(nn.Module):
         depth = int(trie.max_depth)
         Ts = max(2, depth)
         labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
-        self._check_policy_shapes(B, S, Ts, labels, output_attention, with_gold)
-        drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
-                                  temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams, top_k=top_k, top_p=top_p)
-        rewards = None if reward_fn is None else reward_fn(drawn)
-        pb = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=rewards, baseline=baseline, policy_coef=policy_coef,
-                               sft_coef=sft_coef, token_sum=token_sum)
+        self._check_policy_shapes(B, S if K is None else S * K, Ts, labels, output_attention, with_gold)
+        if K is None:
+            drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
+                                      temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams, top_k=top_k, top_p=top_p)
+            rewards = None if reward_fn is None else reward_fn(drawn)
+            pb = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=rewards, baseline=baseline, policy_coef=policy_coef,
+                                   sft_coef=sft_coef, token_sum=token_sum)
+        else:
+            drawn = self.sample_slates(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, slate_size=K + 1,
+                                       num_slates=S, temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
+            rewards = None if reward_fn is None else reward_fn(drawn)
+            pb = self.policy_slate_batch(drawn, labels, output_attention, K, S, rewards=rewards, estimator=slate_estimator, policy_coef=policy_coef,
+                                         sft_coef=sft_coef, token_sum=token_sum)
         kw = {}
         if ec != 0.0 or kc != 0.0:
             kw.update(entropy_coef=ec, kl_coef=kc)
@@ -1075,7 +1215,7 @@ class P5T5Native(nn.Module):
     def policy_collect(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_samples, temperature=1.0,
                        excluded_items=None, top_k=0, top_p=1.0, item_head=None, baseline="loo", policy_coef=1.0, sft_coef=1.0, token_sum=False,
                        reward_fn=None, seed=None, streams=None, entropy_coef=0.0, kl_coef=0.0, ref_model=None, old_logprobs="sampler", clip_eps=0.2,
-                       ratio="token"):
+                       ratio="token", slate_size=None, slate_estimator="normalized"):
         """The rollout of a clipped-ratio (PPO / GRPO style) step: `sample_items` and `policy_batch` as in `policy_step`, ONCE, for several
         `policy_update` calls.  Returns the dict of `policy_batch` plus "old_logprobs" fp32 [B, G, To] (the behaviour policy's log-probability
         of every label), "target_mode" int32 [B, G] (gold 0, draws 1), "sampled" (the sampler's dict) and -- with `kl_coef != 0` -- "ref_logits"
@@ -1083,13 +1223,21 @@ class P5T5Native(nn.Module):
         `old_logprobs`: "sampler" = the sampler's `token_logprobs`, which cost nothing (the decode kernels and the training forward differ in
         their last bits: the first update's ratio is 1 up to those); "forward" = recomputed with one grouped item-loss forward of this model,
         no gradient, no dropout: the first update's ratio is then exactly 1 when dropout is off.  `clip_eps` / `ratio` / `entropy_coef` are only
-        checked here (every refusal of the update is raised before anything is sampled).  Not under top_k / top_p."""
+        checked here (every refusal of the update is raised before anything is sampled).  Not under top_k / top_p.
+        `slate_size` / `slate_estimator`: those of `policy_step` -- slates and `policy_slate_batch(with_old_logprobs=True)` in place of draws
+        and `policy_batch`."""
         if trie is None:
             raise ValueError("policy_collect needs trie=...: the draws and the item loss share it")
         if old_logprobs not in ("sampler", "forward"):
             raise ValueError(f'old_logprobs={old_logprobs!r}: "sampler" (the sampler\'s token_logprobs) or "forward" (recomputed by a training-path forward)')
         self._clip_args(True, None, clip_eps, ratio, top_k, top_p)
-        S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
+        K = None
+        if slate_size is not None:
+            trie = self._compiled_trie(trie)
+            K, S, _, _, _, _, with_gold = self._check_slate_step(trie, slate_size, num_samples, slate_estimator, baseline, top_k, top_p, policy_coef,
+                                                                 sft_coef, token_sum)
+        else:
+            S, _, _, _, _, _, with_gold = self._policy_args(num_samples, baseline, policy_coef, sft_coef, token_sum, 1e-6)
         item_head = self._item_head_mode(item_head, trie)
         ec, kc = float(entropy_coef), float(kl_coef)
         if not (math.isfinite(ec) and math.isfinite(kc)):
@@ -1101,12 +1249,19 @@ class P5T5Native(nn.Module):
         B = int(input_ids.shape[0])
         Ts = max(2, int(trie.max_depth))
         labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
-        self._check_policy_shapes(B, S, Ts, labels, output_attention, with_gold)
-        drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
-                                  temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
-        rewards = None if reward_fn is None else reward_fn(drawn)
-        rollout = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=rewards, baseline=baseline, policy_coef=policy_coef,
-                                    sft_coef=sft_coef, token_sum=token_sum, token_logprobs=drawn["token_logprobs"])
+        self._check_policy_shapes(B, S if K is None else S * K, Ts, labels, output_attention, with_gold)
+        if K is None:
+            drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
+                                      temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
+            rewards = None if reward_fn is None else reward_fn(drawn)
+            rollout = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=rewards, baseline=baseline, policy_coef=policy_coef,
+                                        sft_coef=sft_coef, token_sum=token_sum, token_logprobs=drawn["token_logprobs"])
+        else:
+            drawn = self.sample_slates(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, slate_size=K + 1,
+                                       num_slates=S, temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
+            rewards = None if reward_fn is None else reward_fn(drawn)
+            rollout = self.policy_slate_batch(drawn, labels, output_attention, K, S, rewards=rewards, estimator=slate_estimator, policy_coef=policy_coef,
+                                              sft_coef=sft_coef, token_sum=token_sum, with_old_logprobs=True)
         rollout["sampled"] = drawn
         if old_logprobs == "forward":
             dev = self._be.device
@@ -2167,7 +2322,10 @@ class P5T5Native(nn.Module):
         slate is never split) or slate ranges split by hand with `slate_base` do not change a bit.  Tree-shaped tries only.
         Returns {"sequences" int64 [B * S * K, T], "sequences_logprob" fp32 [B * S * K] (log p(item)), "perturbed" fp32 [B, S, K]
         (descending, <= 0), "token_logprobs" fp32 [B * S * K, T - 1], "item_index" int64 [B, S, K]}.  A user with fewer than K allowed items
-        gets trailing slots with the all-pad sequence, log-probability -inf, perturbed -inf and item_index -1."""
+        gets trailing slots with the all-pad sequence, log-probability -inf, perturbed -inf and item_index -1.
+        The search starts its root at G = 0, so `perturbed` are the values of a draw whose MAXIMUM is conditioned to be 0 (the first slot
+        holds 0): the slate's distribution does not depend on that, a threshold taken from the values does.  "noise_key" = (seed, stream ids
+        int32 [B] on the device, slate_base) is what `policy_slate_batch` un-conditions its threshold with."""
         if trie is None:
             raise ValueError("sample_slates() needs the item trie (Trie / CompiledTrie)")
         trie = self._compiled_trie(trie)
@@ -2246,7 +2404,7 @@ class P5T5Native(nn.Module):
         R = B * S * K
         item_index = self._sampled_item_index(trie, seq.reshape(R, T), ln.reshape(R)).view(B, S, K)
         return {"sequences": seq.reshape(R, T).to(torch.int64), "sequences_logprob": lp.reshape(R), "perturbed": pert,
-                "token_logprobs": tok_lp.reshape(R, T)[:, 1:].contiguous(), "item_index": item_index}
+                "token_logprobs": tok_lp.reshape(R, T)[:, 1:].contiguous(), "item_index": item_index, "noise_key": (seed, streams_t, slate_base)}
 
     def _in_user_chunks(self, fn, args):
         """fn(*args) for a search wider than the narrow step, over consecutive chunks of users of at most `wide_max_rows` decode rows each,

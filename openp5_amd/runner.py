@@ -110,6 +110,12 @@ def parse_runner_args(parser):
                         "exactly 1 without dropout)")
     parser.add_argument("--policy_token_sum", type=int, default=0, choices=[0, 1], help="1 = a draw's term is the SUM of its tokens' NLL (REINFORCE "
                         "proper) instead of their mean")
+    parser.add_argument("--policy_slate_size", type=int, default=0, help="K > 0 = the on-policy step draws SLATES of K distinct items per user "
+                        "(stochastic beam search; --train_policy_samples then counts slates) and weights them with the importance-weighted "
+                        "without-replacement estimator (P5T5Native.policy_slate_batch).  Not with --item_loss_top_k / --item_loss_top_p or a "
+                        "non-default --policy_baseline.  0 = off, nothing changes.")
+    parser.add_argument("--policy_slate_estimator", type=str, default="normalized", choices=["normalized", "unbiased"], help="normalized = weights "
+                        "and baseline normalised by the slate's own weight sum (biased, consistent, lower variance; K >= 2); unbiased = p / q alone")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -166,7 +172,8 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
     reference's `item_logits` of the batch when kl_coef != 0.
 
     `policy` (None = off): keyword arguments of `P5T5Native.policy_step` on top of `item_loss` -- {"num_samples", "baseline", "policy_coef",
-    "sft_coef", "token_sum", "seed"}: the step samples, rewards, weights and trains in one call."""
+    "sft_coef", "token_sum", "seed"} and, for slates, {"slate_size", "slate_estimator"}: the step samples, rewards, weights and trains in
+    one call."""
     kw = dict(item_loss or {})
     input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
     fused = getattr(model, "loss_and_backward", None)
@@ -460,9 +467,14 @@ class DistributedRunner:
                     # the one host read of the statistics -- and of this batch's loss: this runner logs no per-batch loss elsewhere, so with the
                     # flag on rank 0 synchronises with the device once per --logging_step batches; with the flag off nothing is read
                     if self.rank == 0 and n_batches % max(1, int(self.args.logging_step)) == 0:
-                        st = [float(x) for x in self.model.last_policy_stats[:6].cpu()]
-                        logging.info(f"policy step {self.optimizer.t} batch {n_batches}: loss {float(loss):.6f} "
-                                     + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.POLICY_STATS, st)))
+                        if "slate_size" in pol:
+                            st = [float(x) for x in self.model.last_policy_stats.cpu()]
+                            logging.info(f"policy slate step {self.optimizer.t} batch {n_batches}: loss {float(loss):.6f} "
+                                         + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.SLATE_POLICY_STATS, st)))
+                        else:
+                            st = [float(x) for x in self.model.last_policy_stats[:6].cpu()]
+                            logging.info(f"policy step {self.optimizer.t} batch {n_batches}: loss {float(loss):.6f} "
+                                         + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.POLICY_STATS, st)))
                         if clip_stats is not None:
                             cs = [float(x) for x in clip_stats.mean(0).cpu()]
                             logging.info(f"policy clip step {self.optimizer.t} batch {n_batches} (mean of {clip_stats.shape[0]} updates): "
@@ -531,6 +543,16 @@ class DistributedRunner:
             raise ValueError(f"--policy_epochs {E} cannot be combined with --gradient_accumulation_steps > 1")
         if eps > 0.0 and S == 0:
             raise ValueError("--policy_clip_eps requires --train_policy_samples > 0")
+        K = int(getattr(self.args, "policy_slate_size", 0))
+        estimator = str(getattr(self.args, "policy_slate_estimator", "normalized"))
+        if K < 0:
+            raise ValueError(f"--policy_slate_size {K}: the number of items per slate (0 = off)")
+        if K > 0 and S <= 0:
+            raise ValueError("--policy_slate_size requires --train_policy_samples > 0 (the number of slates per user) and --train_item_loss 1")
+        if K > 0 and estimator not in ("normalized", "unbiased"):
+            raise ValueError(f"--policy_slate_estimator {estimator}: normalized or unbiased")
+        if K == 1 and estimator == "normalized":
+            raise ValueError("--policy_slate_estimator normalized needs --policy_slate_size >= 2 (use unbiased for slates of one item)")
         if S == 0:
             return None
         if eps > 0.0:
@@ -551,12 +573,24 @@ class DistributedRunner:
         baseline = str(getattr(self.args, "policy_baseline", "loo"))
         if baseline not in ("loo", "mean", "grpo", "none"):
             raise ValueError(f"--policy_baseline {baseline}: loo, mean, grpo or none")
-        if baseline == "loo" and S < 2:
+        if K > 0:
+            if baseline != "loo":
+                raise ValueError(f"--policy_baseline {baseline} belongs to the plain draws: with --policy_slate_size the baseline is "
+                                 "--policy_slate_estimator's (normalized = the slate's own weighted mean, unbiased = none)")
+            if int(getattr(self.args, "item_loss_top_k", 0) or 0) > 0 or float(getattr(self.args, "item_loss_top_p", 1.0) or 1.0) < 1.0:
+                raise ValueError("--policy_slate_size cannot be combined with --item_loss_top_k / --item_loss_top_p: the slate sampler has no "
+                                 "truncation (use the plain draws, --policy_slate_size 0)")
+            if not hasattr(self.model, "policy_slate_batch"):
+                raise ValueError("--policy_slate_size needs the native model (P5T5Native)")
+        elif baseline == "loo" and S < 2:
             raise ValueError("--policy_baseline loo needs --train_policy_samples >= 2")
         pc, sc = float(getattr(self.args, "policy_coef", 1.0)), float(getattr(self.args, "policy_sft_coef", 1.0))
         if not (math.isfinite(pc) and math.isfinite(sc)):
             raise ValueError(f"--policy_coef {pc} / --policy_sft_coef {sc}: finite values")
-        return {"num_samples": S, "baseline": baseline, "policy_coef": pc, "sft_coef": sc, "token_sum": bool(int(getattr(self.args, "policy_token_sum", 0)))}
+        pol = {"num_samples": S, "baseline": baseline, "policy_coef": pc, "sft_coef": sc, "token_sum": bool(int(getattr(self.args, "policy_token_sum", 0)))}
+        if K > 0:
+            pol.update(slate_size=K, slate_estimator=estimator)
+        return pol
 
     def _item_loss_kw(self):
         """--train_item_loss 1: the keyword arguments of the trie-normalised item loss -- ONE union trie over the items of all training
