@@ -211,6 +211,26 @@ int p5_train_set_item_regularizers(P5Engine* e, const float* ref_logits, int ld_
  * may differ between the two policies); p5_forward / p5_forward_targets called while it is armed refuse and disarm it. */
 int p5_train_set_clip_objective(P5Engine* e, const float* old_logprobs, const int* target_mode, float eps_low, float eps_high, int ratio_mode,
                                 float* row_seed, float* user_partials, float* clip_stats);
+/* A listwise preference objective (p5_pref.h) over the G targets of every user.  One-shot, like p5_train_set_clip_objective (call it behind
+ * p5_train_set_item_loss): arms the NEXT p5_forward_loss_targets and the backward behind it; two launches take the place of the masked-mean
+ * loss kernels.  Per target (b, g) with m = output_attention != 0: cnt = sum_t m, s = sum_t m nll, r = sum_t m ref_logprobs (0 when NULL =
+ * reference-free), Delta = (-s - r) / c' (c' = max(cnt, 1) with length_normalize, else 1), h = beta Delta.  The list of user b: its targets
+ * with pref_mask != 0 (int32 DEVICE [B * G], NULL = all) and cnt > 0, in index order, the preferred one first; every other target is skipped
+ * (no contribution, exact-zero seeds, ref_logprobs never read -- it is read only where m, and only at targets with pref_mask != 0).
+ *   kind 0 (Plackett-Luce), depth D (0 = full): for a list of n >= 2, D_b = min(D or n - 1, n - 1) and
+ *        l_b = sum_{k < D_b} (logsumexp_{j >= k} h_j - h_k): n = 2 is DPO, D = 1 softmax-DPO, full depth the PL likelihood of the order
+ *   kind 1 (IPO): l_b = mean_{j = 1 .. n - 1} ((Delta_0 - Delta_j) - 1 / (2 beta))^2        (depth is ignored)
+ * A list of fewer than two has l_b = 0; a list of at least one adds sft_coef * (sum_t m nll / max(cnt, 1)) of its first target.
+ * loss = sum_b (l_b + sft_b) / B.  row_seed: DEVICE fp32 [B G T], caller-owned until the backward has run; user_partials DEVICE fp32 [B * 16]
+ * scratch; pref_stats DEVICE fp32 [8], no host sync: users with a pair (n >= 2), share of pairs (first, j) with h_first > h_j, mean h_first
+ * over those users, mean h_j over the pairs, mean margin h_first - h_j over the pairs, the preference part of the loss, the SFT part, mean n
+ * over users with n >= 1; no pair: 0 .. 4 are 0, no list: 7 is 0.  With a list of one and sft_coef = c the seeds are the bits of the plain
+ * step with target_weights (c G, 0, ...) when G is a power of two.  No atomics: equal inputs give equal bits.
+ * Errors: beta not finite or <= 0, an unknown kind, depth < 0, sft_coef not finite, NULL required pointers, the clip objective armed as well,
+ * item regularizers armed (not built), the truncated item loss armed (the kept set may differ between the two policies); the armed forward
+ * refuses target_weights != NULL and G > 512; p5_forward / p5_forward_targets called while it is armed refuse and disarm it. */
+int p5_train_set_pref_objective(P5Engine* e, const float* ref_logprobs, const int* pref_mask, int kind, float beta, int depth, int length_normalize,
+                                float sft_coef, float* row_seed, float* user_partials, float* pref_stats);
 /* One-shot, in front of p5_backward / p5_backward_stage (stage 0) / p5_backward_staged called WITH dnll: DEVICE fp32 [rows] gradients of the
  * rows' H and KL of the last forward (NULL = zeros).  Error: the last forward ran without p5_train_set_item_regularizers. */
 int p5_backward_set_item_grads(P5Engine* e, const float* d_entropy, const float* d_kl);
@@ -771,6 +791,12 @@ int p5_op_clip_objective(float* loss, float* terms, float* row_seed, float* user
                          const float* old_logprobs, const int64_t* out_attn, const int64_t* labels, const float* tw, const int* target_mode,
                          const float* entropy_rows, const float* kl_rows, float entropy_coef, float kl_coef, float eps_low, float eps_high,
                          int ratio_mode, int B, int G, int T, void* stream);
+/* The two kernels of p5_train_set_pref_objective behind a given per-token NLL, no engine: nll fp32 [B*G*T], ref_logprobs fp32 [B*G*T] or NULL,
+ * out_attn / labels int64 [B*G*T], pref_mask int32 [B*G] or NULL; row_seed fp32 [B*G*T], user_partials fp32 [B*16], pref_stats fp32 [8].
+ * 1 <= G <= 512. */
+int p5_op_pref_objective(float* loss, float* row_seed, float* user_partials, float* pref_stats, const float* nll, const float* ref_logprobs,
+                         const int64_t* out_attn, const int64_t* labels, const int* pref_mask, int kind, float beta, int depth, int length_normalize,
+                         float sft_coef, int B, int G, int T, void* stream);
 /* decode-step projection over a few hundred rows (p5_decode2.h): C = A W^T, W = T [N, ldw].  amode 0: A = T [M, lda];
  * amode 1: A = fp32 residual stream [M, K], normalised with T5LayerNorm weight `ln` by the kernel itself.
  * (K <= 1024 then).  epi: 0 store T (alpha), 1 relu store T, 2 fp32 atomic accumulate (split-K), 3 store fp32 (alpha), 4 fp32 += by one writer */

@@ -55,6 +55,7 @@ PROTOTYPES = {
     "p5_train_set_item_head": (i32, [vp, vp, i32, vp, vp, C.c_size_t]),
     "p5_train_set_item_regularizers": (i32, [vp, vp, i32, vp, f32, f32, vp]),
     "p5_backward_set_item_grads": (i32, [vp, vp, vp]),
+    "p5_train_set_pref_objective": (i32, [vp, vp, vp, i32, f32, i32, i32, f32, vp, vp, vp]),
     "p5_train_set_clip_objective": (i32, [vp, vp, vp, f32, f32, i32, vp, vp, vp]),
     "p5_train_last_item_logits": (i32, [vp, vp, vp, vp, vp]),
     "p5_backward_num_stages": (i32, [vp]),
@@ -147,6 +148,7 @@ PROTOTYPES = {
     "p5_policy_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "p5_policy_batch_clip": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "p5_policy_slate_batch": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp]),
+    "p5_op_pref_objective": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, f32, i32, i32, i32, vp]),
     "p5_op_clip_objective": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, i32, i32, vp]),
     "p5_op_dec_cross_attn": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "p5_op_skinny_gemm": (i32, [i32, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, vp]),

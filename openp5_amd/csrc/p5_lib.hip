@@ -35,6 +35,7 @@
 #include "p5_policy.h"
 #include "p5_slate_policy.h"
 #include "p5_clip.h"
+#include "p5_pref.h"
 #include "../../include/p5hip.h"
 
 thread_local std::string g_p5_err;
@@ -214,6 +215,13 @@ struct P5Engine {
     float *seed = nullptr, *partials = nullptr, *stats = nullptr;
   };
   ClipObj clip_next, clip;
+  // preference objective (p5_pref.h): pref_next = p5_train_set_pref_objective, armed for the NEXT p5_forward_loss_targets (one-shot); pref = what
+  // the last forward ran under: the backward behind it (dnll == nullptr) takes its per-row seeds from pref.seed
+  struct PrefObj {
+    bool on = false; const float* ref_lp = nullptr; const int* mask = nullptr; int kind = 0, depth = 0, length_normalize = 0;
+    float beta = 0.f, sft_coef = 0.f; float *seed = nullptr, *partials = nullptr, *stats = nullptr;
+  };
+  PrefObj pref_next, pref;
   const float *bw_dH = nullptr, *bw_dKL = nullptr;      // p5_backward_set_item_grads: per-row gradients of H / KL for the NEXT backward (one-shot)
   void* Sf = nullptr;              // folded bf16 weight copy W diag(ln) for q/k/v, wi, cross-attention q (same arena offsets; behind St)
   float *dres_a = nullptr, *dres_b = nullptr, *d_enc = nullptr, *Dvec = nullptr, *dres_cur = nullptr, *rel_partial = nullptr;
@@ -1459,6 +1467,7 @@ static int backward_stage_impl(P5Engine* e, const float* dnll, int stage, hipStr
       dnll = e->clip.seed;
       if (e->il.on && e->il.reg) { e->bw_dH = e->clip.seed + Md; e->bw_dKL = e->clip.seed + 2 * (size_t)Md; }
     }
+    if (!dnll && e->pref.on) dnll = e->pref.seed;      // the preference objective's kernel has written this backward's seeds
     const float alpha = 1.0f / sqrtf((float)d);
     // the head's logits, their gradient and their leading dimension: the vocabulary's, or -- item loss on the restricted head
     // (p5_item_head.h) -- the compact arrays of the caller's workspace
@@ -3755,6 +3764,26 @@ static int clip_params_ok(float eps_low, float eps_high, int ratio_mode) {
   P5_REQUIRE(ratio_mode == P5_RATIO_TOKEN || ratio_mode == P5_RATIO_SEQUENCE, "clip objective: unknown ratio mode (0 token, 1 sequence)");
   return 0;
 }
+// both kernels of p5_pref.h behind a per-token NLL: the seeds and the users' partials, then loss / stats
+static int launch_pref(hipStream_t s, float* loss, float* seed, float* partials, float* stats, const float* nll, const float* ref_lp,
+                       const int64_t* out_attn, const int64_t* labels, const int* pref_mask, int kind, float beta, int depth, int length_normalize,
+                       float sft_coef, int B, int G, int T) {
+  P5PrefArgs a;
+  a.nll = nll; a.ref_lp = ref_lp; a.out_attn = out_attn; a.labels = labels; a.pref_mask = pref_mask; a.seed = seed; a.partials = partials;
+  a.G = G; a.T = T; a.kind = kind; a.depth = depth; a.length_normalize = length_normalize ? 1 : 0;
+  a.beta = beta; a.sft_coef = sft_coef; a.inv_b = 1.0f / (float)B;
+  P5_LAUNCH(p5_pref_objective_kernel, dim3(B), dim3(256), 0, s, a);
+  P5_TRY(P5_KCHECK());
+  P5_LAUNCH(p5_pref_finish_kernel, dim3(1), dim3(256), 0, s, loss, stats, (const float*)partials, B);
+  return P5_KCHECK();
+}
+static int pref_params_ok(int kind, float beta, int depth, float sft_coef) {
+  P5_REQUIRE(beta - beta == 0.f && beta > 0.f, "preference objective: beta must be finite and > 0");
+  P5_REQUIRE(kind == P5_PREF_PL || kind == P5_PREF_IPO, "preference objective: unknown kind (0 Plackett-Luce, 1 IPO)");
+  P5_REQUIRE(depth >= 0, "preference objective: depth >= 0 (0 = full depth)");
+  P5_REQUIRE(sft_coef - sft_coef == 0.f, "preference objective: sft_coef must be finite");
+  return 0;
+}
 static int forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
                            int B, int L, int T, int G, int training, float* nll_out, void* ws, int64_t ws_bytes, void* stream, bool with_loss) {
   e->clip = e->clip_next;        // one-shot, whatever this call returns
@@ -3762,6 +3791,16 @@ static int forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t*
   if (e->clip.on && !with_loss) {
     e->clip.on = false;
     P5_REQUIRE(false, "p5_forward / p5_forward_targets: a clip objective is armed (p5_train_set_clip_objective): it needs p5_forward_loss / p5_forward_loss_targets");
+  }
+  e->pref = e->pref_next;        // one-shot, whatever this call returns
+  e->pref_next.on = false;
+  if (e->pref.on && !with_loss) {
+    e->pref.on = false;
+    P5_REQUIRE(false, "p5_forward / p5_forward_targets: a preference objective is armed (p5_train_set_pref_objective): it needs p5_forward_loss_targets");
+  }
+  if (e->pref.on && e->clip.on) {
+    e->pref.on = e->clip.on = false;
+    P5_REQUIRE(false, "preference objective: the clip objective is armed as well (p5_train_set_clip_objective): one objective per forward");
   }
   P5_REQUIRE(e->P, "engine not bound");
   P5_REQUIRE(B >= 1 && L >= 1 && L <= 512 && T >= 1 && T <= 512, "shape limits: 1 <= L,T <= 512");
@@ -3789,6 +3828,12 @@ static int forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t*
     P5_REQUIRE(nll_out, "clip objective: nll_out");
     P5_REQUIRE(!(e->il.on && e->il.trunc), "clip objective: not built for the truncated item loss (top_k / top_p): the kept set may differ between the two policies");
   }
+  if (e->pref.on) {
+    P5_REQUIRE(nll_out, "preference objective: nll_out");
+    P5_REQUIRE(G <= P5_PREF_MAX_G, "preference objective: G <= 512");
+    P5_REQUIRE(!(e->il.on && e->il.trunc), "preference objective: not built for the truncated item loss (top_k / top_p): the kept set may differ between the two policies");
+    P5_REQUIRE(!(e->il.on && e->il.reg), "preference objective: not built beside the item regularizers (p5_train_set_item_regularizers)");
+  }
   return e->c.dtype == 1 ? forward_impl<bf16>(e, nll_out, (hipStream_t)stream) : forward_impl<float>(e, nll_out, (hipStream_t)stream);
 }
 int p5_forward_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
@@ -3802,11 +3847,15 @@ int p5_forward(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_
 int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t* whole_word_ids, const int64_t* attention_mask, const int64_t* labels,
                             const int64_t* output_attention, int B, int L, int T, int G, const float* target_weights, int training, float* nll_out,
                             float* loss_out, void* ws, int64_t ws_bytes, void* stream) {
-  if (!(output_attention && loss_out)) e->clip_next.on = false;     // (one-shot, refused calls included)
+  if (!(output_attention && loss_out)) e->clip_next.on = e->pref_next.on = false;     // (one-shot, refused calls included)
   P5_REQUIRE(output_attention && loss_out, "null argument");
+  if (e->pref_next.on && target_weights) {
+    e->pref_next.on = e->clip_next.on = false;
+    P5_REQUIRE(false, "preference objective: target_weights must be NULL (the objective forms every target's weight itself)");
+  }
   {
     const int rc = forward_targets(e, input_ids, whole_word_ids, attention_mask, labels, B, L, T, G, training, nll_out, ws, ws_bytes, stream, true);
-    if (rc) { e->clip.on = false; return rc; }
+    if (rc) { e->clip.on = e->pref.on = false; return rc; }
   }
   e->out_attn = output_attention;
   e->tgt_w = target_weights;
@@ -3819,6 +3868,9 @@ int p5_forward_loss_targets(P5Engine* e, const int64_t* input_ids, const int64_t
                        e->clip.old_lp, output_attention, e->labels, target_weights, e->clip.mode, rt, reg && e->il.ref ? rt + e->Md : nullptr,
                        reg ? e->il.ent_coef : 0.f, reg ? e->il.kl_coef : 0.f, e->clip.eps_low, e->clip.eps_high, e->clip.ratio_mode, B, G, T);
   }
+  if (e->pref.on)      // the preference objective in the loss kernels' place: it writes the seeds of the backward behind this call
+    return launch_pref((hipStream_t)stream, loss_out, e->pref.seed, e->pref.partials, e->pref.stats, (const float*)nll_out, e->pref.ref_lp, output_attention,
+                       e->labels, e->pref.mask, e->pref.kind, e->pref.beta, e->pref.depth, e->pref.length_normalize, e->pref.sft_coef, B, G, T);
   if (e->il.on && e->il.reg) {
     const float* rt = e->il.row_terms;
     P5_LAUNCH(p5_trie_reg_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, e->il.terms_out, (const float*)nll_out, rt,
@@ -3916,6 +3968,21 @@ int p5_train_set_clip_objective(P5Engine* e, const float* old_logprobs, const in
   e->clip_next.old_lp = old_logprobs; e->clip_next.mode = target_mode; e->clip_next.eps_low = eps_low; e->clip_next.eps_high = eps_high;
   e->clip_next.ratio_mode = ratio_mode; e->clip_next.seed = row_seed; e->clip_next.partials = user_partials; e->clip_next.stats = clip_stats;
   e->clip_next.on = true;
+  return 0;
+}
+int p5_train_set_pref_objective(P5Engine* e, const float* ref_logprobs, const int* pref_mask, int kind, float beta, int depth, int length_normalize,
+                                float sft_coef, float* row_seed, float* user_partials, float* pref_stats) {
+  e->pref_next.on = false;
+  P5_TRY(pref_params_ok(kind, beta, depth, sft_coef));
+  P5_REQUIRE(row_seed && user_partials && pref_stats, "preference objective: null pointer (row_seed, user_partials and pref_stats are required)");
+  P5_REQUIRE(!e->clip_next.on, "preference objective: the clip objective is armed as well (p5_train_set_clip_objective): one objective per forward");
+  P5_REQUIRE(!(e->il_next.on && e->il_next.reg), "preference objective: not built beside the item regularizers (p5_train_set_item_regularizers)");
+  P5_REQUIRE(!(e->il_next.on && e->il_next.trunc),
+             "preference objective: not built for the truncated item loss (top_k / top_p): the kept set may differ between the two policies");
+  P5Engine::PrefObj& p = e->pref_next;
+  p.ref_lp = ref_logprobs; p.mask = pref_mask; p.kind = kind; p.beta = beta; p.depth = depth; p.length_normalize = length_normalize ? 1 : 0;
+  p.sft_coef = sft_coef; p.seed = row_seed; p.partials = user_partials; p.stats = pref_stats;
+  p.on = true;
   return 0;
 }
 int p5_backward_set_item_grads(P5Engine* e, const float* d_entropy, const float* d_kl) {
@@ -4992,6 +5059,17 @@ int p5_op_masked_mean_g(int merged, float* loss, float* g_out, const float* nll,
   P5_TRY(P5_KCHECK());
   P5_LAUNCH(p5_ce_gscale_kernel, dim3((B * T + 255) / 256), dim3(256), 0, s, g_out, labels, (const float*)nullptr, out_attn, T, gscale, B * T, tw);
   return P5_KCHECK();
+}
+// the preference objective (p5_pref.h) behind a given per-token NLL: both launches, no engine
+int p5_op_pref_objective(float* loss, float* row_seed, float* user_partials, float* pref_stats, const float* nll, const float* ref_logprobs,
+                         const int64_t* out_attn, const int64_t* labels, const int* pref_mask, int kind, float beta, int depth, int length_normalize,
+                         float sft_coef, int B, int G, int T, void* stream) {
+  P5_TRY(pref_params_ok(kind, beta, depth, sft_coef));
+  P5_REQUIRE(loss && row_seed && user_partials && pref_stats && nll && out_attn && labels, "preference objective: null pointer argument");
+  P5_REQUIRE(B >= 1 && G >= 1 && G <= P5_PREF_MAX_G && T >= 1 && (int64_t)B * G * T <= ((int64_t)1 << 30),
+             "preference objective: shapes B, G, T >= 1, G <= 512, B * G * T <= 2^30");
+  return launch_pref((hipStream_t)stream, loss, row_seed, user_partials, pref_stats, nll, ref_logprobs, out_attn, labels, pref_mask, kind, beta, depth,
+                     length_normalize, sft_coef, B, G, T);
 }
 // the clipped-ratio objective (p5_clip.h) behind a given per-token NLL: both launches, no engine
 int p5_op_clip_objective(float* loss, float* terms, float* row_seed, float* user_partials, float* clip_stats, const float* nll, const float* old_logprobs,

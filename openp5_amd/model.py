@@ -805,7 +805,8 @@ class P5T5Native(nn.Module):
 
     def loss_and_backward(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie=None, temperature=1.0, excluded_items=None,
                           top_k=0, top_p=1.0, item_head=None, target_weights=None, entropy_coef=0.0, kl_coef=0.0, ref_logits=None, old_logprobs=None,
-                          target_mode=None, clip_eps=None, ratio="token"):
+                          target_mode=None, clip_eps=None, ratio="token", preference=None, pref_beta=0.1, ref_logprobs=None, pref_mask=None,
+                          pref_depth=None, pref_length_normalize=False, pref_sft_coef=0.0):
         """Fused form of the reference loop body DistributedRunner.py:63-80: forward, masked-mean loss
         (`(nll.view(B,T) * m).sum(1) / m.sum(1).clamp(min=1)).mean()`) and backward, all inside the engine -- the loss is
         reduced behind the cross-entropy kernel and the backward is seeded from the label mask, so no torch autograd graph and
@@ -835,9 +836,28 @@ class P5T5Native(nn.Module):
         carries the bits of the call without the objective.  Rows are taken as they come: the item loss gives NLL 0 to a row it did not score
         (`last_item_loss_state`), so clipped targets should be fully scored -- `policy_batch`'s draws are.  Not under top_k / top_p (the kept set
         may differ between the two policies).  `last_clip_stats` is the device tensor fp32 [8] named by `CLIP_STATS`, no host sync (None behind
-        a call without the objective).  Without these keywords the call issues the engine calls it always did."""
+        a call without the objective).  Without these keywords the call issues the engine calls it always did.
+        `preference` ("pl" | "ipo"; None = off) and `pref_*`, `ref_logprobs`: a listwise preference objective over the G targets of every user
+        (csrc/p5_pref.h; needs `labels` [B, G, T], no `target_weights`, not beside the clipped objective, the regularisers or top_k / top_p).
+        Per target, with m = output_attention != 0: Delta = (log p(target) - log p_ref(target)) / c', log p = -sum_t m nll, log p_ref =
+        sum_t m ref_logprobs (`ref_logprobs` fp32 shaped like `labels`, e.g. `ref.sequence_logprobs(...)` of a `frozen_copy()`; None =
+        reference-free), c' = max(sum_t m, 1) under `pref_length_normalize`, else 1; h = pref_beta * Delta.  A user's LIST is its targets with
+        `pref_mask` [B, G] != 0 (None = all) and at least one attended token, in index order, the preferred one first; anything else is
+        skipped: no contribution, exact-zero gradients, its `ref_logprobs` never read.  "pl" (Plackett-Luce) with `pref_depth` D (None = full):
+        sum_{k < min(D, n - 1)} (logsumexp_{j >= k} h_j - h_k) -- a list of two is DPO, D = 1 softmax-DPO (one positive against the listed
+        negatives), full depth the likelihood of the whole order; "ipo": mean_{j >= 1} ((Delta_0 - Delta_j) - 1 / (2 pref_beta))^2.  A list of
+        fewer than two gives 0; `pref_sft_coef` times the first listed target's masked-mean NLL is added.  The loss is the mean over the B
+        users.  `last_pref_stats` is the device tensor fp32 [8] named by `PREF_STATS`, no host sync (None behind a call without the objective)."""
         item_head = self._item_head_mode(item_head, trie)
         clip = self._clip_args(old_logprobs, target_mode, clip_eps, ratio, top_k, top_p)
+        pref = self._pref_args(preference, pref_beta, pref_depth, pref_sft_coef, ref_logprobs, pref_mask, top_k, top_p)
+        if pref is not None:
+            if clip is not None:
+                raise ValueError("preference and the clipped objective (old_logprobs / clip_eps) exclude each other: one objective per call")
+            if target_weights is not None:
+                raise ValueError("preference: target_weights must be None (the objective forms every target's weight itself; list targets with pref_mask)")
+            if entropy_coef != 0.0 or kl_coef != 0.0 or ref_logits is not None:
+                raise ValueError("preference is not built beside the item regularisers (entropy_coef / kl_coef / ref_logits)")
         dev = self._be.device
         input_ids = self._i64(input_ids, dev)
         B, L = input_ids.shape
@@ -855,6 +875,15 @@ class P5T5Native(nn.Module):
                 raise ValueError(f"old_logprobs {tuple(getattr(old_logprobs, 'shape', ()))} must be a tensor shaped like labels {tuple(labels.shape)}")
             if target_mode is not None and (not torch.is_tensor(target_mode) or tuple(target_mode.shape) != tuple(labels.shape[:-1])):
                 raise ValueError(f"target_mode {tuple(getattr(target_mode, 'shape', ()))} must be a tensor of shape {tuple(labels.shape[:-1])} (one per target)")
+        if pref is not None:
+            if G is None:
+                raise ValueError(f"preference needs labels [B, G, T] (the G targets of every user); labels {tuple(labels.shape)} has one")
+            if G > self.PREF_MAX_TARGETS:
+                raise ValueError(f"preference: G = {G} targets per user exceed the limit G <= {self.PREF_MAX_TARGETS}")
+            if ref_logprobs is not None and (not torch.is_tensor(ref_logprobs) or tuple(ref_logprobs.shape) != tuple(labels.shape)):
+                raise ValueError(f"ref_logprobs {tuple(getattr(ref_logprobs, 'shape', ()))} must be a tensor shaped like labels {tuple(labels.shape)}")
+            if pref_mask is not None and (not torch.is_tensor(pref_mask) or tuple(pref_mask.shape) != (B, G)):
+                raise ValueError(f"pref_mask {tuple(getattr(pref_mask, 'shape', ()))} must be a tensor of shape [B, G] = {(B, G)}")
         item_loss = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, B, top_k, top_p, item_head)
         if entropy_coef != 0.0 or kl_coef != 0.0 or ref_logits is not None:
             item_loss = self._item_regularizers(item_loss, Bd * T, ref_logits, entropy_coef, kl_coef, fused=True)
@@ -884,6 +913,20 @@ class P5T5Native(nn.Module):
             self._be.check(self._lib.p5_train_set_clip_objective(self._engine, _ptr(old), _ptr(mode), clip[0], clip[1], clip[2], _ptr(seed), _ptr(partials),
                                                                  _ptr(stats)), "p5_train_set_clip_objective")
             self.last_clip_stats = stats
+        self.last_pref_stats = None
+        if pref is not None:
+            # the seeds, the users' partials and the statistics: the caller's, until the backward has run
+            ref_lp = None if ref_logprobs is None else ref_logprobs.detach().to(device=dev, dtype=torch.float32).contiguous()
+            pmask = None
+            if pref_mask is not None:          # (int32 as it is: the kernel tests != 0)
+                pmask = (pref_mask if pref_mask.dtype == torch.int32 else (pref_mask != 0)).to(device=dev, dtype=torch.int32).contiguous()
+            buf = torch.empty(Bd * T + 16 * B + 8, dtype=torch.float32, device=dev)
+            seed, partials, stats = torch.split(buf, [Bd * T, 16 * B, 8])
+            self._saved_inputs += (ref_lp, pmask, buf)
+            self._be.check(self._lib.p5_train_set_pref_objective(self._engine, _ptr(ref_lp), _ptr(pmask), pref[0], pref[1], pref[2],
+                                                                 1 if pref_length_normalize else 0, pref[3], _ptr(seed), _ptr(partials), _ptr(stats)),
+                           "p5_train_set_pref_objective")
+            self.last_pref_stats = stats
         if G is None:
             self._be.check(self._lib.p5_forward_loss(self._engine, _ptr(input_ids), _ptr(whole_word_ids), _ptr(attention_mask), _ptr(labels),
                                                      _ptr(output_attention), B, L, T, training, _ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * B * T),
@@ -933,6 +976,113 @@ class P5T5Native(nn.Module):
             raise ValueError("the clipped objective (clip_eps) is not built for the truncated item loss (top_k / top_p): the kept set may differ "
                              "between the two policies")
         return lo, hi, self.CLIP_RATIOS[ratio]
+
+    PREF_KINDS = {"pl": 0, "ipo": 1}
+    PREF_STATS = ("users_with_pair", "pairs_won", "h_first_mean", "h_others_mean", "margin_mean", "preference_loss", "sft_loss", "list_length_mean")
+    PREF_MAX_TARGETS = 512
+    last_pref_stats = None        # of the last loss_and_backward with a preference objective: fp32 [8] on the device (PREF_STATS); else None
+
+    def _pref_args(self, preference, pref_beta, pref_depth, pref_sft_coef, ref_logprobs=None, pref_mask=None, top_k=0, top_p=1.0):
+        """the checked scalars of a preference objective, (kind code, beta, depth (0 = full), sft_coef), or None when the call does not ask for it"""
+        if preference is None:
+            if ref_logprobs is not None or pref_mask is not None:
+                raise ValueError("ref_logprobs / pref_mask belong to a preference objective: they need preference=\"pl\" | \"ipo\"")
+            return None
+        if preference not in self.PREF_KINDS:
+            raise ValueError(f"preference={preference!r}: one of {sorted(self.PREF_KINDS)}, or None")
+        try:
+            beta, sc = float(pref_beta), float(pref_sft_coef)
+        except (TypeError, ValueError):
+            raise ValueError(f"pref_beta={pref_beta!r}, pref_sft_coef={pref_sft_coef!r}: numbers") from None
+        if not (math.isfinite(beta) and beta > 0.0):
+            raise ValueError(f"pref_beta={pref_beta!r}: a finite value > 0")
+        if not math.isfinite(sc):
+            raise ValueError(f"pref_sft_coef={pref_sft_coef!r}: a finite value")
+        if pref_depth is None:
+            depth = 0
+        else:
+            if isinstance(pref_depth, bool) or not isinstance(pref_depth, int) or pref_depth < 1:
+                raise ValueError(f"pref_depth={pref_depth!r}: an integer >= 1, or None for the full depth")
+            depth = int(pref_depth)
+        tk, tp = self._truncation(top_k, top_p)
+        if tk > 0 or tp < 1.0:
+            raise ValueError("preference is not built for the truncated item loss (top_k / top_p): the kept set may differ between the two policies")
+        return self.PREF_KINDS[preference], beta, depth, sc
+
+    @torch.no_grad()
+    def sequence_logprobs(self, input_ids, whole_word_ids, attention_mask, labels, trie=None, temperature=1.0, excluded_items=None, item_head=None):
+        """log p(label) of every position, -nll shaped like `labels` ([B, T] or [B, G, T]): the full-vocabulary log-softmax, or with `trie` the
+        trie-normalised one of the item loss (`temperature`, `excluded_items`, `item_head`: those of `forward`).  No gradient is recorded,
+        dropout is never applied whatever `self.training` says, `.grad` and the dropout step stay as they are.  On a `frozen_copy()` it is
+        the `ref_logprobs` of `loss_and_backward(preference=...)`.  Positions the loss does not score (label -100, off the trie, behind the
+        end) give 0.  Not between a forward of THIS model and its backward: the engine holds one forward at a time."""
+        item_head = self._item_head_mode(item_head, trie)
+        dev = self._be.device
+        input_ids = self._i64(input_ids, dev)
+        whole_word_ids = self._i64(whole_word_ids if whole_word_ids is not None else torch.zeros_like(input_ids), dev)
+        attention_mask = self._i64(attention_mask if attention_mask is not None else (input_ids != self.config.pad_token_id).long(), dev)
+        labels = self._i64(labels, dev)
+        self._check_targets(input_ids.shape[0], labels)
+        q = None if trie is None else self._item_loss_setup(trie, temperature, excluded_items, input_ids.shape[0], 0, 1.0, item_head)
+        nll = self._engine_forward(input_ids, whole_word_ids, attention_mask, labels, q, inference=True)
+        return (-nll).view(labels.shape)
+
+    def preference_step(self, input_ids, whole_word_ids, attention_mask, labels, output_attention, trie, num_negatives, preference="pl", pref_depth=1,
+                        pref_beta=0.1, pref_sft_coef=0.0, pref_length_normalize=False, ref_model=None, negatives="slate", temperature=1.0,
+                        excluded_items=None, item_head=None, seed=None, streams=None):
+        """One preference step on negatives drawn from the model itself: (1) `num_negatives` = S items per user from the trie --
+        `negatives="slate"`: `sample_slates(slate_size=S)`, S DISTINCT items; "sample": `sample_items(num_samples=S)`, i.i.d. draws; (2)
+        `policy_batch` builds the grouped batch [B, S + 1, To], slot 0 = the gold target `labels` [B, T], and the hit reward; (3) the list of
+        every user is the gold target and the draws that are NOT the gold item (`pref_mask` = [1, hit == 0], formed on the device); (4)
+        `ref_model.sequence_logprobs` of the grouped labels (a `frozen_copy()`; None = reference-free); (5)
+        `loss_and_backward(preference=...)`.  The defaults are softmax-DPO (Plackett-Luce, depth 1): the gold against the listed negatives.
+        Returns the loss; `last_policy_batch` (the dict of `policy_batch` plus "pref_mask" and "sampled") and `last_pref_stats` stay on the
+        device, no host sync.  Every refusal is raised before anything is drawn.  Not built: reward-ordered draws (order `labels` yourself and
+        call `loss_and_backward`), per-user weights, a SimPO margin, entropy / KL regularisers beside the objective."""
+        if trie is None:
+            raise ValueError("preference_step needs trie=...: the draws and the item loss share it")
+        if preference is None:
+            raise ValueError('preference_step needs preference="pl" | "ipo"')
+        self._pref_args(preference, pref_beta, pref_depth, pref_sft_coef)
+        if negatives not in ("slate", "sample"):
+            raise ValueError(f'negatives={negatives!r}: "slate" (distinct items, sample_slates) or "sample" (i.i.d. draws, sample_items)')
+        if isinstance(num_negatives, bool) or not isinstance(num_negatives, int) or num_negatives < 1:
+            raise ValueError(f"num_negatives={num_negatives!r}: an integer >= 1 (draws per user)")
+        S = int(num_negatives)
+        trie = self._compiled_trie(trie)
+        item_head = self._item_head_mode(item_head, trie)
+        if negatives == "slate":
+            if trie.grafted:
+                raise ValueError('negatives="slate": a trie with an appended trie (Trie.append) is a DAG, which sample_slates refuses; use negatives="sample"')
+            if S > self.SLATE_MAX_K or S > int(self.wide_max_rows):
+                raise ValueError(f'negatives="slate": num_negatives={S} exceeds min(SLATE_MAX_K, wide_max_rows) = '
+                                 f'{min(self.SLATE_MAX_K, int(self.wide_max_rows))}; use negatives="sample"')
+        input_ids = torch.as_tensor(input_ids)
+        B = int(input_ids.shape[0])
+        Ts = max(2, int(trie.max_depth))
+        labels, output_attention = torch.as_tensor(labels), torch.as_tensor(output_attention)
+        G, _ = self._check_policy_shapes(B, S, Ts, labels, output_attention, 1)
+        if G > self.PREF_MAX_TARGETS:
+            raise ValueError(f"num_negatives={S}: G = {G} targets per user exceed the limit G <= {self.PREF_MAX_TARGETS}")
+        if negatives == "slate":
+            drawn = self.sample_slates(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, slate_size=S,
+                                       num_slates=1, temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
+        else:
+            drawn = self.sample_items(input_ids=input_ids, attention_mask=attention_mask, whole_word_ids=whole_word_ids, trie=trie, num_samples=S,
+                                      temperature=temperature, excluded_items=excluded_items, seed=seed, streams=streams)
+        pb = self.policy_batch(drawn["sequences"], labels, output_attention, S, rewards=None, baseline="none", policy_coef=1.0, sft_coef=1.0)
+        pmask = torch.cat([torch.ones(B, 1, dtype=torch.int32, device=pb["rewards"].device), (pb["rewards"] == 0).to(torch.int32)], dim=1)
+        ref_lp = None
+        if ref_model is not None:
+            ref_lp = ref_model.sequence_logprobs(input_ids, whole_word_ids, attention_mask, pb["labels"], trie=trie, temperature=temperature,
+                                                 excluded_items=excluded_items, item_head=item_head)
+        loss = self.loss_and_backward(input_ids, whole_word_ids, attention_mask, pb["labels"], pb["output_attention"], trie=trie, temperature=temperature,
+                                      excluded_items=excluded_items, item_head=item_head, preference=preference, pref_beta=pref_beta,
+                                      ref_logprobs=ref_lp, pref_mask=pmask, pref_depth=pref_depth, pref_length_normalize=pref_length_normalize,
+                                      pref_sft_coef=pref_sft_coef)
+        pb["pref_mask"], pb["sampled"] = pmask, drawn
+        self.last_policy_batch, self.last_policy_stats = pb, pb["stats"]
+        return loss
 
     def _policy_args(self, num_samples, baseline, policy_coef, sft_coef, token_sum, adv_eps):
         """the checked scalars of policy_batch / policy_step: (S, baseline code, policy_coef, sft_coef, token_sum, adv_eps, with_gold)"""

@@ -116,6 +116,21 @@ def parse_runner_args(parser):
                         "non-default --policy_baseline.  0 = off, nothing changes.")
     parser.add_argument("--policy_slate_estimator", type=str, default="normalized", choices=["normalized", "unbiased"], help="normalized = weights "
                         "and baseline normalised by the slate's own weight sum (biased, consistent, lower variance; K >= 2); unbiased = p / q alone")
+    parser.add_argument("--train_preference", type=str, default="", choices=["", "pl", "ipo"], help="pl | ipo = preference fine-tuning "
+                        "(P5T5Native.preference_step; needs --train_item_loss 1 and the native model): every step draws --pref_negatives items per user "
+                        "from the model's own distribution on the item trie and trains the gold item against the draws that are not the gold item.  pl = "
+                        "Plackett-Luce with --pref_depth (1 = softmax-DPO; one negative = DPO), ipo = IPO.  Not with --train_policy_samples, "
+                        "--item_loss_top_k / --item_loss_top_p or the item-loss regularisers.  Empty = off, nothing changes.")
+    parser.add_argument("--pref_negatives", type=int, default=4, help="S sampled negatives per user")
+    parser.add_argument("--pref_beta", type=float, default=0.1, help="beta: the scale of the log-probability ratios (> 0)")
+    parser.add_argument("--pref_depth", type=int, default=1, help="Plackett-Luce depth (1 = softmax-DPO; 0 = the full order)")
+    parser.add_argument("--pref_sft_coef", type=float, default=0.0, help="weight of the gold item's masked-mean NLL beside the preference loss")
+    parser.add_argument("--pref_length_normalize", type=int, default=0, choices=[0, 1], help="1 = sequence log-probabilities are divided by their "
+                        "number of tokens")
+    parser.add_argument("--pref_ref", type=str, default="init", choices=["init", "none"], help="reference policy: init = a frozen copy of the model's "
+                        "weights when the runner is built; none = reference-free")
+    parser.add_argument("--pref_negatives_mode", type=str, default="slate", choices=["slate", "sample"], help="slate = S distinct items per user "
+                        "(stochastic beam search); sample = S i.i.d. draws")
     parser.add_argument("--resume", type=int, default=0, help="continue from <model_path>.resume when it exists (weights + optimizer "
                         "moments + schedule position + epoch/step + dropout and data-order state; the reference saves weights only).")
     parser.add_argument("--save_steps", type=int, default=0, help="with --resume: also write the resume file every N optimizer steps "
@@ -153,7 +168,7 @@ def policy_seed(seed, step, micro, rank):
     return mix(mix(mix(mix(int(seed) + 0x9E3779B9) ^ (int(step) & 0xFFFFFFFF)) ^ (int(micro) & 0xFFFFFFFF)) ^ (int(rank) & 0xFFFFFFFF))
 
 
-def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=None, policy=None):
+def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=None, policy=None, preference=None):
     """One pass of the reference loop body (DistributedRunner.py:63-87): forward, masked-mean loss, backward, clip + AdamW +
     scheduler (fused), zero_grad.  `batch` = (input_ids, whole_word_ids, attention_mask, labels, output_attention) on the
     device.  With the native model the loss and its gradient seed are computed by the engine
@@ -173,7 +188,10 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
 
     `policy` (None = off): keyword arguments of `P5T5Native.policy_step` on top of `item_loss` -- {"num_samples", "baseline", "policy_coef",
     "sft_coef", "token_sum", "seed"} and, for slates, {"slate_size", "slate_estimator"}: the step samples, rewards, weights and trains in
-    one call."""
+    one call.
+
+    `preference` (None = off): keyword arguments of `P5T5Native.preference_step` on top of `item_loss` -- {"num_negatives", "preference",
+    "pref_depth", "pref_beta", "pref_sft_coef", "pref_length_normalize", "ref_model", "negatives", "seed"}."""
     kw = dict(item_loss or {})
     input_ids, whole_ids, attn, output_ids, output_attention = batch[:5]
     fused = getattr(model, "loss_and_backward", None)
@@ -191,6 +209,10 @@ def training_step(model, optimizer, batch, alpha=2, micro=0, accum=1, item_loss=
             raise ValueError("the on-policy step needs the native model and the item loss's keywords (trie=...)")
         kw.pop("ref_logits", None)         # (policy_step takes the reference's logits on the grouped labels itself)
         loss = model.policy_step(input_ids, whole_ids, attn, output_ids, output_attention, ref_model=ref_model, **kw, **policy)
+    elif preference is not None:
+        if not hasattr(model, "preference_step") or "trie" not in kw:
+            raise ValueError("the preference step needs the native model and the item loss's keywords (trie=...)")
+        loss = model.preference_step(input_ids, whole_ids, attn, output_ids, output_attention, **kw, **preference)
     elif fused is not None:
         loss = fused(input_ids, whole_ids, attn, output_ids, output_attention, **kw)
     else:
@@ -302,6 +324,7 @@ class DistributedRunner:
         self.generate_num = max(int(m.split("@")[1]) for m in self.metrics)
         self.get_testloader()
         self._policy = self._policy_flags()          # (raises now, not at the first step)
+        self._pref = self._pref_flags()
         if args.train:
             self.optimizer, self.scheduler = self.create_optimizer_and_scheduler()
         self.samples_per_sec = None
@@ -447,7 +470,16 @@ class DistributedRunner:
                 g0 = (n_batches - 1) // accum * accum
                 gsize = min(accum, n_total - g0)
                 micro = n_batches - 1 - g0
-                if self._policy is None:
+                if self._pref is not None:
+                    prf = dict(self._pref, seed=policy_seed(getattr(self.args, "seed", 0), self.optimizer.t, micro, self.rank))
+                    loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
+                                         micro=micro, accum=gsize, item_loss=self._item_loss_kw(), preference=prf)
+                    # (the one host read, once per --logging_step batches, as for the on-policy step)
+                    if self.rank == 0 and n_batches % max(1, int(self.args.logging_step)) == 0:
+                        st = [float(x) for x in self.model.last_pref_stats.cpu()]
+                        logging.info(f"preference step {self.optimizer.t} batch {n_batches}: loss {float(loss):.6f} "
+                                     + " ".join(f"{k} {v:.4f}" for k, v in zip(self.model.PREF_STATS, st)))
+                elif self._policy is None:
                     loss = training_step(self.model, self.optimizer, (input_ids, whole_ids, attn, output_ids, output_attention), self.args.alpha,
                                          micro=micro, accum=gsize, item_loss=self._item_loss_kw())
                 else:
@@ -591,6 +623,44 @@ class DistributedRunner:
         if K > 0:
             pol.update(slate_size=K, slate_estimator=estimator)
         return pol
+
+    def _pref_flags(self):
+        """--train_preference pl | ipo: the keyword arguments of `P5T5Native.preference_step` (None with the flag absent), every flag checked
+        here.  The reference policy (--pref_ref init) is a frozen copy of the weights the runner is built with: a --resume'd run is built
+        with the same weights as the run it continues, so both train against the same reference."""
+        kind = str(getattr(self.args, "train_preference", "") or "")
+        if not kind:
+            return None
+        if kind not in ("pl", "ipo"):
+            raise ValueError(f"--train_preference {kind}: pl or ipo")
+        if not int(getattr(self.args, "train_item_loss", 0)):
+            raise ValueError("--train_preference requires --train_item_loss 1 (the draws and the loss share the union item trie)")
+        if not hasattr(self.model, "preference_step"):
+            raise ValueError("--train_preference needs the native model (P5T5Native)")
+        if int(getattr(self.args, "train_policy_samples", 0)) != 0:
+            raise ValueError("--train_preference cannot be combined with --train_policy_samples: one objective per run")
+        if int(getattr(self.args, "item_loss_top_k", 0)) != 0 or float(getattr(self.args, "item_loss_top_p", 1.0)) != 1.0:
+            raise ValueError("--train_preference is not built for the truncated item loss (top_k / top_p): --item_loss_top_k / --item_loss_top_p")
+        if float(getattr(self.args, "item_loss_entropy_coef", 0.0)) != 0.0 or float(getattr(self.args, "item_loss_kl_coef", 0.0)) != 0.0:
+            raise ValueError("--train_preference is not built beside --item_loss_entropy_coef / --item_loss_kl_coef")
+        S, depth = int(getattr(self.args, "pref_negatives", 4)), int(getattr(self.args, "pref_depth", 1))
+        beta, sc = float(getattr(self.args, "pref_beta", 0.1)), float(getattr(self.args, "pref_sft_coef", 0.0))
+        if S < 1:
+            raise ValueError(f"--pref_negatives {S}: at least one sampled negative per user")
+        if not (math.isfinite(beta) and beta > 0.0):
+            raise ValueError(f"--pref_beta {beta}: a finite value > 0")
+        if depth < 0:
+            raise ValueError(f"--pref_depth {depth}: the Plackett-Luce depth (0 = the full order)")
+        if not math.isfinite(sc):
+            raise ValueError(f"--pref_sft_coef {sc}: a finite value")
+        ref, mode = str(getattr(self.args, "pref_ref", "init")), str(getattr(self.args, "pref_negatives_mode", "slate"))
+        if ref not in ("init", "none"):
+            raise ValueError(f"--pref_ref {ref}: init or none")
+        if mode not in ("slate", "sample"):
+            raise ValueError(f"--pref_negatives_mode {mode}: slate or sample")
+        return {"num_negatives": S, "preference": kind, "pref_depth": depth if depth > 0 else None, "pref_beta": beta, "pref_sft_coef": sc,
+                "pref_length_normalize": bool(int(getattr(self.args, "pref_length_normalize", 0))),
+                "ref_model": self.model.frozen_copy() if ref == "init" else None, "negatives": mode}
 
     def _item_loss_kw(self):
         """--train_item_loss 1: the keyword arguments of the trie-normalised item loss -- ONE union trie over the items of all training
